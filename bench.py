@@ -20,9 +20,14 @@ rank gets B/N images and the batch-coupled estimators (B x B log-density matrix,
 GLOBAL batch; `--scaling weak` keeps B images per GPU (global batch B x N).
 
 One JSON line on rank 0.  `value` = images/s of the whole job over EXACTLY --steps iterations bracketed by
-barrier + synchronize on both sides (max over ranks).  Also reported: HIP-event timing of the same iterations on the
-compute stream in 5 segments (`hip_event_ms_per_step`: segments + median), `roofline` = algorithmic FLOPs of the
-dominant kernel family / its HIP-event-timed duration vs the 157.3 TFLOP/s fp32 MFMA peak, `roofline_kernels` = the other
+barrier + synchronize on both sides (max over ranks); `ms_per_step` = the time of one of them.  A plain run does only that:
+set up, settle + warm up, time the steps, print the line (+ HIP-event timing of the same iterations on the compute stream in
+5 segments, `hip_event_ms_per_step`: segments + median).  `--dump-outputs DIR` writes what the last timed step handed its
+caller (loss, parameters after the step, their gradients; FactorVAE: also the discriminator's) as DIR/<name>.npy, float32;
+the inputs are seeded, so two builds can be compared output for output.
+
+`--full` adds everything else (each still switched off by its --no-* option): `host_issue_ms_per_step`,
+`roofline` = algorithmic FLOPs of the dominant kernel family / its HIP-event-timed duration vs the 157.3 TFLOP/s fp32 MFMA peak, `roofline_kernels` = the other
 two 32-channel conv families (bound "mfma") and the five thin (C = 1 / 3) conv launches of the step (bound "hbm":
 algorithmic bytes / HIP-event time vs 8 TB/s), `parity_check` = the first iteration of this very workload (same weights,
 batch, injected noise, the SAME optimizer construction as the timed loop) against the oracle, `drop_in` = the same
@@ -31,7 +36,8 @@ iteration as Trainer does under is_progress_bar=True), `configs` = the other thr
 legs (value, ms_per_step, fraction of the fp32 peak, parity, CPU baseline), `cpu_baseline` = the reference's CPU path
 timed on this box's host cores on a bounded sample: kind "reference" = the unmodified /root/reference Trainer (only where
 that directory exists: the build container), kind "port" = the oracle's restatement of it (the GPU boxes).
-`python bench.py --cpu-reference` (no GPU needed) times both CPU legs side by side.
+`python bench.py --cpu-reference` (no GPU needed) times both CPU legs side by side.  Only a --full run exits with status 3
+when its parity check fails.
 """
 import argparse
 import glob
@@ -674,10 +680,11 @@ def _free_port():
     return port
 
 
-def settle_rounds(step_fn, max_rounds=12, tol=0.015, min_round_ms=40.0):
+def settle_rounds(step_fn, max_rounds=12, tol=0.015, min_round_ms=40.0, until_steady=True):
     """Untimed settle phase: rounds of >= 5 steps and >= `min_round_ms` each until two consecutive rounds agree within `tol`
     (clocks, caches and the allocator reach their steady state: a leg that follows seconds of CPU work starts on an idle-clocked
-    GPU).  Returns the ms per step of each round."""
+    GPU).  until_steady=False: all `max_rounds` rounds (with min_round_ms=0 a fixed number of steps, so that the state the
+    timed steps start from does not depend on the box's clocks).  Returns the ms per step of each round."""
     rounds, n = [], 5
     for _ in range(max_rounds):
         torch.cuda.synchronize()
@@ -690,7 +697,7 @@ def settle_rounds(step_fn, max_rounds=12, tol=0.015, min_round_ms=40.0):
         if dt < min_round_ms:
             n = min(int(n * min_round_ms / max(dt, 1e-3)) + 1, 400)
             continue
-        if len(rounds) >= 2 and abs(rounds[-1] - rounds[-2]) <= tol * rounds[-1]:
+        if until_steady and len(rounds) >= 2 and abs(rounds[-1] - rounds[-2]) <= tol * rounds[-1]:
             break
     return rounds
 
@@ -860,6 +867,27 @@ def self_launch(argv, n):
     return rc
 
 
+# ---------------------------------------------------------------------------------- outputs
+MAX_DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss, model, loss_f):
+    """--dump-outputs: what the last timed step handed its caller -- the loss, the model's parameters after the step and their
+    gradients (the parameter / gradient arenas; FactorVAE: also the discriminator's) -- as <path>/<name>.npy in float32."""
+    import numpy as np
+    arrays = {"loss": loss.detach().reshape(1), "params": model.arena.flat, "grads": model.arena.grad}
+    disc = getattr(loss_f, "discriminator", None)
+    if disc is not None:
+        arrays["disc_params"], arrays["disc_grads"] = disc.arena.flat, disc.arena.grad
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > MAX_DUMP_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs exceed %d" % (total, MAX_DUMP_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 # ---------------------------------------------------------------------------------- main
 _MARKS = []
 
@@ -888,6 +916,10 @@ def main():
     ap.add_argument("--scaling", default=None, choices=["strong", "weak"],
                     help="N > 1: strong (default) = the config's batch is the global batch, split over the ranks; "
                          "weak = the config's batch per GPU")
+    ap.add_argument("--full", action="store_true", help="also the parity check, host issue time, rooflines, drop-in leg, CPU "
+                    "baseline and the other workloads' legs (a plain run: only the timed steps of the headline workload)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed (loss, "
+                    "parameters, gradients) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-parity-check", action="store_true")
@@ -902,7 +934,7 @@ def main():
     ap.add_argument("--replay", default=None, choices=["auto", "eager", "plan", "graph"],
                     help="how the launches of an iteration are issued (disvae_amd/graph.py)")
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the short legs of the other three BASELINE "
-                    "workloads (they run by default with N = 1 and the default workload)")
+                    "workloads (they run under --full with N = 1 and the default workload)")
     ap.add_argument("--no-drop-in", action="store_true", help="skip the drop-in leg (Adam(model.parameters()) + a host "
                     "sync per iteration)")
     ap.add_argument("--shard-which", default="single,torch,rccl", help="subset of the shard legs (profiling)")
@@ -980,7 +1012,7 @@ def main():
 
     parity = None
     mark("parity_check")
-    if world == 1 and not args.no_parity_check:
+    if args.full and world == 1 and not args.no_parity_check:
         parity = parity_check(cfg, B, device)
     mark("timed_leg")
 
@@ -1013,14 +1045,15 @@ def main():
 
     # settle phase (before the W warm-up steps, untimed): clocks, caches and the allocator reach their steady state.  Five
     # warm-up steps alone left the first timed segment 7 % slower than the last (BENCH_r03: 1.314 -> 1.222 ms).  Single
-    # process: rounds of 5 steps until two consecutive rounds agree within 1.5 % (at most 12 rounds); data parallel: a fixed 20
-    # steps (every rank must issue the same collectives).
+    # process: 12 rounds of 5 steps (two consecutive rounds agreed within 1.5 % after 25-30 steps on every box of round 6;
+    # a fixed count keeps the trained state of the timed steps, hence --dump-outputs, the same from run to run); data
+    # parallel: a fixed 20 steps (every rank must issue the same collectives).
     settle = []
     if ddp:
         for _ in range(20):
             trainer._train_iteration_async(data, storer)
     else:
-        settle = settle_rounds(lambda: trainer._train_iteration_async(data, storer), min_round_ms=0.0)
+        settle = settle_rounds(lambda: trainer._train_iteration_async(data, storer), min_round_ms=0.0, until_steady=False)
     for _ in range(args.warmup):
         trainer._train_iteration_async(data, storer)
     # HIP events on the compute stream (torch's current stream = the stream the engine launches on) at the
@@ -1045,7 +1078,9 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     final_loss = float(loss.item())
-    host_ms = host_issue_ms(lambda: trainer._train_iteration_async(data, storer), n=20) if not ddp else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model, loss_f)
+    host_ms = host_issue_ms(lambda: trainer._train_iteration_async(data, storer), n=20) if args.full and not ddp else None
 
     def flush_c_stdio():
         # RCCL in this image prints a banner ("Hostname", "Librccl path") through C stdio, block-buffered on a pipe:
@@ -1098,7 +1133,7 @@ def main():
     if parity is not None:
         out["parity_check"] = parity
     mark("rooflines")
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         nimg = B if loss_name != "factor" else B // 2
         fams = kernel_rooflines(nimg, device)
         thin = thin_kernel_rooflines(nimg, C, device)
@@ -1120,7 +1155,7 @@ def main():
         if loss_name == "factor":
             out["roofline_kernels"] += disc_kernel_rooflines(B, device)
     mark("drop_in")
-    if world == 1 and not args.no_drop_in:
+    if args.full and world == 1 and not args.no_drop_in:
         d_steps = min(args.steps, 50)
         d_ms, _ = time_leg(cfg, B, device, d_steps, min(args.warmup, 10), drop_in="epoch")
         p_ms, _ = time_leg(cfg, B, device, d_steps, min(args.warmup, 10), drop_in=True)
@@ -1137,10 +1172,10 @@ def main():
                                                              "training.py:164: what tqdm's postfix needs)",
                                                 "over_timed_configuration": round(p_ms / ms, 3)}}
     mark("cpu_baseline")
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, B)
     mark("configs")
-    if world == 1 and not args.force_ddp and not args.no_extra_configs and name == "btcvae_celeba" and not (
+    if args.full and world == 1 and not args.force_ddp and not args.no_extra_configs and name == "btcvae_celeba" and not (
             args.batch or args.channels or args.loss):
         out["configs"] = [extra_config(n, device, steps=min(args.steps, 30), warmup=min(args.warmup, 10),
                                        with_cpu=not args.no_cpu_baseline, with_parity=not args.no_parity_check)

@@ -2,7 +2,7 @@
 
 Run in the build container only (the GPU box has no /root/reference):
 
-    python tests/golden/make_golden.py [--latent | --wide-latent | --metrics | --bench-size]
+    python tests/golden/make_golden.py [--latent | --wide-latent | --metrics | --bench-size | --checkpoints]
 
 The reference is imported unmodified with the two import shims of SURVEY.md section 8c
 (stub ``imageio``; ``numpy.product = numpy.prod``).  Noise is recorded by wrapping
@@ -219,7 +219,38 @@ def metrics_case():
     return out
 
 
+CHECKPOINTS = ["btcvae_dsprites", "factor_celeba", "VAE_mnist"]
+
+
+def checkpoint_case(name):
+    """results/<name>/ of the reference checkout without its trained weights: specs.json verbatim, and model.pt -- torch's
+    legacy serialisation (pickled header, then per storage an int64 element count and its raw bytes) -- as its header and the
+    element counts of its storages.  tests/test_host_logic.py rebuilds the file with seeded values in the storages."""
+    d = os.path.join(REF, "results", name)
+    raw = open(os.path.join(d, "model.pt"), "rb").read()
+    state = torch.load(os.path.join(d, "model.pt"), map_location="cpu")
+    assert all(v.dtype == torch.float32 for v in state.values())
+    assert len({v.untyped_storage().data_ptr() for v in state.values()}) == len(state)
+    off = len(raw) - sum(8 + v.untyped_storage().nbytes() for v in state.values())
+    header, numel = raw[:off], []
+    while off < len(raw):
+        n = int(np.frombuffer(raw, dtype="<i8", count=1, offset=off)[0])
+        numel.append(n)
+        off += 8 + 4 * n
+    assert off == len(raw) and len(numel) == len(state)
+    specs = open(os.path.join(d, "specs.json"), "rb").read()
+    return {name + "_header": np.frombuffer(header, dtype=np.uint8), name + "_numel": np.array(numel, dtype=np.int64),
+            name + "_specs": np.frombuffer(specs, dtype=np.uint8)}
+
+
 def main():
+    if "--checkpoints" in sys.argv:      # only the reference checkpoint layouts (results/*/model.pt + specs.json)
+        out = {}
+        for name in CHECKPOINTS:
+            out.update(checkpoint_case(name))
+        np.savez_compressed(os.path.join(HERE, "reference_checkpoints.npz"), **out)
+        print("checkpoints:", {n: int(out[n + "_numel"].sum()) for n in CHECKPOINTS})
+        return
     if "--metrics" in sys.argv:          # only the MIG / AAM fixture (the training-step fixtures stay as committed)
         out = metrics_case()
         np.savez_compressed(os.path.join(HERE, "metrics.npz"), **out)

@@ -155,17 +155,33 @@ def test_allocation_generation_invalidates_plan_keys():
     assert _lib.ALLOC_GEN[0] == g0 + 1
 
 
-REF_RESULTS = "/root/reference/results"
+REF_CHECKPOINTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_checkpoints.npz")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_RESULTS), reason="reference checkpoints only exist in the build container")
+def _reference_checkpoint(name, d):
+    """results/<name>/ as the reference wrote it (recorded by tests/golden/make_golden.py --checkpoints): specs.json verbatim,
+    model.pt = the reference's file (torch's legacy serialisation: its pickled header, then per storage an int64 element
+    count and the raw fp32 values) with seeded values in place of the trained weights."""
+    import numpy as np
+    g = np.load(REF_CHECKPOINTS)
+    with open(os.path.join(d, "specs.json"), "wb") as f:
+        f.write(g[name + "_specs"].tobytes())
+    rng = np.random.default_rng(1234)
+    with open(os.path.join(d, "model.pt"), "wb") as f:
+        f.write(g[name + "_header"].tobytes())
+        for n in g[name + "_numel"]:
+            f.write(np.array(n, dtype="<i8").tobytes())
+            f.write(rng.standard_normal(int(n), dtype=np.float32).astype("<f4").tobytes())
+
+
 @pytest.mark.parametrize("name", ["btcvae_dsprites", "factor_celeba", "VAE_mnist"])
-def test_reference_checkpoints_load_into_the_native_model(name):
+def test_reference_checkpoints_load_into_the_native_model(name, tmp_path):
     """results/*/model.pt + specs.json written by the reference load through the native
     load_model (modelIO.py:81-153) -- same state_dict keys / shapes, every tensor bit-identical, weights land in the
     flat parameter arena that the HIP engine reads."""
     from disvae_amd.utils.modelIO import load_model, load_metadata
-    d = os.path.join(REF_RESULTS, name)
+    d = str(tmp_path)
+    _reference_checkpoint(name, d)
     meta = load_metadata(d)
     model = load_model(d, is_gpu=False)
     state = torch.load(os.path.join(d, "model.pt"), map_location="cpu")
@@ -397,6 +413,31 @@ def test_bench_starts_its_own_ranks_for_gpus_above_one(monkeypatch):
     monkeypatch.undo()
     assert out.getvalue().splitlines()[-1] == '{"value": 1}'
     assert seen["cmd"][5] == "2" and seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_bench_dump_outputs_writes_the_step_results_as_float32(tmp_path):
+    """--dump-outputs: the loss, the parameter and gradient arenas (FactorVAE: also the discriminator's) as <name>.npy, float32,
+    within the 64 MB bound"""
+    from disvae_amd.models.vae import init_specific_model
+    from disvae_amd.models.discriminator import Discriminator
+    b = _bench_module()
+    model = init_specific_model("Burgess", (3, 64, 64), 10)
+    model.arena.grad.normal_()
+
+    class FactorLoss:
+        discriminator = Discriminator(latent_dim=10)
+    b.dump_outputs(str(tmp_path / "vae"), torch.tensor(3.5), model, object())
+    b.dump_outputs(str(tmp_path / "factor"), torch.tensor(3.5), model, FactorLoss())
+    assert sorted(os.listdir(tmp_path / "vae")) == ["grads.npy", "loss.npy", "params.npy"]
+    names = sorted(os.listdir(tmp_path / "factor"))
+    assert names == ["disc_grads.npy", "disc_params.npy", "grads.npy", "loss.npy", "params.npy"]
+    arrays = {n: np.load(str(tmp_path / "factor" / n)) for n in names}
+    assert all(a.dtype == np.float32 for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= b.MAX_DUMP_BYTES
+    assert arrays["loss.npy"].tolist() == [3.5]
+    assert np.array_equal(arrays["params.npy"], model.arena.flat.numpy())
+    assert np.array_equal(arrays["grads.npy"], model.arena.grad.numpy())
+    assert np.array_equal(arrays["disc_params.npy"], FactorLoss.discriminator.arena.flat.numpy())
 
 
 def test_bench_cpu_baseline_leg_runs_the_port_and_calibrates_threads_once(monkeypatch):

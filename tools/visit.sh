@@ -7,7 +7,7 @@
 #   fused     the round-3 kernel tests only (tests/test_gpu_fused_core.py + FUSED_EXTRA)
 #   tests     the whole -m gpu suite (PYTEST_ARGS to narrow it)
 #   smoke     __graft_entry__.smoke()
-#   bench     python bench.py (BENCH_ARGS; default run = headline + drop-in + the other three configs + CPU baseline)
+#   bench     python bench.py (BENCH_ARGS, default --full = headline + parity + rooflines + drop-in + the other configs + CPU baseline)
 #   sweep     short bench lines at B = 64 / 128 / 256 / 1024 (btcvae 3ch) and the dsprites / factor configs
 #   absweep   A/B of the host-side schedule knobs (DVAE_DEBUG=1) over the batch size
 #   ab2       alternating A/B runs (needs a --debug build for the grid caps)
@@ -23,6 +23,7 @@ cd "$REPO"
 mkdir -p gpurun_out
 TAG=${TAG:-visit}
 STEPS=${STEPS:-"tests smoke bench"}
+BENCH_ARGS=${BENCH_ARGS:---full}
 has() { case " $STEPS " in *" $1 "*) return 0;; *) return 1;; esac; }
 echo "== host: $(nproc) cpus; $(rocm-smi --showproductname 2>/dev/null | grep -m1 -i 'card series' || true)"
 if has probe; then echo "== probe"; timeout 120 tools/ubench/mfma4x4_probe 2>&1 | tail -n 14 | tee gpurun_out/${TAG}_probe.txt; fi
