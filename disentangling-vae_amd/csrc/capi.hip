@@ -150,6 +150,26 @@ int dvae_u8_to_f32(const uint8_t* src, float* dst, long n, void* stream) {
   return launch_u8_to_f32(src, dst, n, (hipStream_t)stream);
 }
 
+int dvae_image_grid_u8(const float* imgs, long n, int C, int H, int W, int nrow, int padding, float pad_value, int upsample,
+                       uint8_t* out, void* stream) {
+  DVAE_CHECK_ARG(imgs && out && n > 0 && (C == 1 || C == 3) && H > 0 && W > 0 && nrow > 0 && padding >= 0 && upsample >= 1);
+  return launch_image_grid_u8(imgs, n, C, H, W, nrow, padding, pad_value, upsample, out, (hipStream_t)stream);
+}
+
+int dvae_image_grid_shape(long n, int H, int W, int nrow, int padding, int upsample, long* height, long* width) {
+  DVAE_CHECK_ARG(height && width && n > 0 && H > 0 && W > 0 && nrow > 0 && padding >= 0 && upsample >= 1);
+  long gh, gw;
+  int xmaps, pad;
+  if (image_grid_geom(n, H, W, nrow, padding, upsample, &gh, &gw, &xmaps, &pad) != 0) {
+    set_error("dvae_image_grid_shape: grid of %ld images of %dx%d (nrow %d, padding %d, upsample %d) is too large", n, H, W,
+              nrow, padding, upsample);
+    return -1;
+  }
+  *height = gh;
+  *width = gw;
+  return 0;
+}
+
 int dvae_u8_fused_supported(int C, int H, int W) { return u8_fused_shape(C, H, W, 32) ? 1 : 0; }
 
 int dvae_conv4s2_fwd_u8(const uint8_t* x, const float* w, const float* b, float* y, int N, int Cin, int H, int W,

@@ -200,6 +200,9 @@ int launch_wgrad_thin_u8(const uint8_t* x, const float* small, float* dw, float*
 int launch_kl_normal_bwd(const float* g, const float* mu, const float* lv, float* dmu, float* dlv, int B, int D, hipStream_t s);
 int launch_reduce_sum(const float* src, long n, float scale, float* dst, hipStream_t s);
 int launch_u8_to_f32(const uint8_t* src, float* dst, long n, hipStream_t s);
+int image_grid_geom(long n, int H, int W, int nrow, int padding, int upsample, long* gh, long* gw, int* xmaps, int* pad);
+int launch_image_grid_u8(const float* imgs, long n, int C, int H, int W, int nrow, int padding, float pad_value, int upsample,
+                         uint8_t* out, hipStream_t s);   // viz.hip
 
 size_t wgrad32_ws_floats();
 size_t wgrad_thin_ws_floats();

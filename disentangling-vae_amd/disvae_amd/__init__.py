@@ -25,5 +25,6 @@ if "GPU_MAX_HW_QUEUES" not in _os.environ:
 from .models.vae import init_specific_model  # noqa: E402
 from .training import Trainer  # noqa: E402
 from .evaluate import Evaluator  # noqa: E402
+from .visualize import Visualizer, GifTraversalsTraining  # noqa: E402
 
-__all__ = ["init_specific_model", "Trainer", "Evaluator"]
+__all__ = ["init_specific_model", "Trainer", "Evaluator", "Visualizer", "GifTraversalsTraining"]

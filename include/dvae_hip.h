@@ -394,6 +394,22 @@ int dvae_set_coef(float* coef, float c0, float c1, float c2, float c3, float c4,
 /* out[i] = a[i] + b[i] (n elements), helper for merging latent gradients (quirk Q1).       */
 int dvae_add(const float* a, const float* b, float* out, long n, void* stream);
 
+/* ---- pictures of a batch (new: the visualizer's image grids, utils/visualize.py:124-135) ---------------------------------
+ * imgs fp32 [n][C][H][W] (C = 1 or 3) -> out uint8 [gh][gw][3], RGB, row-major: what F.interpolate(nearest, scale_factor=upsample)
+ * + torchvision make_grid(nrow, padding, pad_value) + make_grid_img / save_image produce, bit for bit:
+ *   - upsampling: out pixel (y, x) of an image reads (y / upsample, x / upsample), upsample >= 1;
+ *   - xmaps = min(nrow, n) images per row, ceil(n / xmaps) rows; image k at row k / xmaps, column k % xmaps, its top-left corner at
+ *     (row * (H*upsample + padding) + padding, column * (W*upsample + padding) + padding); every other byte (unfilled cells too) is
+ *     pad_value; n == 1: no padding at all (make_grid returns the single image);
+ *   - C = 1 is replicated to the three channels;
+ *   - value v -> (uint8) clamp(fl(fl(v * 255) + 0.5), 0, 255): two fp32 roundings, no fused multiply-add, truncation.
+ * gh, gw: dvae_image_grid_shape.  out holds gh * gw * 3 bytes (written with 16-byte stores when it is 16-byte aligned).      */
+int dvae_image_grid_u8(const float* imgs, long n, int C, int H, int W, int nrow, int padding, float pad_value, int upsample,
+                       uint8_t* out, void* stream);
+/* Host only (no launch, no device access): *height, *width (HOST pointers) <- gh, gw of dvae_image_grid_u8 with these
+ * arguments; <0 when they are invalid.  (Replayable like the launching entry points: it only writes the two values again.)   */
+int dvae_image_grid_shape(long n, int H, int W, int nrow, int padding, int upsample, long* height, long* width);
+
 /* ---- torch.optim.Adam's update as one launch (main.py:208, losses.py:238: the optimizers; training.py:158,
  * losses.py:307-308: their step()) ------------------------------------------------------------------------------------
  * The optimizer object, its hyper-parameters and its state tensors stay the caller's (torch's): this runs the element-wise
