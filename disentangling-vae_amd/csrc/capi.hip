@@ -170,6 +170,28 @@ int dvae_image_grid_shape(long n, int H, int W, int nrow, int padding, int upsam
   return 0;
 }
 
+int dvae_recon_rows_ws_floats(long n_img, int K, long row_elems, long* floats) {
+  DVAE_CHECK_ARG(floats && n_img > 0 && K > 0 && row_elems > 0 && row_elems % 4 == 0);
+  *floats = recon_rows_ws_floats(n_img, K, row_elems);
+  return 0;
+}
+
+int dvae_recon_rows(const float* recon, const void* target, int target_u8, long n_img, int K, long row_elems, int dist,
+                    float* ws, float* rec_rows, void* stream) {
+  DVAE_CHECK_ARG(recon && target && rec_rows && n_img > 0 && K > 0 && row_elems > 0 && row_elems % 4 == 0);
+  DVAE_CHECK_ARG(dist == DVAE_REC_BERNOULLI || dist == DVAE_REC_GAUSSIAN || dist == DVAE_REC_LAPLACE);
+  DVAE_CHECK_ARG(((uintptr_t)recon & 15) == 0 && ((uintptr_t)target & (target_u8 ? 3 : 15)) == 0);
+  return launch_recon_rows(recon, target, target_u8 ? 1 : 0, n_img, K, row_elems, dist, ws, rec_rows, (hipStream_t)stream);
+}
+
+int dvae_iw_loglik(const float* mu, const float* logvar, const float* z, const float* eps, const float* rec_rows, long n_img,
+                   int nk, int D, int K, int first, int last, float* state, float* loglik, float* kl, void* stream) {
+  DVAE_CHECK_ARG(mu && logvar && n_img > 0 && D > 0 && (state || kl));
+  DVAE_CHECK_ARG(!state || (z && eps && rec_rows && nk > 0 && K >= nk && (!last || loglik)));
+  return launch_iw_loglik(mu, logvar, z, eps, rec_rows, n_img, nk, D, K, first ? 1 : 0, last ? 1 : 0, state, loglik, kl,
+                          (hipStream_t)stream);
+}
+
 int dvae_u8_fused_supported(int C, int H, int W) { return u8_fused_shape(C, H, W, 32) ? 1 : 0; }
 
 int dvae_conv4s2_fwd_u8(const uint8_t* x, const float* w, const float* b, float* y, int N, int Cin, int H, int W,

@@ -203,6 +203,11 @@ int launch_u8_to_f32(const uint8_t* src, float* dst, long n, hipStream_t s);
 int image_grid_geom(long n, int H, int W, int nrow, int padding, int upsample, long* gh, long* gw, int* xmaps, int* pad);
 int launch_image_grid_u8(const float* imgs, long n, int C, int H, int W, int nrow, int padding, float pad_value, int upsample,
                          uint8_t* out, hipStream_t s);   // viz.hip
+long recon_rows_ws_floats(long n_img, int K, long row_elems);   // loglik.hip
+int launch_recon_rows(const float* recon, const void* target, int target_u8, long n_img, int K, long row_elems, int dist,
+                      float* ws, float* rec_rows, hipStream_t s);
+int launch_iw_loglik(const float* mu, const float* logvar, const float* z, const float* eps, const float* rec_rows, long n_img,
+                     int nk, int D, int K, int first, int last, float* state, float* loglik, float* kl, hipStream_t s);
 
 size_t wgrad32_ws_floats();
 size_t wgrad_thin_ws_floats();

@@ -126,6 +126,9 @@ SIGNATURES = {
     "dvae_swap_outer": [_p, _p, _i, _i, _l, _p],
     "dvae_image_grid_u8": [_p, _l, _i, _i, _i, _i, _i, ctypes.c_float, _i, _p, _p],
     "dvae_image_grid_shape": [_l, _i, _i, _i, _i, _i, _p, _p],
+    "dvae_recon_rows_ws_floats": [_l, _i, _l, _p],
+    "dvae_recon_rows": [_p, _p, _i, _l, _i, _l, _i, _p, _p, _p],
+    "dvae_iw_loglik": [_p, _p, _p, _p, _p, _l, _i, _i, _i, _i, _i, _p, _p, _p, _p],
     "dvae_stream_order": [_p, _p],
     "dvae_stream_create": [_p],
     "dvae_event_record": [_i, _p],

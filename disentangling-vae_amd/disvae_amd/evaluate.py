@@ -11,6 +11,8 @@
   log-densities + logsumexp per entropy, the kernel family of the beta-TCVAE estimator -- as ONE HIP launch sequence per
   entropy (``dvae_latent_entropy``) instead of 1 000 Python-driven [N, D, 10] torch chunks.  The few-element table
   arithmetic (mutual information, sort, MIG, AAM) stays on the host as in the reference.
+* Importance-weighted log-likelihood (``compute_log_likelihood``, new): the mean over the data set of likelihood.log_likelihood
+  (K samples per image, a private seeded generator), written to log_likelihood.log by ``__call__(is_log_likelihood=True)``.
 """
 import logging
 import math
@@ -24,12 +26,14 @@ import torch
 from . import _lib
 from ._lib import call, ptr
 from .engine import _stream
+from .likelihood import _ScorePasses, check_rec_dist, log_likelihood
 from .models.losses import FactorKLoss
 from .utils.modelIO import save_metadata
 
 TEST_LOSSES_FILE = "test_losses.log"
 METRICS_FILENAME = "metrics.log"
 METRIC_HELPERS_FILE = "metric_helpers.pth"
+LOG_LIKELIHOOD_FILE = "log_likelihood.log"
 
 
 class Evaluator:
@@ -44,8 +48,9 @@ class Evaluator:
         self.reference_early_return = reference_early_return
         self.logger.info("Testing Device: {}".format(self.device))
 
-    def __call__(self, data_loader, is_metrics=False, is_losses=True):
-        """evaluate.py:60-95."""
+    def __call__(self, data_loader, is_metrics=False, is_losses=True, is_log_likelihood=False, n_samples=128):
+        """evaluate.py:60-95.  is_log_likelihood: also write compute_log_likelihood(data_loader, n_samples) to
+        log_likelihood.log (the return value stays the reference's (metric, losses))."""
         start = default_timer()
         is_still_training = self.model.training
         self.model.eval()
@@ -62,6 +67,12 @@ class Evaluator:
             self.logger.info('Losses: {}'.format(losses))
             os.makedirs(self.save_dir, exist_ok=True)
             save_metadata(losses, self.save_dir, filename=TEST_LOSSES_FILE)
+        if is_log_likelihood:
+            self.logger.info('Computing the importance-weighted log-likelihood...')
+            ll = self.compute_log_likelihood(data_loader, n_samples=n_samples)
+            self.logger.info('Log-likelihood: {}'.format(ll))
+            os.makedirs(self.save_dir, exist_ok=True)
+            save_metadata(ll, self.save_dir, filename=LOG_LIKELIHOOD_FILE)
         if is_still_training:
             self.model.train()
         self.logger.info('Finished evaluating after {:.1f} min.'.format((default_timer() - start) / 60))
@@ -80,6 +91,22 @@ class Evaluator:
             if self.reference_early_return:
                 return {k: sum(v) / n for k, v in storer.items()}
         return {k: sum(v) / len(v) for k, v in storer.items()}
+
+    def compute_log_likelihood(self, dataloader, n_samples=128, seed=0):
+        """Mean over the data set of the importance-weighted estimate of log p(x) (nats per image; likelihood.log_likelihood)
+        with n_samples samples of q(z|x) per image under the loss's rec_dist -- the bound itself for bernoulli, up to the
+        likelihood's missing normalising constant for gaussian / laplace.  The draws come from a private generator seeded with
+        `seed` (the same seed gives the same bits; the global random states are untouched); train / eval mode is restored."""
+        rec_dist = getattr(self.loss_f, "rec_dist", "bernoulli")
+        check_rec_dist(rec_dist)
+        if int(n_samples) < 1:
+            raise ValueError("n_samples must be >= 1, got %r" % (n_samples,))
+        dev = _ScorePasses.of(self.model).check_device()
+        gen = torch.Generator(device=dev).manual_seed(int(seed))
+        parts = [log_likelihood(self.model, data, n_samples=n_samples, rec_dist=rec_dist, generator=gen)
+                 for data, _ in dataloader]
+        per_image = torch.cat(parts).cpu().double()
+        return {"log_likelihood": per_image.mean().item(), "n_samples": int(n_samples), "rec_dist": rec_dist}
 
     # ------------------------------------------------------------------ MIG / AAM (evaluate.py:119-317)
     def compute_metrics(self, dataloader, sample_idx=None, n_samples=10000):

@@ -55,11 +55,17 @@ class _NativePasses:
         self._eng = None
         self._rows = 0
 
+    def check_device(self):
+        """The model's device; DvaeHipError unless it is a GPU (there is no CPU path)."""
+        dev = self.model.arena.flat.device
+        if dev.type != "cuda":
+            raise _lib.DvaeHipError("the native VAE computes only on an MI355X (model is on %s); move it with .to('cuda') -- "
+                                    "there is no CPU fallback" % dev)
+        return dev
+
     def _buffers(self, rows):
         m = self.model
-        if m.arena.flat.device.type != "cuda":
-            raise _lib.DvaeHipError("the native VAE computes only on an MI355X (model is on %s); move it with .to('cuda') -- "
-                                    "there is no CPU fallback" % m.arena.flat.device)
+        self.check_device()
         if self._eng is None:
             self._eng = VAEEngine(m.img_size, m.latent_dim, m.arena)
         want = min(self.MAX_ROWS, 1 << max(0, int(rows) - 1).bit_length())

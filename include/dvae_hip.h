@@ -410,6 +410,36 @@ int dvae_image_grid_u8(const float* imgs, long n, int C, int H, int W, int nrow,
  * arguments; <0 when they are invalid.  (Replayable like the launching entry points: it only writes the two values again.)   */
 int dvae_image_grid_shape(long n, int H, int W, int nrow, int padding, int upsample, long* height, long* width);
 
+/* ---- per-image scores (new: the reference reports batch means only) -------------------------------------------------------
+ * Per-row reconstruction term of K decoded samples per image:
+ *   rec_rows[i*K + k] = sum over the row_elems elements of recon row i*K + k of the element term of losses.py:394-449 (bernoulli:
+ *   ATen's binary_cross_entropy with its -100 clamp; gaussian: mse(255 p, 255 x) / 255; laplace: 3 |p - x|) against target row i,
+ *   i < n_img, k < K.
+ * recon fp32 [n_img*K][row_elems] (16-byte aligned); target [n_img][row_elems]: fp32 (target_u8 == 0, 16-byte aligned) or uint8
+ * pixels (target_u8 != 0, 4-byte aligned; value v is float(v) / 255 as ToTensor computes it); row_elems a multiple of 4.
+ * Schedule: a workgroup per (image, 8 consecutive samples -- all of them when K < 8 --, column slice of 1024 elements); every
+ * thread loads ONE 16-byte quad of the target into registers and streams the same quad of the workgroup's reconstruction rows
+ * against it, so the target is read ceil(K / 8) times per image, each time reused for 8 rows.  Each row is summed in one fixed
+ * order that depends on row_elems only (4 elements of a thread, the waves of a slice, then the slices in order): the same inputs
+ * give the same bits on every run and at every n_img, K.
+ * ws: dvae_recon_rows_ws_floats floats (the per-slice sums of rows longer than 1024 elements; NULL when that is 0).           */
+int dvae_recon_rows(const float* recon, const void* target, int target_u8, long n_img, int K, long row_elems, int dist,
+                    float* ws, float* rec_rows, void* stream);
+/* Host only (no launch, no device access): *floats (a HOST pointer) <- the workspace dvae_recon_rows needs for these sizes
+ * (n_img * K * ceil(row_elems / 1024) when row_elems > 1024, else 0).  (Replayable: it only writes the value again.)         */
+int dvae_recon_rows_ws_floats(long n_img, int K, long row_elems, long* floats);
+/* Importance-weighted log-likelihood (Burda et al.), folded over the samples of n_img images, nk samples per image in this call:
+ *   row r = i*nk + j (sample j of this call of image i): z[r][D] (the decoder's input, dvae_reparam_kl_fwd's output), eps[r][D],
+ *   rec_rows[r] (dvae_recon_rows);  log w = -rec_rows[r] + log p(z) - log q(z|x) with
+ *   log p(z) = -1/2 sum_d z^2 and log q(z|x) = -1/2 sum_d (eps^2 + logvar[i][d])  (the two -D/2 log 2pi cancel; both dropped).
+ * state[n_img][2] = running (max, sum of exp(log w - max)) per image, updated in sample order j = 0 .. nk-1: first != 0 starts it
+ * (otherwise it continues a previous call over the earlier samples of the same images); last != 0 also writes
+ *   loglik[i] = max + log(sum) - log K      (K = the total number of samples per image over all calls).
+ * kl (may be NULL): kl[i][d] = 0.5 (-1 - logvar + mu^2 + e^logvar), the per-image value behind _kl_normal_loss's batch mean.
+ * state == NULL: only kl is written (z, eps, rec_rows, loglik unused).  Any D >= 1.                                        */
+int dvae_iw_loglik(const float* mu, const float* logvar, const float* z, const float* eps, const float* rec_rows, long n_img,
+                   int nk, int D, int K, int first, int last, float* state, float* loglik, float* kl, void* stream);
+
 /* ---- torch.optim.Adam's update as one launch (main.py:208, losses.py:238: the optimizers; training.py:158,
  * losses.py:307-308: their step()) ------------------------------------------------------------------------------------
  * The optimizer object, its hyper-parameters and its state tensors stay the caller's (torch's): this runs the element-wise
