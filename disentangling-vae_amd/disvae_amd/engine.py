@@ -111,6 +111,9 @@ class ParamArena:
 # (measured -1.5 %: profiles/r02_run12_tail_ab.txt)
 _TAIL_MAIN = ("conv3", "conv_64")
 
+# launch queues of the backward pass (VAEEngine._queue): the caller's stream and the two weight-gradient streams
+MAIN, SIDE, WG2 = 0, 1, 2
+
 
 _DEVICE_STREAMS = {}
 _WG2_STREAMS = {}
@@ -296,14 +299,14 @@ class VAEEngine:
         # is what small steps end on, and it now starts ~15 us sooner: 128 / 256 images 0.341 -> 0.330, 0.443 -> 0.431 ms,
         # btcvae 64x64x1 B = 256 0.412 -> 0.398, 1024 images 1.054 -> 1.048 ms (profiles/r06_s2_sched2.txt).  Mode 2 (in FRONT of
         # convT3's input gradient) wins another 1-2 % at 128 images and loses 1.6 % at 256, 0.7 % at 1024 (r06_s2_sched3.txt): used at
-        # 112-128 images only (decode_backward).
+        # 112-128 images only (_decode_convs_batch).
         # Moving the main stream's tail (tail_main) to the side stream loses 2-8 % at every small batch (same file).
         _et = knob("DVAE_EARLY_THIN", "auto")                          # (A/B knob: DVAE_DEBUG=1 only: 0 / 1 / 2 force a mode)
         self.early_thin_wgrad = 1 if _et == "auto" else int(_et)
         self.early_thin_auto = _et == "auto"
         self.sharded = False   # this step runs under data parallelism (set per step by the loss plugins, BaseLoss._streams)
         # the weight gradients on TWO side streams, each launched at the first fork behind the kernel that produces its last operand
-        # (decode_backward's `three` branch / _encode_backward_3s).  Set per step by the loss plugins (BaseLoss._streams: FactorVAE
+        # (_decode_backward_3q / _encode_backward_3q).  Set per step by the loss plugins (BaseLoss._streams: FactorVAE
         # from 2048 rows; slower for every other step measured).
         self.three_streams = False
         # steps of 129-320 images end on the side stream (its weight-gradient grid is the smaller one there, conv_wgrad_ws.hip): the
@@ -384,12 +387,15 @@ class VAEEngine:
             ent = self._fc_descs[key] = _lib.struct_of(cls, **fields)
         return ent[1]
 
-    # ---- fork / join of the side stream (weight-gradient kernels) ----------------------------------
-    def fork_side(self):
-        """Order the side stream after everything enqueued so far on the current stream.  A fork
-        costs the current stream ~6 us (event signal between hardware queues, profiles/r01_run19
+    # ---- fork / join of the side streams (weight-gradient kernels) ---------------------------------
+    def fork_side(self, wg2=False):
+        """Order the side stream (wg2: the second one, three_streams) after everything enqueued so far on the current
+        stream.  A fork costs the current stream ~6 us (event signal between hardware queues, profiles/r01_run19
         timeline), so the FC weight gradients fork once per chain, not once per layer."""
         if self.single_stream:
+            return
+        if wg2:
+            call("dvae_stream_order", _stream(), self._wg2.cuda_stream)
             return
         call("dvae_stream_order", _stream(), self._side.cuda_stream)
         hook, self._fork_hook = self._fork_hook, None
@@ -425,8 +431,17 @@ class VAEEngine:
     def _aux_raw(self):
         return _stream() if self.single_stream else self._aux.cuda_stream
 
-    def _side_wgrad_grouped(self, problems, stream=None):
-        """All FC weight gradients of `problems` = [(x, dy, dw, db, M, K, N)] (tensors) in ONE launch on the side stream
+    def _queue(self, q):
+        """(partial-sum workspace, hipStream_t) of launch queue q: MAIN = the current stream, SIDE / WG2 = the two
+        weight-gradient streams (single_stream: SIDE is the current stream as well, with a workspace of its own)."""
+        if q == MAIN:
+            return self._ws, _stream()
+        if q == SIDE:
+            return self._ws_side, self._side_raw()
+        return self._ws_wg2, self._wg2.cuda_stream
+
+    def _fc_wgrads(self, q, problems):
+        """All FC weight gradients of `problems` = [(x, dy, dw, db, M, K, N)] (tensors) in ONE launch on queue q
         (dvae_linear_wgrad_grouped): ~400 short-lived workgroups instead of six launches that each leave most of
         the chip idle and delay the conv weight gradients queued behind them."""
         key = tuple((ptr(x), ptr(dy), ptr(dw), ptr(db), M, K, N) for x, dy, dw, db, M, K, N in problems)
@@ -436,21 +451,20 @@ class VAEEngine:
                 self._fc_descs.clear()
                 _lib.note_alloc()
             ent = self._fc_descs[key] = _lib.wgrad_descs(key)
-        call("dvae_linear_wgrad_grouped", ent[1], len(problems), self._side_raw() if stream is None else stream)
+        call("dvae_linear_wgrad_grouped", ent[1], len(problems), self._queue(q)[1])
 
-    def _conv_wgrad(self, fn, *args, fork=True, main=False):
-        """Conv / convT weight gradient `fn(*args, ws, stream)`: off the dgrad critical path, so it
-        goes to the side stream (after a fork) and co-runs with the dgrad chain (main=True: the current stream).
+    def _wgrad(self, q, wgrad):
+        """Conv / convT weight gradient `wgrad` = (entry point, *arguments in front of workspace and stream) on queue q: off the
+        chain of input gradients, so on a side stream (behind a fork: the caller's business) beside that chain, or MAIN.
         (Capping the side stream's chip-filling launches at 96-224 workgroups so that the other stream's short kernels find
         free CUs measured 0.3-4.7 % SLOWER at 1024 images: profiles/r05_v23_side_cap_ab.txt.)"""
-        if fork and not main:
-            self.fork_side()
-        call(fn, *args, ptr(self._ws if main else self._ws_side), _stream() if main else self._side_raw())
+        ws, stream = self._queue(q)
+        call(*wgrad, ptr(ws), stream)
 
-    def _join_side(self):
+    def _join_side(self, wg2=False):
         if self.single_stream:
             return
-        call("dvae_stream_order", self._side.cuda_stream, _stream())
+        call("dvae_stream_order", (self._wg2 if wg2 else self._side).cuda_stream, _stream())
 
     # ------------------------------------------------------------------ input
     @property
@@ -608,24 +622,10 @@ class VAEEngine:
     def _fc_layers_bwd(self, buf, eps, dz2, dz3, dmu_x, dlv_x, scal, coef, n):
         """fc_chain_bwd for any latent dimension: dvae_linear_dgrad x 3, dvae_reparam_kl_bwd, x 3 (the launches of the
         autograd-compatible path: decode_backward / encode_backward without fc_chain)."""
-        s = _stream()
-        ws = ptr(self._ws)
-        D = self.latent_dim
-        P = self.p
-        call("dvae_linear_dgrad", ptr(buf.gd3), ptr(P("decoder.lin3.weight")), ptr(buf.d2), ACT_RELU, ptr(buf.gd2),
-             n, HIDDEN_DIM, HID * 16, ws, s)
-        call("dvae_linear_dgrad", ptr(buf.gd2), ptr(P("decoder.lin2.weight")), ptr(buf.d1), ACT_RELU, ptr(buf.gd1),
-             n, HIDDEN_DIM, HIDDEN_DIM, ws, s)
-        call("dvae_linear_dgrad", ptr(buf.gd1), ptr(P("decoder.lin1.weight")), None, ACT_NONE, ptr(buf.dz),
-             n, D, HIDDEN_DIM, ws, s)
+        self._dec_fc_dgrads(buf, n)
         call("dvae_reparam_kl_bwd", ptr(buf.dz), ptr(dz2), ptr(dz3), ptr(dmu_x), ptr(dlv_x), ptr(buf.mu), ptr(buf.logvar),
-             ptr(eps), ptr(scal), ptr(coef), ptr(buf.dml), n, D, s)
-        call("dvae_linear_dgrad", ptr(buf.dml), ptr(P("encoder.mu_logvar_gen.weight")), ptr(buf.h2), ACT_RELU, ptr(buf.gh2),
-             n, HIDDEN_DIM, 2 * D, ws, s)
-        call("dvae_linear_dgrad", ptr(buf.gh2), ptr(P("encoder.lin2.weight")), ptr(buf.h1), ACT_RELU, ptr(buf.gh1),
-             n, HIDDEN_DIM, HIDDEN_DIM, ws, s)
-        call("dvae_linear_dgrad", ptr(buf.gh1), ptr(P("encoder.lin1.weight")), ptr(buf.a_flat), ACT_RELU, ptr(buf.ga_flat),
-             n, HID * 16, HIDDEN_DIM, ws, s)
+             ptr(eps), ptr(scal), ptr(coef), ptr(buf.dml), n, self.latent_dim, _stream())
+        self._enc_fc_dgrads(buf, n)
 
     def fc_chain_bwd(self, buf, eps, dz2, dz3, dmu_x, dlv_x, scal, coef, n):
         """buf.gd3 -> gd2, gd1, dz, dml, gh2, gh1, ga_flat (rows < n) in ONE launch (dvae_fc_chain_bwd): the input gradients
@@ -710,302 +710,308 @@ class VAEEngine:
              ptr(buf.d3), B, HIDDEN_DIM, HID * 16, ACT_RELU, ws, s)
         self.decode_convs(buf, B, fuse_loss)
 
-    # ---- three-queue schedule of small steps ----------------------------------------------------------------------------
+    # ------------------------------------------------------------------ backward: WHAT is launched
+    def _dec_layers(self, buf, B, chain_ends):
+        """The decoder's conv layers in the order the backward pass meets them (convT3 first): [(h, wgrad, dgrad)] -- the layer's
+        input H, its weight-gradient launch (as _wgrad takes it) and its input-gradient launch (a complete call on the
+        current stream).  dgrad is None for the 4x4 layer when fc_chain_bwd computes it in its prologue (chain_ends)."""
+        s = _stream()
+        acts = [buf.d3] + buf.dec_act           # inputs of convT_64/convT1/convT2/convT3 (the first one NCHW = lin3's output)
+        gacts = [buf.gd3] + buf.dec_gact
+        names = self.dec_names + ["convT3"]
+        last = len(names) - 1
+        layers = []
+        dy, dy_layout = buf.g_logit, NCHW
+        for k in range(last, -1, -1):
+            lname, x_in, gx, h = "decoder.%s" % names[k], acts[k], gacts[k], 4 << k
+            cout = self.img_size[0] if k == last else HID
+            # the first decoder layer's input gradient leaves NCHW = (c,h,w) order, straight into gd3 (the
+            # gradient of lin3's output; ReLU mask = lin3's output d3 in the same order): no relayout pass
+            layout = NCHW if k == 0 else NHWC
+            wgrad = ("dvae_convT4s2_wgrad", ptr(x_in), layout, ptr(dy), dy_layout, ptr(self.g(lname + ".weight")),
+                     ptr(self.g(lname + ".bias")), B, HID, h, h, cout)
+            if k == 0 and chain_ends:
+                dgrad = None
+            elif cout == HID:
+                dgrad = ("dvae_conv32_down", ptr(dy), self._img(lname, "down"), None, ptr(x_in), ptr(gx), layout, B, h,
+                         ACT_NONE, s)
+            elif self.mask_bits:
+                dgrad = ("dvae_convT3_dgrad_bits", ptr(dy), ptr(self.p(lname + ".weight")), ptr(buf.bits_convT2), ptr(gx), B,
+                         cout, s)
+            else:
+                dgrad = ("dvae_convT4s2_dgrad", ptr(dy), dy_layout, ptr(self.p(lname + ".weight")), ptr(x_in), ptr(gx),
+                         layout, B, HID, h, h, cout, s)
+            layers.append((h, wgrad, dgrad))
+            dy, dy_layout = gx, NHWC
+        return layers
+
+    def _enc_layers(self, x, buf, B, fused_end):
+        """The encoder's conv layers in the order the backward pass meets them (conv1 last): [(name, h_in, wgrad, dgrad)] as in
+        _dec_layers.  The input gradient of layer k goes into buf.enc_gact[k - 1], masked by the ReLU of layer k - 1: by the
+        bit plane conv1's forward emitted where there is one (conv2 at the 64x64 geometry), else by the fp32 activation.
+        dgrad is None for conv1 (nothing to propagate to) and for the 4x4 layer when fc_chain_bwd's epilogue wrote its
+        input gradient (fused_end).  conv1's weight gradient reads the batch as it came: uint8 through dvae_*_u8."""
+        s = _stream()
+        c = self.img_size[0]
+        last = len(self.enc_names) - 1
+        layers = []
+        for k in range(last, -1, -1):
+            name, h_in = self.enc_names[k], self.enc_sizes[k] * 2
+            lname = "encoder.%s" % name
+            gw, gb = ptr(self.g(lname + ".weight")), ptr(self.g(lname + ".bias"))
+            # the last conv's output gradient is lin1's input gradient, (c,h,w) order = NCHW 4x4x32: read as such
+            dy, dy_layout = (buf.ga_flat, NCHW) if k == last else (buf.enc_gact[k], NHWC)
+            x_in, x_layout, cin = (buf.enc_act[k - 1], NHWC, HID) if k > 0 else (x, NCHW, c)
+            if k == 0 and x.dtype == torch.uint8:
+                wgrad = ("dvae_conv4s2_wgrad_u8", ptr(x), ptr(dy), gw, gb, B, c, h_in, h_in, HID)
+            else:
+                wgrad = ("dvae_conv4s2_wgrad", ptr(x_in), x_layout, ptr(dy), dy_layout, gw, gb, B, cin, h_in, h_in, HID)
+            if k == 0 or (k == last and fused_end):
+                dgrad = None
+            elif self.mask_bits and k == 1:
+                dgrad = ("dvae_conv32_up_bits", ptr(dy), self._img(lname, "up"), None, ptr(buf.bits_conv1),
+                         ptr(buf.enc_gact[0]), None, B, ACT_NONE, s)
+            else:
+                dgrad = ("dvae_conv32_up", ptr(dy), dy_layout, self._img(lname, "up"), None, ptr(x_in),
+                         ptr(buf.enc_gact[k - 1]), B, h_in // 2, ACT_NONE, s)
+            layers.append((name, h_in, wgrad, dgrad))
+        return layers
+
+    def _dec_fc_wgrads(self, z, buf, B):
+        """The decoder's three FC weight-gradient problems (_fc_wgrads)."""
+        g = self.g
+        return [(buf.d2, buf.gd3, g("decoder.lin3.weight"), g("decoder.lin3.bias"), B, HIDDEN_DIM, HID * 16),
+                (buf.d1, buf.gd2, g("decoder.lin2.weight"), g("decoder.lin2.bias"), B, HIDDEN_DIM, HIDDEN_DIM),
+                (z, buf.gd1, g("decoder.lin1.weight"), g("decoder.lin1.bias"), B, self.latent_dim, HIDDEN_DIM)]
+
+    def _enc_fc_wgrads(self, buf, B, dec):
+        """The encoder's three FC weight-gradient problems with the decoder's deferred ones (`dec`: three or none) between
+        them -- largest problems first (128, 128, 64, 64, 8, 8 tiles): the long-running workgroups start first."""
+        g = self.g
+        return ([(buf.a_flat, buf.gh1, g("encoder.lin1.weight"), g("encoder.lin1.bias"), B, HID * 16, HIDDEN_DIM)]
+                + dec[:1]
+                + [(buf.h1, buf.gh2, g("encoder.lin2.weight"), g("encoder.lin2.bias"), B, HIDDEN_DIM, HIDDEN_DIM)]
+                + dec[1:]
+                + [(buf.h2, buf.dml, g("encoder.mu_logvar_gen.weight"), g("encoder.mu_logvar_gen.bias"), B, HIDDEN_DIM,
+                    2 * self.latent_dim)])
+
+    def _fc_dgrads(self, layers, n):
+        """Input gradients of a stack of FC layers, one launch each: layers = [(dy, layer, x, dx, K, N)], x = the layer's input
+        (the ReLU mask of dx) or None."""
+        s = _stream()
+        ws = ptr(self._ws)
+        for dy, layer, x, dx, K, N in layers:
+            call("dvae_linear_dgrad", ptr(dy), ptr(self.p(layer + ".weight")), ptr(x), ACT_NONE if x is None else ACT_RELU,
+                 ptr(dx), n, K, N, ws, s)
+
+    def _dec_fc_dgrads(self, buf, n):
+        """buf.gd3 -> gd2, gd1, dz."""
+        self._fc_dgrads(((buf.gd3, "decoder.lin3", buf.d2, buf.gd2, HIDDEN_DIM, HID * 16),
+                         (buf.gd2, "decoder.lin2", buf.d1, buf.gd1, HIDDEN_DIM, HIDDEN_DIM),
+                         (buf.gd1, "decoder.lin1", None, buf.dz, self.latent_dim, HIDDEN_DIM)), n)
+
+    def _enc_fc_dgrads(self, buf, n):
+        """buf.dml -> gh2, gh1, ga_flat."""
+        self._fc_dgrads(((buf.dml, "encoder.mu_logvar_gen", buf.h2, buf.gh2, HIDDEN_DIM, 2 * self.latent_dim),
+                         (buf.gh2, "encoder.lin2", buf.h1, buf.gh1, HIDDEN_DIM, HIDDEN_DIM),
+                         (buf.gh1, "encoder.lin1", buf.a_flat, buf.ga_flat, HID * 16, HIDDEN_DIM)), n)
+
+    # ------------------------------------------------------------------ backward: WHEN, and on which stream
+    # Weight gradients are off the critical path and only due at the end of the backward pass.  Three policies over the layer
+    # lists above: batch-sized (the default), dependency-driven (eager_wgrad), three-queue (three_streams).  single_stream is
+    # none of its own: fork_side / _join_side do nothing and SIDE is the current stream.
     def _three(self, chain):
         """The backward pass of this step puts its weight gradients on two side streams (64x64 geometry, native step)."""
         return bool(self.three_streams and chain and self.is64 and not self.single_stream and not self.eager_wgrad)
 
-    def _fork_q(self, *qs):
-        """Order side stream 1 (side) and / or 2 (wg2) behind everything enqueued so far on the current stream."""
-        for q in qs:
-            if q == 1:
-                self.fork_side()
+    def _decode_convs_batch(self, layers, B):
+        """Batch-sized schedule, decoder conv layers.  The dgrads of the two big layers (convT3, convT2) fill the chip by
+        themselves; everything after them on this stream is small (8x8 / 4x4 layers, the FC chain, the latent glue, the
+        encoder's FC chain) and leaves most CUs idle -- so the big weight gradients are forked THERE (behind the last big
+        dgrad), and the rest after the FC dgrads (-> the small layers' weight gradients: the caller launches them behind
+        that fork).  Every fork costs this stream ~6 us."""
+        # where convT3's weight gradient is forked (early_thin_wgrad): behind its input gradient -- or, at the 128 images of one
+        # rank of the 8-GPU headline configuration, in FRONT of it (beside it): 0.332 -> 0.325 ms there, level at 32 / 64, +1.3 %
+        # at 96, +1.6 % at 256 images (profiles/r06_s2_sched3.txt, r06_s2_sched4.txt).  Not under data parallelism: the fork carries the
+        # late epilogue with its collectives, whose host-side issue would then stand in front of convT3's input gradient
+        early = 2 if (self.early_thin_auto and 112 <= B <= 128 and not self.sharded) else self.early_thin_wgrad
+        early = 0 if self.single_stream else early
+        queued, pending, small = [], [], []
+        for h, wgrad, dgrad in layers:
+            if h < 16:
+                small.append(wgrad)
+            elif early == 2 and h == 32:
+                self.fork_side()                 # (its launch follows this stream's next kernel, like every side launch)
+                queued.append(wgrad)
             else:
-                call("dvae_stream_order", _stream(), self._wg2.cuda_stream)
+                pending.append(wgrad)
+            if dgrad is not None:
+                call(*dgrad)
+            for w_ in queued:                    # side launches of the previous fork, issued AFTER this stream's next kernel
+                self._wgrad(SIDE, w_)
+            queued = []
+            # the last big dgrad is enqueued (or, early == 1, convT3's): its inputs and those of `pending` are final
+            if pending and (h == 16 or early == 1):
+                self.fork_side()
+                queued, pending = pending, []
+        return small
 
-    def _wgrad_q(self, q, fn, *args):
-        """Conv / convT weight gradient (+ its fixed-order reduction) on side stream q, with that stream's partial-sum workspace."""
-        call(fn, *args, ptr(self._ws_side if q == 1 else self._ws_wg2), (self._side if q == 1 else self._wg2).cuda_stream)
+    def _decode_convs_eager(self, layers):
+        """Dependency-driven schedule, decoder conv layers: both operands of a layer's weight gradient exist when the backward
+        pass reaches the layer (dy: the previous input gradient or g_logit) -- side stream, now, beside this layer's input
+        gradient."""
+        for _, wgrad, dgrad in layers:
+            self.fork_side()
+            self._wgrad(SIDE, wgrad)
+            if dgrad is not None:
+                call(*dgrad)
 
-    # ------------------------------------------------------------------ backward
+    def _decode_backward_3q(self, layers, fc_chain):
+        """Three-queue schedule, decoder half (64x64: four layers).  A weight gradient needs its layer's OUTPUT gradient, i.e.
+        the input gradient of the layer above: behind convT3's input gradient both convT3's and convT2's are due (one per
+        side stream), behind convT2's convT1's."""
+        (_, w_T3, d_T3), (_, w_T2, d_T2), (_, w_T1, d_T1), (_, w_T64, d_T64) = layers
+        call(*d_T3)
+        self.fork_side()
+        self.fork_side(wg2=True)
+        call(*d_T2)                              # this stream's next kernel first, then the side launches
+        self._wgrad(SIDE, w_T3)
+        self._wgrad(WG2, w_T2)                   # forked behind convT3's input gradient, its operands were final there
+        self.fork_side()
+        call(*d_T1)
+        self._wgrad(SIDE, w_T1)                  # forked behind convT2's input gradient
+        if d_T64 is not None:
+            call(*d_T64)
+        fc_chain()
+        # behind the chain of FC input gradients: convT_64's weight gradient here, the FC layers' and the encoder's 4x4 end
+        # in _encode_backward_3q (same fork)
+        self.fork_side()
+        self.fork_side(wg2=True)
+        self._wgrad(SIDE, w_T64)
+
     def decode_backward(self, z, buf, n=None, join=True, defer_fc_wgrad=False, fc_chain=None):
         """buf.g_logit (grad w.r.t. the pre-sigmoid output) -> decoder weight grads, buf.dz.
         defer_fc_wgrad: the three FC weight gradients are not launched here but handed to the next
         encode_backward, which computes all six FC weight gradients of the step in one grouped launch.
         fc_chain: callable that enqueues fc_chain_bwd (the native training step): it replaces the three FC input-gradient
         launches here AND the latent glue + the encoder's three of the following encode_backward(fc_chain=True)."""
-        s = _stream()
         B = z.shape[0] if n is None else n
-        D = self.latent_dim
-        c = self.img_size[0]
-        ws = ptr(self._ws)
-        acts = [buf.d3] + buf.dec_act           # inputs of convT_64/convT1/convT2/convT3 (the first one NCHW = lin3's output)
-        gacts = [buf.gd3] + buf.dec_gact
-        names = self.dec_names + ["convT3"]
-        couts = [HID] * len(self.dec_names) + [c]
-        hs = [4 << i for i in range(len(names))]  # input H of each convT
-        dy, dy_layout = buf.g_logit, NCHW
-        # Weight gradients are off the critical path and only due at the end of the backward pass.  The
-        # dgrads of the two big layers (convT3, convT2) fill the chip by themselves; everything after them
-        # on this stream is small (8x8 / 4x4 layers, the FC chain, the latent glue, the encoder's FC chain)
-        # and leaves most CUs idle -- so the big weight gradients are forked THERE (fork 1, after the last
-        # big dgrad), and the rest after the FC dgrads (fork 2).  Every fork costs this stream ~6 us.
-        eager = self.eager_wgrad and not self.single_stream
-        # where convT3's weight gradient is forked (early_thin_wgrad): behind its input gradient -- or, at the 128 images of one
-        # rank of the 8-GPU headline configuration, in FRONT of it (beside it): 0.332 -> 0.325 ms there, level at 32 / 64, +1.3 %
-        # at 96, +1.6 % at 256 images (profiles/r06_s2_sched3.txt, r06_s2_sched4.txt).  Not under data parallelism: the fork carries the
-        # late epilogue with its collectives, whose host-side issue would then stand in front of convT3's input gradient
-        early_mode = 2 if (self.early_thin_auto and 112 <= B <= 128 and not self.sharded) else self.early_thin_wgrad
-        three = self._three(fc_chain is not None) and defer_fc_wgrad and not join
-        pending, deferred, queued = [], [], []
-        W3 = {}                                  # three-queue schedule: every layer's weight-gradient launch, by layer
-        for k in range(len(names) - 1, -1, -1):
-            name, x_in, gx, h = names[k], acts[k], gacts[k], hs[k]
-            lname = "decoder.%s" % name
-            wargs = ("dvae_convT4s2_wgrad", ptr(x_in), NCHW if k == 0 else NHWC, ptr(dy), dy_layout,
-                     ptr(self.g(lname + ".weight")), ptr(self.g(lname + ".bias")), B, HID, h, h, couts[k])
-            if three:
-                W3[k] = wargs
-            elif eager:
-                # both operands of this layer's weight gradient exist (dy: the previous input gradient or g_logit): side
-                # stream, now, beside this layer's input gradient
-                self._conv_wgrad(*wargs, fork=True)
-            elif early_mode == 2 and h == 32 and not self.single_stream:
-                self.fork_side()                 # (its launch follows this stream's next kernel, like every side launch)
-                queued.append(wargs)
-            else:
-                (pending if h >= 16 else deferred).append(wargs)
-            # the first decoder layer's input gradient leaves NCHW = (c,h,w) order, straight into gd3 (the
-            # gradient of lin3's output; ReLU mask = lin3's output d3 in the same order): no relayout pass
-            out_layout = NCHW if k == 0 else NHWC
-            if k == 0 and fc_chain is not None and self._ends(B):
-                pass                                 # convT_64's input gradient: the prologue of fc_chain_bwd
-            elif couts[k] == HID:
-                call("dvae_conv32_down", ptr(dy), self._img(lname, "down"), None, ptr(x_in), ptr(gx), out_layout, B, h,
-                     ACT_NONE, s)
-            elif self.mask_bits:
-                call("dvae_convT3_dgrad_bits", ptr(dy), ptr(self.p(lname + ".weight")), ptr(buf.bits_convT2), ptr(gx), B,
-                     couts[k], s)
-            else:
-                call("dvae_convT4s2_dgrad", ptr(dy), dy_layout, ptr(self.p(lname + ".weight")), ptr(x_in), ptr(gx),
-                     out_layout, B, HID, h, h, couts[k], s)
-            dy, dy_layout = gx, NHWC
-            if three:
-                # a weight gradient needs its layer's OUTPUT gradient, i.e. the input gradient of the layer above: behind convT3's
-                # input gradient both convT3's and convT2's are due (one per side stream), behind convT2's convT1's
-                last = len(names) - 1
-                for q, w_ in queued:
-                    self._wgrad_q(q, *w_)
-                queued = []
-                if k == last:
-                    self._fork_q(1, 2)
-                    queued = [(1, wargs)]        # (W3[last - 1] does not exist yet: built at the head of the next iteration)
-                elif k == last - 1:
-                    self._wgrad_q(2, *wargs)     # convT2's: forked behind convT3's input gradient, its operands were final there
-                    self._fork_q(1)
-                elif k == last - 2:
-                    self._wgrad_q(1, *wargs)     # convT1's: forked behind convT2's input gradient
-                continue
-            if eager:
-                continue
-            for w_ in queued:                    # side launches of the previous fork, issued AFTER this stream's next kernel
-                self._conv_wgrad(*w_, fork=False)
-            queued = []
-            early = early_mode == 1 and h == 32 and pending and not self.single_stream
-            if h == 16 or (k == 0 and pending) or early:  # last big dgrad is enqueued: its inputs and those of `pending` are final
-                self.fork_side()
-                queued, pending = pending, []
-        if three:
-            for q, w_ in queued:
-                self._wgrad_q(q, *w_)
-            fc_chain()
-            # behind the chain of FC input gradients: convT_64's weight gradient here, the FC layers' and the encoder's 4x4 end
-            # in _encode_backward_3s (same fork)
-            self._fork_q(1, 2)
-            if len(names) == 4:
-                self._wgrad_q(1, *W3[0])
-            self._fc_pending = [(buf.d2, buf.gd3, self.g("decoder.lin3.weight"), self.g("decoder.lin3.bias"), B, HIDDEN_DIM, HID * 16),
-                                (buf.d1, buf.gd2, self.g("decoder.lin2.weight"), self.g("decoder.lin2.bias"), B, HIDDEN_DIM, HIDDEN_DIM),
-                                (z, buf.gd1, self.g("decoder.lin1.weight"), self.g("decoder.lin1.bias"), B, D, HIDDEN_DIM)]
+        layers = self._dec_layers(buf, B, fc_chain is not None and self._ends(B))
+        fc = self._dec_fc_wgrads(z, buf, B)
+        if self._three(fc_chain is not None) and defer_fc_wgrad and not join:
+            self._decode_backward_3q(layers, fc_chain)
+            self._fc_pending = fc
             return
-        for w_ in queued:
-            self._conv_wgrad(*w_, fork=False)
+        small = []
+        if self.eager_wgrad and not self.single_stream:
+            self._decode_convs_eager(layers)
+        else:
+            small = self._decode_convs_batch(layers, B)
         if fc_chain is not None:
             fc_chain()
         else:
-            call("dvae_linear_dgrad", ptr(buf.gd3), ptr(self.p("decoder.lin3.weight")), ptr(buf.d2), ACT_RELU, ptr(buf.gd2),
-                 B, HIDDEN_DIM, HID * 16, ws, s)
-            call("dvae_linear_dgrad", ptr(buf.gd2), ptr(self.p("decoder.lin2.weight")), ptr(buf.d1), ACT_RELU, ptr(buf.gd1),
-                 B, HIDDEN_DIM, HIDDEN_DIM, ws, s)
-            call("dvae_linear_dgrad", ptr(buf.gd1), ptr(self.p("decoder.lin1.weight")), None, ACT_NONE, ptr(buf.dz),
-                 B, D, HIDDEN_DIM, ws, s)
+            self._dec_fc_dgrads(buf, B)
         # small conv layers + the three FC weight gradients: one fork, then they co-run with whatever follows
-        if deferred or not defer_fc_wgrad:
+        if small or not defer_fc_wgrad:
             self.fork_side()
-        for wargs in deferred:
-            self._conv_wgrad(*wargs, fork=False)
-        fc = [(buf.d2, buf.gd3, self.g("decoder.lin3.weight"), self.g("decoder.lin3.bias"), B, HIDDEN_DIM, HID * 16),
-              (buf.d1, buf.gd2, self.g("decoder.lin2.weight"), self.g("decoder.lin2.bias"), B, HIDDEN_DIM, HIDDEN_DIM),
-              (z, buf.gd1, self.g("decoder.lin1.weight"), self.g("decoder.lin1.bias"), B, D, HIDDEN_DIM)]
+        for wgrad in small:
+            self._wgrad(SIDE, wgrad)
         if defer_fc_wgrad:
             self._fc_pending = fc
         else:
-            self._side_wgrad_grouped(fc)
+            self._fc_wgrads(SIDE, fc)
         if join:
             self._join_side()
 
-    def _encode_backward_3s(self, x, buf, B, fc, fused_end):
-        """encode_backward of the three-queue schedule; _decode_backward's fork behind the FC chain covers the first launches."""
-        s = _stream()
-        c, H, _ = self.img_size
-        last = len(self.enc_names) - 1
-        W = {}
-        for k in range(last, -1, -1):
-            lname = "encoder.%s" % self.enc_names[k]
-            h_in = self.enc_sizes[k] * 2
-            x_in, x_layout, cin = (buf.enc_act[k - 1], NHWC, HID) if k > 0 else (x, NCHW, c)
-            dy, dy_layout = (buf.ga_flat, NCHW) if k == last else (buf.enc_gact[k], NHWC)
-            W[k] = (("dvae_conv4s2_wgrad", ptr(x_in), x_layout, ptr(dy), dy_layout, ptr(self.g(lname + ".weight")),
-                     ptr(self.g(lname + ".bias")), B, cin, h_in, h_in, HID), dy, dy_layout, lname, x_in, h_in)
-        # all six FC weight gradients + conv_64's (ga_flat is final): second side stream
-        self._side_wgrad_grouped(fc, stream=self._wg2.cuda_stream)
-        self._wgrad_q(2, *W[last][0])
-        if not fused_end:                        # conv_64's input gradient as a launch of its own: conv3's weight gradient waits for it
-            _, dy, dyl, lname, x_in, h_in = W[last]
-            self._conv_dgrad(dy, dyl, lname, x_in, buf, last, B, h_in, s)
-            self._fork_q(1)
-        for k in range(last - 1, 0, -1):
-            _, dy, dyl, lname, x_in, h_in = W[k]
-            self._conv_dgrad(dy, dyl, lname, x_in, buf, k, B, h_in, s)     # this stream's next kernel first, then the side launch
-            if k == last - 1:
-                self._wgrad_q(1, *W[k][0])       # conv3's (operand: fc_chain_bwd's epilogue / the launch above)
-                self._fork_q(2)                  # behind conv3's input gradient: conv2's weight gradient
-            else:
-                self._wgrad_q(2, *W[k][0])
-        if x.dtype == torch.uint8:
-            lname = "encoder.%s" % self.enc_names[0]
-            call("dvae_conv4s2_wgrad_u8", ptr(x), ptr(buf.enc_gact[0]), ptr(self.g(lname + ".weight")),
-                 ptr(self.g(lname + ".bias")), B, c, H, H, HID, ptr(self._ws), s)
-        else:
-            self._conv_wgrad(*W[0][0], fork=False, main=True)
-        self._join_side()
-        call("dvae_stream_order", self._wg2.cuda_stream, s)
-
-    def _conv_dgrad(self, dy, dy_layout, lname, x_in, buf, k, B, h_in, s):
-        """Input gradient of encoder conv layer k (> 0) into buf.enc_gact[k - 1], masked by the ReLU of layer k - 1: by the
-        bit plane conv1's forward emitted where there is one (conv2 at the 64x64 geometry), else by the fp32 activation."""
-        if self.mask_bits and k == 1:
-            call("dvae_conv32_up_bits", ptr(dy), self._img(lname, "up"), None, ptr(buf.bits_conv1), ptr(buf.enc_gact[0]),
-                 None, B, ACT_NONE, s)
-        else:
-            call("dvae_conv32_up", ptr(dy), dy_layout, self._img(lname, "up"), None, ptr(x_in), ptr(buf.enc_gact[k - 1]),
-                 B, h_in // 2, ACT_NONE, s)
-
-    def encode_backward(self, x, buf, n=None, fc_chain=False):
-        """buf.dml (grad w.r.t. the interleaved mu/logvar output) -> encoder weight grads.  fc_chain: the three FC input
-        gradients were already computed by fc_chain_bwd (buf.gh2, gh1, ga_flat are final)."""
-        s = _stream()
-        B = x.shape[0] if n is None else n
-        c, H, _ = self.img_size
-        ws = ptr(self._ws)
-        if not fc_chain:
-            call("dvae_linear_dgrad", ptr(buf.dml), ptr(self.p("encoder.mu_logvar_gen.weight")), ptr(buf.h2), ACT_RELU,
-                 ptr(buf.gh2), B, HIDDEN_DIM, 2 * self.latent_dim, ws, s)
-            call("dvae_linear_dgrad", ptr(buf.gh2), ptr(self.p("encoder.lin2.weight")), ptr(buf.h1), ACT_RELU, ptr(buf.gh1),
-                 B, HIDDEN_DIM, HIDDEN_DIM, ws, s)
-            call("dvae_linear_dgrad", ptr(buf.gh1), ptr(self.p("encoder.lin1.weight")), ptr(buf.a_flat), ACT_RELU,
-                 ptr(buf.ga_flat), B, HID * 16, HIDDEN_DIM, ws, s)
-        # weight gradients wait for the next fork (they only have to be done by the end of the backward pass): the
-        # encoder's three FC layers + the decoder's three when decode_backward deferred them = one grouped launch
-        pend, self._fc_pending = [p_ for p_ in self._fc_pending if p_[4] == B], []
-        # largest problems first (128, 128, 64, 64, 8, 8 tiles): the long-running workgroups start first
-        fc = ([(buf.a_flat, buf.gh1, self.g("encoder.lin1.weight"), self.g("encoder.lin1.bias"), B, HID * 16, HIDDEN_DIM)]
-              + pend[:1]
-              + [(buf.h1, buf.gh2, self.g("encoder.lin2.weight"), self.g("encoder.lin2.bias"), B, HIDDEN_DIM, HIDDEN_DIM)]
-              + pend[1:]
-              + [(buf.h2, buf.dml, self.g("encoder.mu_logvar_gen.weight"), self.g("encoder.mu_logvar_gen.bias"),
-                  B, HIDDEN_DIM, 2 * self.latent_dim)])
-        eager = self.eager_wgrad and not self.single_stream
-        fused_end = bool(fc_chain) and self._ends(B)        # conv_64's input gradient: fc_chain_bwd's epilogue wrote enc_gact[2]
-        if self._three(bool(fc_chain)) and len(pend) == 3:
-            return self._encode_backward_3s(x, buf, B, fc, fused_end)
+    def _encode_backward_batch(self, layers, fc, B):
+        """Batch-sized schedule, encoder half.  Forks: one before the first big layer (h_in >= 32; the grouped FC weight
+        gradients and the small layers' ride along with it), one per big layer after that, one in front of conv1's weight
+        gradient if anything still waits: conv1 has no dgrad, this stream has nothing else left, so it computes that last
+        weight gradient itself while the side stream drains its queue -- and after it those of tail_main."""
         # the grouped FC weight gradients: side stream (in front of conv2's weight gradient) -- or, fcw_main, the LAST launch of the
         # main stream's tail (a step of a few hundred images ends on the side stream: profiles/r06_final4_dsprites_timeline.md)
         fcw_main = (self.fcw_main and self.is64 and not self.single_stream
                     and self.fcw_main_rows[0] <= B <= self.fcw_main_rows[1])
-        deferred = [] if fcw_main else [lambda fc=fc: self._side_wgrad_grouped(fc)]
-        tail_main = []                      # weight gradients the main stream computes after conv1's (load balance of the tail)
-        last = len(self.enc_names) - 1
-        if eager:
-            # dependency-driven schedule: the six FC weight gradients now (every operand exists: the chain of input gradients
-            # is behind us), then each conv layer's weight gradient beside its input gradient; conv1 has no input gradient:
-            # its weight gradient is the main stream's last kernel
-            self.fork_side()
-            self._side_wgrad_grouped(fc)
-            for k in range(last, -1, -1):
-                name = self.enc_names[k]
-                lname = "encoder.%s" % name
-                h_in = self.enc_sizes[k] * 2
-                x_in, x_layout, cin = (buf.enc_act[k - 1], NHWC, HID) if k > 0 else (x, NCHW, c)
-                dy, dy_layout = (buf.ga_flat, NCHW) if k == last else (buf.enc_gact[k], NHWC)
-                wargs = ("dvae_conv4s2_wgrad", ptr(x_in), x_layout, ptr(dy), dy_layout,
-                         ptr(self.g(lname + ".weight")), ptr(self.g(lname + ".bias")), B, cin, h_in, h_in, HID)
-                if k == 0:
-                    if x.dtype == torch.uint8:
-                        call("dvae_conv4s2_wgrad_u8", ptr(x), ptr(dy), ptr(self.g(lname + ".weight")),
-                             ptr(self.g(lname + ".bias")), B, cin, h_in, h_in, HID, ptr(self._ws), s)
-                    else:
-                        self._conv_wgrad(*wargs, fork=False, main=True)
-                    break
-                self._conv_wgrad(*wargs, fork=k < last)      # (k == last: the fork above covers it)
-                if not (k == last and fused_end):
-                    self._conv_dgrad(dy, dy_layout, lname, x_in, buf, k, B, h_in, s)
-            self._join_side()
-            return
-        for k in range(last, -1, -1):
-            name = self.enc_names[k]
-            lname = "encoder.%s" % name
-            h_in = self.enc_sizes[k] * 2
-            if k > 0:
-                x_in, x_layout, cin = buf.enc_act[k - 1], NHWC, HID
-            else:
-                x_in, x_layout, cin = x, NCHW, c
-            # the last conv's output gradient is lin1's input gradient, (c,h,w) order = NCHW 4x4x32: read as such
-            dy, dy_layout = (buf.ga_flat, NCHW) if k == last else (buf.enc_gact[k], NHWC)
-            # forks: one before the first big layer (h_in >= 32; the small layers' weight gradients ride
-            # along with it), one per big layer after that
-            big = h_in >= 32
-            wargs = ("dvae_conv4s2_wgrad", ptr(x_in), x_layout, ptr(dy), dy_layout,
-                     ptr(self.g(lname + ".weight")), ptr(self.g(lname + ".bias")), B, cin, h_in, h_in, HID)
-            side = []
-            if k == 0:
-                # the first layer has no dgrad: this stream has nothing else left, so it computes the last
-                # weight gradient itself (no fork) while the side stream drains its queue
-                if deferred:
-                    self.fork_side()
-                    side, deferred = deferred, []
-                if x.dtype == torch.uint8:
-                    call("dvae_conv4s2_wgrad_u8", ptr(x), ptr(dy), ptr(self.g(lname + ".weight")),
-                         ptr(self.g(lname + ".bias")), B, cin, h_in, h_in, HID, ptr(self._ws), s)
-                else:
-                    self._conv_wgrad(*wargs, fork=False, main=True)
-                for w_ in tail_main:
-                    self._conv_wgrad(*w_, fork=False, main=True)
-                if fcw_main:
-                    self._side_wgrad_grouped(fc, stream=s)
-            elif name in self.tail_main and self.is64 and not self.single_stream:
-                tail_main.append(wargs)
-            elif big:
+        fc_side = not fcw_main                  # the grouped launch still waits for a fork of the side stream
+        waiting, tail = [], []                  # weight gradients waiting for that fork / for the main stream's tail
+        for name, h_in, wgrad, dgrad in layers[:-1]:
+            side = ()
+            if name in self.tail_main and self.is64 and not self.single_stream:
+                tail.append(wgrad)
+            elif h_in >= 32:
                 self.fork_side()
-                side, deferred = deferred + [lambda wargs=wargs: self._conv_wgrad(*wargs, fork=False)], []
+                side, waiting = waiting + [wgrad], []
             else:
-                deferred.append(lambda wargs=wargs: self._conv_wgrad(*wargs, fork=False))
-            if k > 0 and not (k == last and fused_end):   # this stream's next kernel first, then the side launches
-                self._conv_dgrad(dy, dy_layout, lname, x_in, buf, k, B, h_in, s)
-            for launch in side:
-                launch()
-        if deferred:
+                waiting.append(wgrad)
+            if dgrad is not None:               # this stream's next kernel first, then the side launches
+                call(*dgrad)
+            if side:
+                if fc_side:
+                    self._fc_wgrads(SIDE, fc)
+                    fc_side = False
+                for w_ in side:
+                    self._wgrad(SIDE, w_)
+        if fc_side or waiting:
             self.fork_side()
-            for launch in deferred:
-                launch()
+        self._wgrad(MAIN, layers[-1][2])
+        for w_ in tail:
+            self._wgrad(MAIN, w_)
+        if fcw_main:
+            self._fc_wgrads(MAIN, fc)
+        if fc_side:
+            self._fc_wgrads(SIDE, fc)
+        for w_ in waiting:
+            self._wgrad(SIDE, w_)
         self._join_side()
+
+    def _encode_backward_eager(self, layers, fc):
+        """Dependency-driven schedule, encoder half: the six FC weight gradients now (every operand exists: the chain of input
+        gradients is behind us), then each conv layer's weight gradient beside its input gradient; conv1 has no input
+        gradient: its weight gradient is the main stream's last kernel."""
+        self.fork_side()
+        self._fc_wgrads(SIDE, fc)
+        for i, (_, _, wgrad, dgrad) in enumerate(layers[:-1]):
+            if i > 0:                            # (the first layer: the fork above covers it)
+                self.fork_side()
+            self._wgrad(SIDE, wgrad)
+            if dgrad is not None:
+                call(*dgrad)
+        self._wgrad(MAIN, layers[-1][2])
+        self._join_side()
+
+    def _encode_backward_3q(self, layers, fc):
+        """Three-queue schedule, encoder half (64x64: four layers); _decode_backward_3q's fork behind the FC chain covers the
+        first launches."""
+        (_, _, w_64, d_64), (_, _, w_3, d_3), (_, _, w_2, d_2), (_, _, w_1, _) = layers
+        # all six FC weight gradients + conv_64's (ga_flat is final): second side stream
+        self._fc_wgrads(WG2, fc)
+        self._wgrad(WG2, w_64)
+        if d_64 is not None:                     # conv_64's input gradient as a launch of its own: conv3's weight gradient waits for it
+            call(*d_64)
+            self.fork_side()
+        call(*d_3)                               # this stream's next kernel first, then the side launch
+        self._wgrad(SIDE, w_3)                   # conv3's (operand: fc_chain_bwd's epilogue / the launch above)
+        self.fork_side(wg2=True)                 # behind conv3's input gradient: conv2's weight gradient
+        call(*d_2)
+        self._wgrad(WG2, w_2)
+        self._wgrad(MAIN, w_1)
+        self._join_side()
+        self._join_side(wg2=True)
+
+    def encode_backward(self, x, buf, n=None, fc_chain=False):
+        """buf.dml (grad w.r.t. the interleaved mu/logvar output) -> encoder weight grads.  fc_chain: the three FC input
+        gradients were already computed by fc_chain_bwd (buf.gh2, gh1, ga_flat are final)."""
+        B = x.shape[0] if n is None else n
+        if not fc_chain:
+            self._enc_fc_dgrads(buf, B)
+        # weight gradients wait for the next fork (they only have to be done by the end of the backward pass): the
+        # encoder's three FC layers + the decoder's three when decode_backward deferred them = one grouped launch
+        pend, self._fc_pending = [p_ for p_ in self._fc_pending if p_[4] == B], []
+        fc = self._enc_fc_wgrads(buf, B, pend)
+        layers = self._enc_layers(x, buf, B, bool(fc_chain) and self._ends(B))
+        if self._three(bool(fc_chain)) and len(pend) == 3:
+            self._encode_backward_3q(layers, fc)
+        elif self.eager_wgrad and not self.single_stream:
+            self._encode_backward_eager(layers, fc)
+        else:
+            self._encode_backward_batch(layers, fc, B)
