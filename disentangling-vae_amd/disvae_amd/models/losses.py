@@ -12,12 +12,13 @@ Two ways in:
 Host-side state (n_train_steps, annealing, storer cadence) follows losses.py:71-75,105-114.
 """
 import abc
+import contextlib
 
 import torch
 
 from .. import _lib
 from .. import optim
-from .._lib import call, ptr, record_on_stream, record_py
+from .._lib import call, ptr, record_py
 from ..utils.math import log_importance_weights
 from .discriminator import Discriminator
 from ..graph import StepGraphs
@@ -229,10 +230,8 @@ class BaseLoss(abc.ABC):
         if is_train:
             self.n_train_steps += 1
         if not is_train or self.n_train_steps % self.record_loss_every == 1:
-            storer = storer
-        else:
-            storer = None
-        return storer
+            return storer
+        return None
 
     def scratch(self, device):
         if self._scratch is None or self._scratch.device != device:
@@ -261,15 +260,102 @@ class BaseLoss(abc.ABC):
         """(world, rank) as seen by the batch-coupled estimators."""
         return (1, 0) if (self.comm is None or self.estimator == "local") else (self.comm.world_size, self.comm.rank)
 
-    @staticmethod
-    def _store_common(storer, vals, D):
-        storer['recon_loss'].append(vals[_lib.S_REC])
+    # what a step logs, in this order: (storer key, scalar slot); 'kl_loss' brings the per-dimension values with it
+    STORED = ()
+
+    def _store(self, storer, sc, D, keys=None):
+        if storer is None:
+            return
+        vals = sc.scal.tolist()           # ONE device->host copy for every logged scalar
+        for key, slot in self.STORED if keys is None else keys:
+            if key == 'kl_loss':
+                self._store_kl(storer, vals, D)
+            else:
+                storer[key].append(vals[slot])
 
     @staticmethod
     def _store_kl(storer, vals, D):
         storer['kl_loss'].append(vals[_lib.S_KL])
         for i in range(D):
             storer['kl_loss_' + str(i)].append(vals[_lib.kl0(D) + i])
+
+    # ---- the parts of a native step (the skeleton: DESIGN.md, "The step skeleton") ---------------------------------------
+    def _run_step(self, model, data, inputs, injected, key_extra, fn):
+        """Replay dispatch: fn(data, *inputs) now, or recorded / replayed (graph.py).  A replay re-issues launches with frozen
+        pointers: the injected `inputs` [(name, tensor or None)] go through static buffers; the batch pointer is part of the plan
+        key (a hipGraph needs it static as well)."""
+        mode = self._replay_mode(model.training, data)
+        if not mode:
+            return fn(data, *[t for _, t in inputs])
+        if mode == "graph":
+            data = self._static_buf("data", data)
+        inputs = [t if t is None else self._static_buf(name, t) for name, t in inputs]
+        self._graphs.run(self._replay_key(model, data, injected) + key_extra, lambda: fn(data, *inputs), mode)
+
+    def _finish_loss(self, sc, klb, D, rowstats, rows, disc_sums, Bg, stream, on=None, xbuf=None):
+        """The scalar epilogue on `stream`: partial sums -> sc.scal.  Single process: ONE launch.  Sharded: pack, sum-all-reduce
+        over the ranks (issued under torch stream `on`, the handle of `stream`, when that is not the current one), finalize; with
+        `xbuf` (the sharded beta-TCVAE estimator's column gradients) the sums are packed behind them and ride in their
+        collective."""
+        if self.comm is None or self.comm.world_size == 1:
+            call("dvae_loss_epilogue", self.KIND, ptr(sc.partials), ptr(sc.kl_dim), klb, D, ptr(rowstats), rows, ptr(disc_sums), Bg,
+                 ptr(sc.coef), ptr(sc.packed), ptr(sc.scal), stream)
+            return
+        npk = _lib.npack(D)
+        packed = sc.packed if xbuf is None else xbuf[xbuf.numel() - npk:]
+        self._pack_sums(sc, klb, D, rowstats, rows, disc_sums, packed, stream)
+        with contextlib.nullcontext() if on is None else torch.cuda.stream(on):
+            if xbuf is None:
+                self.comm.all_reduce(packed)
+            else:                                 # + the estimator's column gradients: one collective
+                self.comm.all_reduce_cols_sums(xbuf, rows, D, npk)
+        call("dvae_loss_finalize", self.KIND, ptr(packed), D, Bg, ptr(sc.coef), ptr(sc.scal), stream)
+
+    def _defer_loss(self, eng, finish):
+        """The late join.  Nothing on the current stream needs the scalar loss (or the beta-TCVAE estimator) before the FC chain's
+        input gradients, a whole convT backward later -- joining earlier left this stream idle for ~20 us plus the epilogue
+        (profiles/r04_v35_btcvae_celeba_timeline.md).  `finish(stream, on)` therefore runs behind the NEXT fork (the backward
+        pass's first: no fork of its own) on the side stream -- sharded, on the exchange stream behind the estimator, ordered
+        after the fork point through the side stream (whose only queued work at that moment is the wait for that fork: no second
+        event on this stream) -- and an event slot marks the lot.  Returns what fc_chain() calls first: the wait for the slot."""
+        s = _stream()
+        sharded = self._world()[0] > 1
+
+        def deferred():
+            ss = eng._side_raw()
+            if sharded:
+                ss = eng._aux_raw()
+                call("dvae_stream_order", eng._side_raw(), ss)
+            finish(ss, eng.aux_stream if sharded else None)
+            call("dvae_event_record", self._ev_slot, ss)
+        eng.at_next_fork(deferred)
+
+        def wait():
+            eng.flush_fork_hook()
+            call("dvae_event_wait", self._ev_slot, s)
+        return wait
+
+    def _backward(self, eng, model, data, buf, n, fc_chain, pending=()):
+        """Both backward passes and the gradient exchange; one join, at the end of encode_backward.  Single process: ONE grouped
+        launch for all six FC weight gradients (issued by encode_backward).  Sharded, two spans: the decoder's three are launched
+        with the decoder's conv weight gradients -- every kernel that writes a decoder gradient goes to the side stream, so the
+        all-reduce of the decoder span is ordered behind the SIDE stream and overlaps the encoder backward; this stream never
+        waits for it before the end.  Small shards (SMALL_SHARD_ELEMS): ONE all-reduce of the whole arena after the final join.
+        pending: handles of collectives already under way (FactorVAE: the discriminator's gradients), waited for last."""
+        world = self._world()[0]
+        spans = world > 1 and data.numel() > self.SMALL_SHARD_ELEMS
+        pending = list(pending)
+        eng.decode_backward(buf.z, buf, n=n, join=False, defer_fc_wgrad=not spans, fc_chain=fc_chain)
+        if spans:
+            with torch.cuda.stream(eng.side_stream):
+                pending.append(self.comm.all_reduce_async(model.arena.span("decoder.")))
+        eng.encode_backward(data, buf, n=n, fc_chain=True)
+        if spans:
+            pending.append(self.comm.all_reduce_async(model.arena.span("encoder.")))
+        elif world > 1:
+            self.comm.all_reduce(model.arena.grad)
+        for h_ in pending:
+            h_.wait()
 
 
 # ------------------------------------------------------------------------------------------
@@ -415,44 +501,29 @@ class _SingleOptimizerLoss(BaseLoss):
     """Shared fused step of BetaH / BetaB / Btcvae (training.py:152-158 + the loss __call__)."""
 
     KIND = None
+    STORED = (('recon_loss', _lib.S_REC), ('kl_loss', _lib.S_KL), ('loss', _lib.S_LOSS))
 
     def _coefs(self, is_train):
-        raise NotImplementedError
-
-    def _store(self, storer, vals, D):
         raise NotImplementedError
 
     def fused_step(self, data, model, optimizer, storer, eps=None):
         is_train = model.training
         storer = self._pre_call(is_train, storer)
         B, D = data.shape[0], model.latent_dim
-        world, rank = self._world()
         sc = self.scratch(data.device).for_latent_dim(D)
         # ONE launch: this step's weight images (32-channel conv layers, FC chain) + its loss coefficients
-        sc.set_coef_host(INV_B=1.0 / (B * world), **self._coefs(is_train))
+        sc.set_coef_host(INV_B=1.0 / (B * self._world()[0]), **self._coefs(is_train))
         model.engine.stage(sc.coef, sc.coef_host)
         data = data.contiguous()
         self._streams(model, data)
         if self.KIND == _lib.LOSS_BTCVAE:
             sc.set_log_w(B * self._est_world()[0], self.n_data)
-        mode = self._replay_mode(is_train, data)
-        if mode:
-            # a replay re-issues launches with frozen pointers: injected noise goes through a static
-            # buffer; the batch pointer is part of the plan key (a hipGraph needs it static as well)
-            if mode == "graph":
-                data = self._static_buf("data", data)
-            if eps is not None:
-                eps = self._static_buf("eps", eps)
-            self._graphs.run(self._replay_key(model, data, eps is not None),
-                             lambda: self._device_step(data, model, sc, eps, True), mode)
-        else:
-            self._device_step(data, model, sc, eps, is_train)
+        self._run_step(model, data, [("eps", eps)], eps is not None, (),
+                       lambda data, eps: self._device_step(data, model, sc, eps, is_train))
         if is_train:
             model.assign_grads()          # optimizer.zero_grad(); loss.backward()  (training.py:156-157)
             optim.step(optimizer)         # optimizer.step(), training.py:158 (one launch for a stock Adam: disvae_amd/optim.py)
-        if storer is not None:
-            vals = sc.scal.tolist()       # ONE device->host copy for every logged scalar
-            self._store(storer, vals, D)
+        self._store(storer, sc, D)
         return sc.scal[_lib.S_LOSS]
 
     def _device_step(self, data, model, sc, eps, is_train):
@@ -460,7 +531,7 @@ class _SingleOptimizerLoss(BaseLoss):
         eng = model.engine
         eng._fork_hook = None                  # a hook left behind by a step that raised is dropped, not run (nor recorded)
         B, D = data.shape[0], model.latent_dim
-        world, rank = self._world()
+        world = self._world()[0]
         Bg = B * world
         buf = eng.buffers(B)
         s = _stream()
@@ -475,125 +546,42 @@ class _SingleOptimizerLoss(BaseLoss):
         # (latent dimensions above 16: one launch per layer, kl_dim final at once and klb = 0 -- engine.fc_chain_fwd)
         eng.fc_chain_fwd(buf, eps, sc.kl_dim, B, coef=sc.coef)
         klb = eng.kl_blocks(B)            # single process: the one-launch loss epilogue finishes the KL partials
-        npk = _lib.npack(D)
-        lat = {"rowstats": None, "dz": None, "dmu": None, "dlv": None, "xbuf": None}
         btc = self.KIND == _lib.LOSS_BTCVAE
-
-        def estimator():
-            # the B x B estimator (forward AND backward: it needs z, mu, logvar and the coefficients only) on the side stream
-            # while the decoder forward occupies the current one
-            ew, er = self._est_world()            # the estimator's view of the sharding (local mode: one shard = one batch)
-            Be = B * ew
-            with torch.cuda.stream(eng.aux_stream if world > 1 else eng.side_stream):
-                ss = _stream()
-                zg, mug, lvg = buf.z, buf.mu, buf.logvar
-                if ew > 1:
-                    zg, mug, lvg = self.comm.all_gather_latents(buf.z, buf.mu, buf.logvar)
-                rowstats = lat["rowstats"] = sc.latent("rowstats", B, _lib.rowstats_stride(D))
-                tc_tmp = sc.latent("tc_tmp", 1, _lib.btcvae_tmp_floats(Be, B, D))
-                call("dvae_btcvae_fwd", ptr(zg), ptr(mug), ptr(lvg), Be, D, er * B, B, int(self.is_mss), ptr(sc.log_w),
-                     ptr(tc_tmp), ptr(rowstats), ss)
-                if is_train:
-                    dz_x = sc.latent("dz_tc", B, D)
-                    # (dmu, dlogvar) of ALL columns: two slabs of one buffer, followed by the packed loss sums -- sharded, the
-                    # lot is summed over the ranks by ONE all-reduce in the step's late epilogue (Comm.all_reduce_cols_sums)
-                    xbuf = sc.latent("xbuf", 1, 2 * Be * D + npk).view(-1)
-                    dmu_all, dlv_all = xbuf[:Be * D].view(Be, D), xbuf[Be * D:2 * Be * D].view(Be, D)
-                    call("dvae_btcvae_bwd", ptr(zg), ptr(mug), ptr(lvg), ptr(rowstats), Be, D, er * B, B,
-                         int(self.is_mss), ptr(sc.log_w), ptr(sc.coef), ptr(tc_tmp), ptr(dz_x), ptr(dmu_all), ptr(dlv_all), ss)
-                    if ew > 1:
-                        lat["xbuf"] = xbuf
-                        dmu_x, dlv_x = dmu_all[er * B:(er + 1) * B], dlv_all[er * B:(er + 1) * B]
-                    else:
-                        dmu_x, dlv_x = dmu_all, dlv_all
-                    if world > ew:                # local estimator: its mean runs over B, the loss over B * world
-                        for t_ in (dz_x, dmu_x, dlv_x):
-                            scale_(t_, 1.0 / world)
-                    lat["dz"], lat["dmu"], lat["dlv"] = dz_x, dmu_x, dlv_x
-
-        fuse = (data, self._rec_code(), sc.coef, sc.partials)
+        rowstats = dz = dmu = dlv = xbuf = None
         if btc and world == 1:
+            # the B x B estimator on the side stream while the decoder forward occupies the current one
             eng.fork_side()
-            estimator()
+            rowstats, dz, dmu, dlv, xbuf = self._estimator(eng, buf, sc, B, D, is_train)
         elif btc:
             # sharded: the estimator with its exchanges on a stream of its own (engine.buffers: the side stream is the tail of
             # the iteration, nothing may queue in front of its weight gradients)
             call("dvae_stream_order", s, eng._aux_raw())
         # decoder convT stack; its last layer also evaluates the reconstruction likelihood and dL/dlogit
-        eng.decode_convs(buf, B, fuse_loss=fuse, chain=True)
+        eng.decode_convs(buf, B, fuse_loss=(data, self._rec_code(), sc.coef, sc.partials), chain=True)
         if btc and world > 1:
             # sharded: this stream's launches are issued FIRST -- the exchanges make the side stream's part long to issue, and
             # at a hundred images per GPU the host is what the critical path would wait for
-            estimator()
-        rowstats = lat["rowstats"]
-        # Nothing on this stream needs the estimator (or the scalar loss) before the FC chain's input gradients, a whole convT
-        # backward later -- the estimator's backward kernels run past the end of the decoder forward, and joining here left
-        # this stream idle for ~20 us plus the epilogue (profiles/r04_v35_btcvae_celeba_timeline.md).  The epilogue goes to the
-        # side stream behind them, an event slot marks the lot, fc_chain() waits for the slot.  Sharded batches (any loss):
-        # the all-reduce of the packed loss sums sits between the two halves of the epilogue, on the side stream as well.
+            rowstats, dz, dmu, dlv, xbuf = self._estimator(eng, buf, sc, B, D, is_train)
+        # the scalar epilogue: deferred behind the estimator's backward kernels, which run past the end of the decoder forward
+        # (_defer_loss), for beta-TCVAE and for every sharded step (the all-reduce of the packed loss sums sits between its halves)
         late_join = (is_train and not eng.single_stream and (btc or world > 1) and knob("DVAE_LATE_JOIN", "1") != "0")
-        if btc and not late_join:
-            if world > 1:
-                call("dvae_stream_order", eng._aux_raw(), s)
-            else:
-                eng._join_side()
+        wait = None
         if late_join:
-            def epilogue():                       # after the next fork (the backward pass's first): no fork of its own
-                ss = eng._side_raw()
-                if world == 1:
-                    call("dvae_loss_epilogue", self.KIND, ptr(sc.partials), ptr(sc.kl_dim), klb, D, ptr(rowstats), B, None, Bg,
-                         ptr(sc.coef), ptr(sc.packed), ptr(sc.scal), ss)
-                else:
-                    # on the exchange stream, behind the estimator; ordered after this stream's fork point through the side
-                    # stream (whose only queued work at this moment is the wait for that fork): no second event on this stream
-                    ss = eng._aux_raw()
-                    call("dvae_stream_order", eng._side_raw(), ss)
-                    xbuf = lat["xbuf"]
-                    packed = sc.packed if xbuf is None else xbuf[xbuf.numel() - npk:]
-                    self._pack_sums(sc, klb, D, rowstats, B, None, packed, ss)
-                    with torch.cuda.stream(eng.aux_stream):
-                        if xbuf is None:
-                            self.comm.all_reduce(packed)
-                        else:                     # + the estimator's column gradients: one collective
-                            self.comm.all_reduce_cols_sums(xbuf, B, D, npk)
-                    call("dvae_loss_finalize", self.KIND, ptr(packed), D, Bg, ptr(sc.coef), ptr(sc.scal), ss)
-                call("dvae_event_record", self._ev_slot, ss)
-            eng.at_next_fork(epilogue)
-        elif world > 1:
-            self._pack_sums(sc, klb, D, rowstats, B, None, sc.packed, s)
-            self.comm.all_reduce(sc.packed)
-            call("dvae_loss_finalize", self.KIND, ptr(sc.packed), D, Bg, ptr(sc.coef), ptr(sc.scal), s)
+            wait = self._defer_loss(eng, lambda stream, on: self._finish_loss(sc, klb, D, rowstats, B, None, Bg, stream, on, xbuf))
         else:
-            call("dvae_loss_epilogue", self.KIND, ptr(sc.partials), ptr(sc.kl_dim), klb, D, ptr(rowstats), B, None, Bg,
-                 ptr(sc.coef), ptr(sc.packed), ptr(sc.scal), s)
+            if btc and world > 1:
+                call("dvae_stream_order", eng._aux_raw(), s)
+            elif btc:
+                eng._join_side()
+            self._finish_loss(sc, klb, D, rowstats, B, None, Bg, s)
         if not is_train:
             return
 
         def fc_chain():        # the six FC input gradients + the reparameterisation / KL backward in ONE launch
-            if late_join:
-                eng.flush_fork_hook()
-                call("dvae_event_wait", self._ev_slot, s)
-            eng.fc_chain_bwd(buf, eps, lat["dz"], None, lat["dmu"], lat["dlv"], sc.scal, sc.coef, B)
-
-        # one join, at the end of the backward pass.  Single process: ONE grouped launch for all six FC weight gradients
-        # (issued by encode_backward).  Sharded: the decoder's three are launched with the decoder's conv weight gradients --
-        # every kernel that writes a decoder gradient goes to the side stream, so the all-reduce of the decoder span is ordered
-        # behind the SIDE stream and overlaps the encoder backward; this stream never waits for it before the end.  Small shards
-        # (SMALL_SHARD_ELEMS: the step is a latency chain, and every collective costs the host and both streams more than the
-        # overlap of 1 MB buys): ONE all-reduce of the whole arena after the final join.
-        spans = world > 1 and data.numel() > self.SMALL_SHARD_ELEMS
-        eng.decode_backward(buf.z, buf, join=False, defer_fc_wgrad=not spans, fc_chain=fc_chain)
-        pending = []
-        if spans:
-            with torch.cuda.stream(eng.side_stream):
-                pending.append(self.comm.all_reduce_async(model.arena.span("decoder.")))
-        eng.encode_backward(data, buf, fc_chain=True)
-        if spans:
-            pending.append(self.comm.all_reduce_async(model.arena.span("encoder.")))
-            for h_ in pending:
-                h_.wait()
-        elif world > 1:
-            self.comm.all_reduce(model.arena.grad)
+            if wait is not None:
+                wait()
+            eng.fc_chain_bwd(buf, eps, dz, None, dmu, dlv, sc.scal, sc.coef, B)
+        self._backward(eng, model, data, buf, B, fc_chain)
 
 
 class BetaHLoss(_SingleOptimizerLoss):
@@ -607,11 +595,6 @@ class BetaHLoss(_SingleOptimizerLoss):
     def _coefs(self, is_train):
         anneal = linear_annealing(0, 1, self.n_train_steps, self.steps_anneal) if is_train else 1
         return dict(ANNEAL=anneal, BETA=self.beta)
-
-    def _store(self, storer, vals, D):
-        storer['recon_loss'].append(vals[_lib.S_REC])
-        self._store_kl(storer, vals, D)
-        storer['loss'].append(vals[_lib.S_LOSS])
 
     def __call__(self, data, recon_data, latent_dist, is_train, storer, **kwargs):
         storer = self._pre_call(is_train, storer)
@@ -642,11 +625,6 @@ class BetaBLoss(_SingleOptimizerLoss):
     def _coefs(self, is_train):
         return dict(ANNEAL=1.0, BETA=self.gamma, CAP=self._capacity(is_train))
 
-    def _store(self, storer, vals, D):
-        storer['recon_loss'].append(vals[_lib.S_REC])
-        self._store_kl(storer, vals, D)
-        storer['loss'].append(vals[_lib.S_LOSS])
-
     def __call__(self, data, recon_data, latent_dist, is_train, storer, **kwargs):
         storer = self._pre_call(is_train, storer)
         sc = self.scratch(recon_data.device)
@@ -662,6 +640,8 @@ class BetaBLoss(_SingleOptimizerLoss):
 class BtcvaeLoss(_SingleOptimizerLoss):
     """losses.py:316-391 (is_mss=True default, never overridden by get_loss_f)."""
     KIND = _lib.LOSS_BTCVAE
+    STORED = (('recon_loss', _lib.S_REC), ('loss', _lib.S_LOSS), ('mi_loss', _lib.S_MI), ('tc_loss', _lib.S_TC),
+              ('dw_kl_loss', _lib.S_DWKL), ('kl_loss', _lib.S_KL))
 
     def __init__(self, n_data, alpha=1., beta=6., gamma=1., is_mss=True, **kwargs):
         super().__init__(**kwargs)
@@ -675,13 +655,38 @@ class BtcvaeLoss(_SingleOptimizerLoss):
         anneal = linear_annealing(0, 1, self.n_train_steps, self.steps_anneal) if is_train else 1
         return dict(ANNEAL=anneal, ALPHA=self.alpha, BETA=self.beta, GAMMA=self.gamma)
 
-    def _store(self, storer, vals, D):
-        storer['recon_loss'].append(vals[_lib.S_REC])
-        storer['loss'].append(vals[_lib.S_LOSS])
-        storer['mi_loss'].append(vals[_lib.S_MI])
-        storer['tc_loss'].append(vals[_lib.S_TC])
-        storer['dw_kl_loss'].append(vals[_lib.S_DWKL])
-        self._store_kl(storer, vals, D)
+    def _estimator(self, eng, buf, sc, B, D, is_train):
+        """The B x B estimator, forward AND backward (it needs z, mu, logvar and the coefficients only), on the side stream --
+        sharded: the exchange stream -- beside the decoder forward -> (rowstats, dz, dmu, dlogvar, xbuf); xbuf: the buffer a
+        sharded step's late epilogue sums over the ranks (else None)."""
+        world = self._world()[0]
+        ew, er = self._est_world()            # the estimator's view of the sharding (local mode: one shard = one batch)
+        Be = B * ew
+        dz_x = dmu_x = dlv_x = xbuf = None
+        with torch.cuda.stream(eng.aux_stream if world > 1 else eng.side_stream):
+            ss = _stream()
+            zg, mug, lvg = buf.z, buf.mu, buf.logvar
+            if ew > 1:
+                zg, mug, lvg = self.comm.all_gather_latents(buf.z, buf.mu, buf.logvar)
+            rowstats = sc.latent("rowstats", B, _lib.rowstats_stride(D))
+            tc_tmp = sc.latent("tc_tmp", 1, _lib.btcvae_tmp_floats(Be, B, D))
+            call("dvae_btcvae_fwd", ptr(zg), ptr(mug), ptr(lvg), Be, D, er * B, B, int(self.is_mss), ptr(sc.log_w),
+                 ptr(tc_tmp), ptr(rowstats), ss)
+            if is_train:
+                dz_x = sc.latent("dz_tc", B, D)
+                # (dmu, dlogvar) of ALL columns: two slabs of one buffer, followed by the packed loss sums -- sharded, the
+                # lot is summed over the ranks by ONE all-reduce in the step's late epilogue (Comm.all_reduce_cols_sums)
+                slabs = sc.latent("xbuf", 1, 2 * Be * D + _lib.npack(D)).view(-1)
+                dmu_x, dlv_x = slabs[:Be * D].view(Be, D), slabs[Be * D:2 * Be * D].view(Be, D)
+                call("dvae_btcvae_bwd", ptr(zg), ptr(mug), ptr(lvg), ptr(rowstats), Be, D, er * B, B,
+                     int(self.is_mss), ptr(sc.log_w), ptr(sc.coef), ptr(tc_tmp), ptr(dz_x), ptr(dmu_x), ptr(dlv_x), ss)
+                if ew > 1:
+                    xbuf = slabs
+                    dmu_x, dlv_x = dmu_x[er * B:(er + 1) * B], dlv_x[er * B:(er + 1) * B]
+                if world > ew:                # local estimator: its mean runs over B, the loss over B * world
+                    for t_ in (dz_x, dmu_x, dlv_x):
+                        scale_(t_, 1.0 / world)
+        return rowstats, dz_x, dmu_x, dlv_x, xbuf
 
     def __call__(self, data, recon_batch, latent_dist, is_train, storer, latent_sample=None):
         storer = self._pre_call(is_train, storer)
@@ -709,6 +714,9 @@ class FactorKLoss(BaseLoss):
     # the side stream carries the discriminator's chain as well: from 2048 rows per step the VAE's weight gradients go to two
     # side streams (BaseLoss.THREE_STREAM_MIN_ROWS: tensor 2048 1.853 -> 1.832 ms, tensor 256 0.561 -> 0.592)
     THREE_STREAM_MIN_ROWS = 2048
+    KIND = _lib.LOSS_FACTOR
+    STORED = (('recon_loss', _lib.S_REC), ('kl_loss', _lib.S_KL), ('loss', _lib.S_LOSS), ('tc_loss', _lib.S_TC),
+              ('discrim_loss', _lib.S_DTC))
 
     def __init__(self, device, gamma=10., disc_kwargs={}, optim_kwargs=dict(lr=5e-5, betas=(0.5, 0.9)), **kwargs):
         super().__init__(**kwargs)
@@ -749,11 +757,8 @@ class FactorKLoss(BaseLoss):
         eng._fork_hook = None                  # a hook left behind by a step that raised is dropped, not run (nor recorded)
         disc = self.discriminator
         D = model.latent_dim
-        B = data.size(0)
-        Bh = B // 2
-        world, rank = self._world()
-        Bhg = Bh * world
-        dev = data.device
+        Bh = data.size(0) // 2
+        world = self._world()[0]
         s = _stream()
         # the N(0,1) draws of both halves in ONE [2*Bh, D] buffer (rows < Bh: data1, losses.py:254; the rest:
         # sample_latent(data2), losses.py:286) -- two separate draws, like the reference, into its two halves
@@ -764,8 +769,7 @@ class FactorKLoss(BaseLoss):
         else:
             record_py(eps12[:Bh].copy_, eps1)
             record_py(eps12[Bh:].copy_, eps2)
-        eps1 = eps12[:Bh]
-        buf = eng.buffers(B)
+        buf = eng.buffers(data.size(0))
         data = eng.input(data, buf)
         eng.encode_convs(data, buf, n=2 * Bh, chain=True)                         # data1 and data2 in one pass
         # FC core of both halves in one launch; KL only over data1 with the half batch as denominator (losses.py:255-259),
@@ -773,16 +777,12 @@ class FactorKLoss(BaseLoss):
         eng.fc_chain_fwd(buf, eps12, sc.kl_dim, 2 * Bh, n_kl=Bh, n_dec=Bh, coef=sc.coef)
         klb = eng.kl_blocks(2 * Bh)
         eng.decode_convs(buf, Bh, fuse_loss=(data, self._rec_code(), sc.coef, sc.partials), chain=True)
-        off = Bh
         # z_perm: permute across the (global) half batch, losses.py:287
         zin = sc.latent("disc_in", 2 * Bh, D)
         copy_flat_(zin[:Bh], buf.z[:Bh])
-        z2 = buf.z[off:off + Bh]
+        z2 = buf.z[Bh:2 * Bh]
         ew, er = self._est_world()                # scope of permute_dims: global half batch, or this shard ("local")
-        if ew > 1:
-            z2g = self.comm.all_gather_rows(z2)
-        else:
-            z2g = z2
+        z2g = self.comm.all_gather_rows(z2) if ew > 1 else z2
         zperm_g = sc.latent("zperm_g", Bh * ew, D)
         call("dvae_permute_dims", ptr(z2g.contiguous()), ptr(perms), ptr(zperm_g), Bh * ew, D, s)
         copy_flat_(zin[Bh:], zperm_g[er * Bh:(er + 1) * Bh])
@@ -794,34 +794,14 @@ class FactorKLoss(BaseLoss):
             # the CE / tc means run over the global half batch
             scale_(g_dtc, 1.0 / world)
             scale_(g_tc, 1.0 / world)
-
         # the scalar epilogue (13 us; sharded: KL finish + pack + all-reduce of the packed sums + finalize) is first needed by
-        # the FC chain's input gradients, after the discriminator's and the decoder's backward passes: it runs on the side
-        # stream, an event slot marks it (as in the btcvae step)
-        def epilogue(on_side):
-            stream = eng._side_raw() if on_side else s
-            if world > 1 and on_side:             # sharded: the exchange stream (see the btcvae step), ordered through the side stream
-                stream = eng._aux_raw()
-                call("dvae_stream_order", eng._side_raw(), stream)
-            if world == 1:
-                call("dvae_loss_epilogue", _lib.LOSS_FACTOR, ptr(sc.partials), ptr(sc.kl_dim), klb, D, None, 0,
-                     ptr(sc.disc_sums), Bhg, ptr(sc.coef), ptr(sc.packed), ptr(sc.scal), stream)
-                return
-            self._pack_sums(sc, klb, D, None, 0, sc.disc_sums, sc.packed, stream)
-            with torch.cuda.stream(eng.aux_stream if on_side else torch.cuda.current_stream()):
-                self.comm.all_reduce(sc.packed)
-            call("dvae_loss_finalize", _lib.LOSS_FACTOR, ptr(sc.packed), D, Bhg, ptr(sc.coef), ptr(sc.scal), stream)
-            if on_side:
-                call("dvae_event_record", self._ev_slot, stream)
-        late_epi = not eng.single_stream and knob("DVAE_LATE_JOIN", "1") != "0"
-        if late_epi:                          # after the next fork (the backward pass's first): no fork of its own
-            def deferred():
-                epilogue(True)
-                if world == 1:
-                    call("dvae_event_record", self._ev_slot, eng._side_raw())
-            eng.at_next_fork(deferred)
+        # the FC chain's input gradients, after the discriminator's and the decoder's backward passes: deferred (_defer_loss)
+        wait = None
+        if not eng.single_stream and knob("DVAE_LATE_JOIN", "1") != "0":
+            wait = self._defer_loss(eng, lambda stream, on: self._finish_loss(sc, klb, D, None, 0, sc.disc_sums, Bh * world,
+                                                                              stream, on))
         else:
-            epilogue(False)
+            self._finish_loss(sc, klb, D, None, 0, sc.disc_sums, Bh * world, s)
         # discriminator backward of d_tc_loss (weight grads + dz), losses.py:303-304
         # (its six weight gradients: on the side stream, behind one fork after the input-gradient chain)
         side_wg = not eng.single_stream and knob("DVAE_DISC_WGRAD_SIDE", "1") != "0"
@@ -848,25 +828,34 @@ class FactorKLoss(BaseLoss):
             # dz_a: quirk Q1 (the encoder also receives d[0.5 CE(D(z1),0)]/dz1); dz_b: the tc term through D
             if par2:
                 call("dvae_stream_order", eng._aux_raw(), s)
-            if late_epi:
-                eng.flush_fork_hook()
-                call("dvae_event_wait", self._ev_slot, s)
-            eng.fc_chain_bwd(buf, eps1, dz_a, dz_b, None, None, sc.scal, sc.coef, Bh)
+            if wait is not None:
+                wait()
+            eng.fc_chain_bwd(buf, eps12[:Bh], dz_a, dz_b, None, None, sc.scal, sc.coef, Bh)
+        self._backward(eng, model, data, buf, Bh, fc_chain, pending)
 
-        # one join, at the end of encode_backward; sharded: the decoder span's all-reduce is ordered behind the side stream
-        # (every decoder gradient is written there) and overlaps the encoder backward
-        spans = world > 1 and data.numel() > self.SMALL_SHARD_ELEMS      # small shards: ONE all-reduce of the whole VAE arena (see the btcvae step)
-        eng.decode_backward(buf.z, buf, n=Bh, join=False, defer_fc_wgrad=not spans, fc_chain=fc_chain)
-        if spans:
-            with torch.cuda.stream(eng.side_stream):
-                pending.append(self.comm.all_reduce_async(model.arena.span("decoder.")))
-        eng.encode_backward(data, buf, n=Bh, fc_chain=True)
-        if spans:
-            pending.append(self.comm.all_reduce_async(model.arena.span("encoder.")))
-        elif world > 1:
-            self.comm.all_reduce(model.arena.grad)
-        for h_ in pending:
-            h_.wait()
+    def _eval_step(self, data, model, sc):
+        """Evaluation: vae_loss only (losses.py:276-278) on data1, z = mean; the discriminator on z1."""
+        eng, disc = model.engine, self.discriminator
+        D = model.latent_dim
+        Bh = data.size(0) // 2
+        s = _stream()
+        buf = eng.buffers(data.size(0))
+        data = eng.input(data, buf)
+        eng.encode_convs(data, buf, n=Bh, chain=True)
+        # KL over data1 with the half batch as denominator (losses.py:255-259)
+        eng.fc_chain_fwd(buf, None, sc.kl_dim, Bh, coef=sc.coef)
+        if eng.kl_blocks(Bh):
+            call("dvae_kl_finish", ptr(sc.kl_dim), eng.kl_blocks(Bh), ptr(sc.coef), D, s)
+        eng.decode_convs(buf, Bh, fuse_loss=(data, self._rec_code(), sc.coef, sc.partials), chain=True)
+        logits = disc.forward_raw(buf.z, Bh)
+        g_dtc = sc.latent("g_dtc", 2 * Bh, 2)
+        lg2 = sc.latent("lg2", 2 * Bh, 2)
+        lg2[:Bh].copy_(logits[:Bh]); lg2[Bh:].copy_(logits[:Bh])
+        call("dvae_disc_losses", ptr(lg2), Bh, ptr(sc.coef), ptr(sc.disc_sums), ptr(g_dtc), None, s)
+        call("dvae_loss_pack", ptr(sc.partials), ptr(sc.kl_dim), D, None, 0, ptr(sc.disc_sums), ptr(sc.packed), s)
+        if self._world()[0] > 1:
+            self.comm.all_reduce(sc.packed)
+        call("dvae_loss_finalize", self.KIND, ptr(sc.packed), D, Bh * self._world()[0], ptr(sc.coef), ptr(sc.scal), s)
 
     def call_optimize(self, data, model, optimizer, storer, noise=None):
         """noise: optional (eps1[Bh,D], eps2[Bh,D], perms int64[D,Bh]) injected for parity;
@@ -874,82 +863,34 @@ class FactorKLoss(BaseLoss):
         CPU generator, in the reference's order (losses.py:254,286,505)."""
         is_train = model.training
         storer = self._pre_call(is_train, storer)
-        eng = model.engine
-        disc = self.discriminator
         D = model.latent_dim
-        B = data.size(0)
-        Bh = B // 2
-        world, rank = self._world()
-        Bhg = Bh * world
-        dev = data.device
-        s = _stream()
-        sc = self.scratch(dev).for_latent_dim(D)
+        Bh = data.size(0) // 2
+        sc = self.scratch(data.device).for_latent_dim(D)
         anneal = linear_annealing(0, 1, self.n_train_steps, self.steps_anneal) if is_train else 1
-        sc.set_coef_host(INV_B=1.0 / Bhg, ANNEAL=anneal, BETA=self.gamma)
-        eng.stage(sc.coef, sc.coef_host)       # ONE launch: this step's weight images + its loss coefficients
+        sc.set_coef_host(INV_B=1.0 / (Bh * self._world()[0]), ANNEAL=anneal, BETA=self.gamma)
+        model.engine.stage(sc.coef, sc.coef_host)       # ONE launch: this step's weight images + its loss coefficients
         data = data.contiguous()
         self._streams(model, data)
-        if noise is not None:
-            eps1, eps2, perms = noise
-        else:
-            eps1 = eps2 = perms = None       # training draws them on the device in _device_step
-        if is_train:
-            slot = None
-            if perms is None:
-                # CPU generator (shared seed across ranks), reference order losses.py:505 -- drawn straight into a pinned
-                # staging buffer: the copy to the device is then truly asynchronous (from pageable memory it blocks the host
-                # until every launch enqueued before it has run, i.e. the host could never run ahead of the GPU)
-                perms, slot = self._draw_perms(D, Bh * self._est_world()[0])
-            perms = perms.to(dtype=torch.int64)
-            mode = self._replay_mode(True, data)
-            if mode == "graph":
-                data = self._static_buf("data", data)
-            perms = self._static_buf("perms", perms)      # device copy (non-blocking from the pinned ring)
-            if slot is not None:
-                slot[1] = torch.cuda.Event()
-                slot[1].record()                          # the staging buffer is free again once this has passed
-            if mode:
-                if noise is not None:
-                    eps1, eps2 = self._static_buf("eps1", eps1), self._static_buf("eps2", eps2)
-                self._graphs.run(self._replay_key(model, data, noise is not None) + (disc.arena.flat.data_ptr(),),
-                                 lambda: self._device_step(data, model, sc, eps1, eps2, perms), mode)
-            else:
-                self._device_step(data, model, sc, eps1, eps2, perms)
-        else:
-            buf = eng.buffers(B)
-            data = eng.input(data, buf)
-            eng.encode_convs(data, buf, n=Bh, chain=True)
-            # z = mean; KL over data1 with the half batch as denominator (losses.py:255-259)
-            eng.fc_chain_fwd(buf, None, sc.kl_dim, Bh, coef=sc.coef)
-            if eng.kl_blocks(Bh):
-                call("dvae_kl_finish", ptr(sc.kl_dim), eng.kl_blocks(Bh), ptr(sc.coef), D, s)
-            eng.decode_convs(buf, Bh, fuse_loss=(data, self._rec_code(), sc.coef, sc.partials), chain=True)
-            # evaluation: vae_loss only (losses.py:276-278); discriminator on z1
-            logits = disc.forward_raw(buf.z, Bh)
-            g_dtc = sc.latent("g_dtc", 2 * Bh, 2)
-            lg2 = sc.latent("lg2", 2 * Bh, 2)
-            lg2[:Bh].copy_(logits[:Bh]); lg2[Bh:].copy_(logits[:Bh])
-            call("dvae_disc_losses", ptr(lg2), Bh, ptr(sc.coef), ptr(sc.disc_sums), ptr(g_dtc), None, s)
-            call("dvae_loss_pack", ptr(sc.partials), ptr(sc.kl_dim), D, None, 0, ptr(sc.disc_sums), ptr(sc.packed), s)
-            if world > 1:
-                self.comm.all_reduce(sc.packed)
-            call("dvae_loss_finalize", _lib.LOSS_FACTOR, ptr(sc.packed), D, Bhg, ptr(sc.coef), ptr(sc.scal), s)
-            if storer is not None:
-                vals = sc.scal.tolist()
-                storer['recon_loss'].append(vals[_lib.S_REC])
-                self._store_kl(storer, vals, D)
-                storer['loss'].append(vals[_lib.S_LOSS])
-                storer['tc_loss'].append(vals[_lib.S_TC])
+        if not is_train:
+            self._eval_step(data, model, sc)
+            self._store(storer, sc, D, self.STORED[:-1])
             return sc.scal[_lib.S_LOSS]
+        eps1, eps2, perms = noise if noise is not None else (None, None, None)     # (eps: drawn on the device in _device_step)
+        slot = None
+        if perms is None:
+            # CPU generator (shared seed across ranks), reference order losses.py:505 -- drawn straight into a pinned
+            # staging buffer: the copy to the device is then truly asynchronous (from pageable memory it blocks the host
+            # until every launch enqueued before it has run, i.e. the host could never run ahead of the GPU)
+            perms, slot = self._draw_perms(D, Bh * self._est_world()[0])
+        perms = self._static_buf("perms", perms.to(dtype=torch.int64))      # device copy (non-blocking from the pinned ring)
+        if slot is not None:
+            slot[1] = torch.cuda.Event()
+            slot[1].record()                          # the staging buffer is free again once this has passed
+        self._run_step(model, data, [("eps1", eps1), ("eps2", eps2)], noise is not None, (self.discriminator.arena.flat.data_ptr(),),
+                       lambda data, eps1, eps2: self._device_step(data, model, sc, eps1, eps2, perms))
         model.assign_grads()
-        disc.assign_grads()
+        self.discriminator.assign_grads()
         optim.step(optimizer)         # optimizer.step(), losses.py:307
         optim.step(self.optimizer_d)  # losses.py:308
-        if storer is not None:
-            vals = sc.scal.tolist()
-            storer['recon_loss'].append(vals[_lib.S_REC])
-            self._store_kl(storer, vals, D)
-            storer['loss'].append(vals[_lib.S_LOSS])
-            storer['tc_loss'].append(vals[_lib.S_TC])
-            storer['discrim_loss'].append(vals[_lib.S_DTC])
+        self._store(storer, sc, D)
         return sc.scal[_lib.S_LOSS]

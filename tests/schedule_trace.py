@@ -11,6 +11,8 @@ as a list of entries such as
 are scheduled alike share one trace).  The grouped FC weight-gradient launch records its problem list in place of the
 host address of its descriptor array; ``fc_chain`` and the ``at_next_fork`` hook are markers.
 
+The whole step around the backward pass (forward, loss epilogue, exchanges: models/losses.py) is tests/step_trace.py's.
+
 tests/test_backward_schedule.py compares these traces with tests/golden/backward_launch_trace.json.  To print one:
 
   python tests/schedule_trace.py 3,64,64 10 1024 default float32 step
