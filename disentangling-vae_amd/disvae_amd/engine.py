@@ -21,6 +21,7 @@ import torch
 from . import _lib
 from ._debug import knob
 from ._lib import call, ptr, record_py, NCHW, NHWC, ACT_NONE, ACT_RELU, ACT_SIGMOID
+from .schedule import build_policy, switches, TAIL_MAIN as _TAIL_MAIN  # noqa: F401  (the name this constant had here)
 
 HID = 32
 HIDDEN_DIM = 256
@@ -104,12 +105,6 @@ class ParamArena:
         self.grad = self.grad.to(device)
         return self
 
-
-# which encoder conv weight gradients the MAIN stream computes itself at the very end of the backward pass (after conv1's),
-# instead of leaving them in the side stream's queue: the side stream is the tail of the iteration (timeline:
-# profiles/r02_final_timeline.md), the main stream is idle from the end of conv1's weight gradient to the join
-# (measured -1.5 %: profiles/r02_run12_tail_ab.txt)
-_TAIL_MAIN = ("conv3", "conv_64")
 
 # launch queues of the backward pass (VAEEngine._queue): the caller's stream and the two weight-gradient streams
 MAIN, SIDE, WG2 = 0, 1, 2
@@ -257,72 +252,25 @@ class VAEEngine:
         self._wg2 = None
         self._side = None      # side HIP stream: the weight-gradient kernels run beside the dgrad chain
         self._aux = None       # exchange stream of sharded steps (see buffers())
-        # small batches: everything on the caller's stream.  Below ~256 images the iteration is bound by the latency of
-        # dependent launches, a fork / join between hardware queues costs ~6 us each (5 forks + 1 join per iteration) and
-        # the weight-gradient kernels that the side stream would overlap are a few microseconds long.  Set per step by the
-        # loss plugins (BaseLoss._streams).
-        self.single_stream = False
-        # how the weight gradients are scheduled against the chain of input gradients (two streams):
-        #   False: batch-sized schedule -- the big layers' weight gradients are forked behind the big input gradients (two
-        #          chip-filling persistent kernels do not co-run: what matters is that the small kernels of the critical path
-        #          find idle CUs), the tail is balanced between the streams (measured at B = 1024: DESIGN.md section 5);
-        #   True : dependency-driven -- every weight gradient is launched on the side stream as soon as its two operands
-        #          exist (a fork per layer), beside the input gradient of the same layer.  Below a few hundred images per
-        #          step no kernel fills the chip, the iteration is a latency chain, and the side stream should start as
-        #          early as the data allows (profiles/r03_v2_timeline_b128.md: backward pass 287 us against ~150 us of
-        #          dependent work).  Set per step by the loss plugins (BaseLoss._streams).
-        self.eager_wgrad = False
-        # encoder weight gradients the MAIN stream computes after conv1's, at the very end of the backward pass (the balance of
-        # the two streams' tails).  Set per step by the loss plugins (BaseLoss._streams).
-        self.tail_main = _TAIL_MAIN
-        self._fork_hook = None
         # 64x64 images with 1 / 3 channels: the forward kernels of conv1 and convT2 also emit the sign bits of their outputs and
         # the input-gradient kernels of conv2 and convT3 read those instead of the 32x32x32 fp32 activations (dvae_*_bits)
         self.mask_bits = self.is64 and c in (1, 3) and knob("DVAE_MASK_BITS", "1") != "0"   # (A/B knob: DVAE_DEBUG=1 only)
-        # fused FC chain: the 8x8 <-> 4x4 layers (conv_64 / convT_64 at 64x64, conv3 / convT1 at 32x32) and their input
-        # gradients run INSIDE the chain launches (dvae_fc_chain_fwd / _bwd, conv_in / convT_gout fields: csrc/conv4_end.h) --
-        # four launches fewer on the critical path
-        # Up to fuse_ends_max_rows rows per launch, where the step is a chain of dependent launches and each one saved counts
-        # (same box, three alternations, profiles/r06_s2_chain3.txt: factor 64x64x1 tensor 256 0.590 -> 0.569 ms, btcvae 64x64x3 at
-        # 64 / 128 / 256 images 0.311 -> 0.302, 0.347 -> 0.344, 0.450 -> 0.447 ms); from 512 rows up the fused launches -- 150 KB
-        # of LDS, a whole CU per workgroup -- can no longer slip in beside the other stream's persistent kernels the way the
-        # small conv launches do: 0.643 -> 0.652 ms at 512 images, 1.060 -> 1.082 ms at 1024 (profiles/r06_s2_chain2.txt) -- in
-        # the BACKWARD pass, that is (fuse_ends_max_rows); the forward chain has its own limit below
-        self.fuse_ends = not _lib.wide(latent_dim) and knob("DVAE_FUSE_ENDS", "1") != "0"   # (A/B knob: DVAE_DEBUG=1 only)
-        self.fuse_ends_max_rows = int(knob("DVAE_FUSE_ENDS_MAX_ROWS", "256"))
-        # the FORWARD chain's own limit: beside it the other stream carries only the estimator's small kernels, nothing a 150 KB
-        # workgroup could block -- 384 / 512 / 1024 images 0.545 -> 0.543, 0.631 -> 0.629, 1.039 -> 1.030 ms; level at 2048 rows,
-        # where the 8-row variant runs (profiles/r06_s2_fwd_ends.txt)
-        self.fuse_ends_max_rows_fwd = int(knob("DVAE_FUSE_ENDS_MAX_ROWS_FWD", "1024"))
-        # Round 6: convT3's weight gradient (bandwidth-bound) is forked one kernel earlier -- behind convT3's input gradient, beside
-        # the matrix-bound input gradient of convT2 -- instead of behind both.  The side stream's serial chain of weight gradients
-        # is what small steps end on, and it now starts ~15 us sooner: 128 / 256 images 0.341 -> 0.330, 0.443 -> 0.431 ms,
-        # btcvae 64x64x1 B = 256 0.412 -> 0.398, 1024 images 1.054 -> 1.048 ms (profiles/r06_s2_sched2.txt).  Mode 2 (in FRONT of
-        # convT3's input gradient) wins another 1-2 % at 128 images and loses 1.6 % at 256, 0.7 % at 1024 (r06_s2_sched3.txt): used at
-        # 112-128 images only (_decode_convs_batch).
-        # Moving the main stream's tail (tail_main) to the side stream loses 2-8 % at every small batch (same file).
-        _et = knob("DVAE_EARLY_THIN", "auto")                          # (A/B knob: DVAE_DEBUG=1 only: 0 / 1 / 2 force a mode)
-        self.early_thin_wgrad = 1 if _et == "auto" else int(_et)
-        self.early_thin_auto = _et == "auto"
-        self.sharded = False   # this step runs under data parallelism (set per step by the loss plugins, BaseLoss._streams)
-        # the weight gradients on TWO side streams, each launched at the first fork behind the kernel that produces its last operand
-        # (_decode_backward_3q / _encode_backward_3q).  Set per step by the loss plugins (BaseLoss._streams: FactorVAE
-        # from 2048 rows; slower for every other step measured).
-        self.three_streams = False
-        # steps of 129-320 images end on the side stream (its weight-gradient grid is the smaller one there, conv_wgrad_ws.hip): the
-        # grouped FC weight gradients become the LAST launch of the main stream's tail instead -- 256 images 0.425 -> 0.415 ms,
-        # btcvae 64x64x1 B = 256 0.386 -> 0.375; outside that band the main stream is the tail already: 64 / 128 / 512 / 1024
-        # images +1.3 / +1.4 / +2.1 / +0.6 % (profiles/r06_s2_fcw_main.txt)
-        self.fcw_main = knob("DVAE_FCW_MAIN", "1") == "1"
-        self.fcw_main_rows = tuple(int(v) for v in knob("DVAE_FCW_MAIN_ROWS", "129,320").split(","))
-        self._ends_on = False  # this forward pass: set by encode_convs(chain=True), read by fc_chain_fwd / decode_convs
-        self._fc_pending = []  # FC weight-gradient problems waiting for the grouped launch (decoder's, deferred)
+        # every scheduling decision of the step under way (schedule.StepPolicy): handed over by begin_step, read-only here.
+        # Until the first one: the policy of a one-image step
+        self.begin_step(build_policy(self.img_size, latent_dim, 1, switches()))
         self._fc_descs = {}    # host descriptor arrays / argument structs of launches, kept alive for recorded plans
         self._images = None
 
     @property
     def device(self):
         return self.arena.flat.device
+
+    def begin_step(self, policy):
+        """The ONE entry through which scheduling decisions reach the engine, once per step (the loss plugins) or backward pass
+        (the autograd-compatible entry points): everything below reads self.policy.  Per-pass state starts clean: a fork hook
+        left behind by a step that raised is dropped, not run (nor recorded)."""
+        self.policy = policy
+        self._fork_hook = None
 
     def p(self, name):
         return self.arena.view(name)
@@ -392,7 +340,7 @@ class VAEEngine:
         """Order the side stream (wg2: the second one, three_streams) after everything enqueued so far on the current
         stream.  A fork costs the current stream ~6 us (event signal between hardware queues, profiles/r01_run19
         timeline), so the FC weight gradients fork once per chain, not once per layer."""
-        if self.single_stream:
+        if self.policy.single_stream:
             return
         if wg2:
             call("dvae_stream_order", _stream(), self._wg2.cuda_stream)
@@ -405,12 +353,12 @@ class VAEEngine:
     def at_next_fork(self, fn):
         """Side-stream work that needs everything enqueued on the current stream SO FAR but is not urgent: `fn()` is called
         right after the next fork_side() instead of paying for a fork of its own (each costs the current stream ~6 us)."""
-        if knob("DVAE_FORK_HOOK", "1") == "0":      # A/B (DVAE_DEBUG=1): a fork of its own, right here
+        if not self.policy.fork_hook:               # A/B (DVAE_DEBUG=1 DVAE_FORK_HOOK=0): a fork of its own, right here
             self._fork_hook = None
             self.fork_side()
             fn()
             return
-        self._fork_hook = fn                   # (the loss plugins clear a hook left behind by a step that raised)
+        self._fork_hook = fn
 
     def flush_fork_hook(self):
         """A consumer of the deferred side-stream work is about to be enqueued: if no fork has happened yet, fork now."""
@@ -419,17 +367,17 @@ class VAEEngine:
 
     @property
     def side_stream(self):
-        return torch.cuda.current_stream() if self.single_stream else self._side
+        return torch.cuda.current_stream() if self.policy.single_stream else self._side
 
     def _side_raw(self):
-        return _stream() if self.single_stream else self._side.cuda_stream
+        return _stream() if self.policy.single_stream else self._side.cuda_stream
 
     @property
     def aux_stream(self):
-        return torch.cuda.current_stream() if self.single_stream else self._aux
+        return torch.cuda.current_stream() if self.policy.single_stream else self._aux
 
     def _aux_raw(self):
-        return _stream() if self.single_stream else self._aux.cuda_stream
+        return _stream() if self.policy.single_stream else self._aux.cuda_stream
 
     def _queue(self, q):
         """(partial-sum workspace, hipStream_t) of launch queue q: MAIN = the current stream, SIDE / WG2 = the two
@@ -462,7 +410,7 @@ class VAEEngine:
         call(*wgrad, ptr(ws), stream)
 
     def _join_side(self, wg2=False):
-        if self.single_stream:
+        if self.policy.single_stream:
             return
         call("dvae_stream_order", (self._wg2 if wg2 else self._side).cuda_stream, _stream())
 
@@ -494,15 +442,16 @@ class VAEEngine:
     def encode_convs(self, x, buf, n=None, chain=False):
         """x[B,C,H,W] (NCHW; fp32, or uint8 for the fused geometry: see input()) -> buf.a_flat[B,512]: the conv stack of
         encoders.py:73-80.  The 32-channel layers read their pre-staged weight images (stage() must precede).
-        chain: fc_chain_fwd follows -- with fuse_ends it computes conv_64 itself, the stack stops at conv3's output."""
+        chain: fc_chain_fwd follows -- with the policy's fuse_ends it computes conv_64 itself and the stack stops at conv3's
+        output.  Returns whether it does: the `ends` argument of that fc_chain_fwd and of decode_convs."""
         s = _stream()
         B = x.shape[0] if n is None else n
         c, H, _ = self.img_size
         src, h = x, H
         last = len(self.enc_names) - 1
-        self._ends_on = chain and self.fuse_ends and B <= self.fuse_ends_max_rows_fwd
+        ends = chain and self.policy.ends_fwd(B)
         for k, (name, act) in enumerate(zip(self.enc_names, buf.enc_act)):
-            if self._ends_on and k == last:
+            if ends and k == last:
                 break
             # the last conv writes its 4x4x32 output NCHW = the (c,h,w) flatten order lin1 consumes
             # (encoders.py:80), straight into a_flat: no relayout pass; no conv kernel reads that tensor
@@ -521,6 +470,7 @@ class VAEEngine:
                 call("dvae_conv4s2_fwd", ptr(src), NCHW, ptr(self.p(lname + ".weight")), ptr(self.p(lname + ".bias")),
                      ptr(dst), dst_layout, B, c, h, h, HID, ACT_RELU, s)
             src, h = act, h // 2
+        return ends
 
     def encode(self, x, buf, n=None):
         """x -> buf.ml[B,2D] (interleaved mu/logvar), layer by layer (the autograd-compatible entry points; the native
@@ -550,10 +500,11 @@ class VAEEngine:
         r = _lib.fc_chain_rows(n_enc)
         return (n_enc + r - 1) // r
 
-    def fc_chain_fwd(self, buf, eps, kl_dim, n_enc, n_kl=None, n_dec=None, coef=None):
+    def fc_chain_fwd(self, buf, eps, kl_dim, n_enc, n_kl=None, n_dec=None, coef=None, ends=False):
         """buf.a_flat -> h1, h2, ml, mu, logvar, z (rows < n_enc; KL partial blocks from rows < n_kl at kl_dim + 16) and
         d1, d2, d3 (rows < n_dec) in ONE launch (dvae_fc_chain_fwd): encoders.py:81-87, vae.py:52-71, losses.py:470,
-        decoders.py:71-73.  eps [n_enc, D] or None (z = mu).
+        decoders.py:71-73.  eps [n_enc, D] or None (z = mu).  ends: what encode_convs(chain=True) returned -- the launch also
+        computes conv_64 in front of the chain and convT_64 behind it.
         Latent dimensions above _lib.MAX_LATENT_DIM: the same tensors from one launch per layer (_fc_layers_fwd); kl_dim then
         receives the D FINAL per-dimension values, normalised by coef[INV_B] (`coef` is required with kl_dim)."""
         n_kl = n_enc if n_kl is None else n_kl
@@ -563,7 +514,7 @@ class VAEEngine:
         if n_enc > _lib.FC_CHAIN_MAX_ROWS:
             raise _lib.DvaeHipError("fc_chain_fwd: at most %d rows per launch" % _lib.FC_CHAIN_MAX_ROWS)
         P, I = self.p, self._img
-        addr = self._args(("fcf", id(buf), ptr(eps), ptr(kl_dim), n_enc, n_kl, n_dec, self._images.buf.data_ptr(), self._ends_on),
+        addr = self._args(("fcf", id(buf), ptr(eps), ptr(kl_dim), n_enc, n_kl, n_dec, self._images.buf.data_ptr(), ends),
                           _lib.FcChainFwdArgs, a_flat=ptr(buf.a_flat),
                           w_e1=I("encoder.lin1", "fwd"), w_e2=I("encoder.lin2", "fwd"), w_ml=I("encoder.mu_logvar_gen", "fwd"),
                           w_d1=I("decoder.lin1", "fwd"), w_d2=I("decoder.lin2", "fwd"), w_d3=I("decoder.lin3", "fwd"),
@@ -572,17 +523,15 @@ class VAEEngine:
                           b_d2=ptr(P("decoder.lin2.bias")), b_d3=ptr(P("decoder.lin3.bias")), eps=ptr(eps),
                           h1=ptr(buf.h1), h2=ptr(buf.h2), ml=ptr(buf.ml), mu=ptr(buf.mu), logvar=ptr(buf.logvar), z=ptr(buf.z),
                           kl_part=None if kl_dim is None else ptr(kl_dim) + 64, d1=ptr(buf.d1), d2=ptr(buf.d2), d3=ptr(buf.d3),
-                          n_enc=n_enc, n_kl=n_kl, n_dec=n_dec, D=self.latent_dim, **self._ends_fwd(buf, n_dec))
+                          n_enc=n_enc, n_kl=n_kl, n_dec=n_dec, D=self.latent_dim, **(self._ends_fwd(buf, n_dec) if ends else {}))
         call("dvae_fc_chain_fwd", addr, _stream())
 
     def _ends(self, rows):
-        """Do the chain launches over `rows` rows carry the 4x4 conv ends?"""
-        return self.fuse_ends and rows <= self.fuse_ends_max_rows
+        """Do the backward chain launches over `rows` rows carry the 4x4 conv ends?"""
+        return self.policy.ends(rows)
 
     def _ends_fwd(self, buf, n_dec):
         """dvae_fc_chain_fwd_args' conv_in .. convT_out: conv_64 in front of the chain, convT_64 behind it (fuse_ends)."""
-        if not self._ends_on:
-            return {}
         P, I = self.p, self._img
         enc, dec = "encoder." + self.enc_names[-1], "decoder." + self.dec_names[0]
         d = dict(conv_in=ptr(buf.enc_act[-2]), conv_w=I(enc, "down"), conv_b=ptr(P(enc + ".bias")))
@@ -635,7 +584,7 @@ class VAEEngine:
             return self._fc_layers_bwd(buf, eps, dz2, dz3, dmu_x, dlv_x, scal, coef, n)
         I = self._img
         ends = {}
-        if self._ends(n):      # convT_64's input gradient in front of the chain, conv_64's behind it (dvae_fc_chain_bwd_args)
+        if self._ends(n):   # convT_64's input gradient in front of the chain, conv_64's behind it (dvae_fc_chain_bwd_args)
             ends = dict(convT_gout=ptr(buf.dec_gact[0]), convT_w=I("decoder." + self.dec_names[0], "down"), d3=ptr(buf.d3),
                         conv_w=I("encoder." + self.enc_names[-1], "up"), conv_act=ptr(buf.enc_act[-2]),
                         conv_gin=ptr(buf.enc_gact[-2]))
@@ -651,11 +600,11 @@ class VAEEngine:
                           gh1=ptr(buf.gh1), ga_flat=ptr(buf.ga_flat), n=n, D=self.latent_dim, **ends)
         call("dvae_fc_chain_bwd", addr, _stream())
 
-    def decode_convs(self, buf, n, fuse_loss=None, chain=False):
+    def decode_convs(self, buf, n, fuse_loss=None, ends=False):
         """buf.d3[B,512] -> buf.recon[B,C,H,W] (NCHW, post-sigmoid): the convT stack of decoders.py:74-82.
         fuse_loss = (target, dist_code, coef, partials): the last layer also evaluates the reconstruction likelihood
         against `target` (partial sums -> partials) and writes dLoss/dlogit into buf.g_logit in the same pass.
-        chain: fc_chain_fwd preceded -- with fuse_ends it has computed convT_64 already (buf.dec_act[0])."""
+        ends: the fc_chain_fwd in front carried the conv ends -- it has computed convT_64 already (buf.dec_act[0])."""
         s = _stream()
         B = n
         # lin3's output [B, 32*4*4] in (c,h,w) order IS the NCHW 4x4x32 input of the first convT
@@ -663,7 +612,7 @@ class VAEEngine:
         src, src_layout, h = buf.d3, NCHW, 4
         for name, act in zip(self.dec_names, buf.dec_act):
             lname = "decoder.%s" % name
-            if chain and self._ends_on and h == 4:
+            if ends and h == 4:
                 src, src_layout, h = act, NHWC, 8
                 continue
             if self.mask_bits and h == 16:          # convT2: also emits the sign bits of its output (convT3's backward mask)
@@ -822,7 +771,7 @@ class VAEEngine:
     # none of its own: fork_side / _join_side do nothing and SIDE is the current stream.
     def _three(self, chain):
         """The backward pass of this step puts its weight gradients on two side streams (64x64 geometry, native step)."""
-        return bool(self.three_streams and chain and self.is64 and not self.single_stream and not self.eager_wgrad)
+        return self.policy.three(chain) and self.is64
 
     def _decode_convs_batch(self, layers, B):
         """Batch-sized schedule, decoder conv layers.  The dgrads of the two big layers (convT3, convT2) fill the chip by
@@ -830,12 +779,8 @@ class VAEEngine:
         encoder's FC chain) and leaves most CUs idle -- so the big weight gradients are forked THERE (behind the last big
         dgrad), and the rest after the FC dgrads (-> the small layers' weight gradients: the caller launches them behind
         that fork).  Every fork costs this stream ~6 us."""
-        # where convT3's weight gradient is forked (early_thin_wgrad): behind its input gradient -- or, at the 128 images of one
-        # rank of the 8-GPU headline configuration, in FRONT of it (beside it): 0.332 -> 0.325 ms there, level at 32 / 64, +1.3 %
-        # at 96, +1.6 % at 256 images (profiles/r06_s2_sched3.txt, r06_s2_sched4.txt).  Not under data parallelism: the fork carries the
-        # late epilogue with its collectives, whose host-side issue would then stand in front of convT3's input gradient
-        early = 2 if (self.early_thin_auto and 112 <= B <= 128 and not self.sharded) else self.early_thin_wgrad
-        early = 0 if self.single_stream else early
+        # where convT3's weight gradient is forked: 1 = behind its input gradient, 2 = in FRONT of it (schedule.EARLY_THIN_2_ROWS)
+        early = self.policy.early_thin(B)
         queued, pending, small = [], [], []
         for h, wgrad, dgrad in layers:
             if h < 16:
@@ -892,7 +837,8 @@ class VAEEngine:
     def decode_backward(self, z, buf, n=None, join=True, defer_fc_wgrad=False, fc_chain=None):
         """buf.g_logit (grad w.r.t. the pre-sigmoid output) -> decoder weight grads, buf.dz.
         defer_fc_wgrad: the three FC weight gradients are not launched here but handed to the next
-        encode_backward, which computes all six FC weight gradients of the step in one grouped launch.
+        encode_backward, which computes all six FC weight gradients of the step in one grouped launch: returned (else []),
+        to be passed on as its `dec_fc`.
         fc_chain: callable that enqueues fc_chain_bwd (the native training step): it replaces the three FC input-gradient
         launches here AND the latent glue + the encoder's three of the following encode_backward(fc_chain=True)."""
         B = z.shape[0] if n is None else n
@@ -900,10 +846,9 @@ class VAEEngine:
         fc = self._dec_fc_wgrads(z, buf, B)
         if self._three(fc_chain is not None) and defer_fc_wgrad and not join:
             self._decode_backward_3q(layers, fc_chain)
-            self._fc_pending = fc
-            return
+            return fc
         small = []
-        if self.eager_wgrad and not self.single_stream:
+        if self.policy.eager_wgrad and not self.policy.single_stream:
             self._decode_convs_eager(layers)
         else:
             small = self._decode_convs_batch(layers, B)
@@ -916,12 +861,11 @@ class VAEEngine:
             self.fork_side()
         for wgrad in small:
             self._wgrad(SIDE, wgrad)
-        if defer_fc_wgrad:
-            self._fc_pending = fc
-        else:
+        if not defer_fc_wgrad:
             self._fc_wgrads(SIDE, fc)
         if join:
             self._join_side()
+        return fc if defer_fc_wgrad else []
 
     def _encode_backward_batch(self, layers, fc, B):
         """Batch-sized schedule, encoder half.  Forks: one before the first big layer (h_in >= 32; the grouped FC weight
@@ -930,13 +874,12 @@ class VAEEngine:
         weight gradient itself while the side stream drains its queue -- and after it those of tail_main."""
         # the grouped FC weight gradients: side stream (in front of conv2's weight gradient) -- or, fcw_main, the LAST launch of the
         # main stream's tail (a step of a few hundred images ends on the side stream: profiles/r06_final4_dsprites_timeline.md)
-        fcw_main = (self.fcw_main and self.is64 and not self.single_stream
-                    and self.fcw_main_rows[0] <= B <= self.fcw_main_rows[1])
+        fcw_main = self.is64 and self.policy.fcw_main_at(B)
         fc_side = not fcw_main                  # the grouped launch still waits for a fork of the side stream
         waiting, tail = [], []                  # weight gradients waiting for that fork / for the main stream's tail
         for name, h_in, wgrad, dgrad in layers[:-1]:
             side = ()
-            if name in self.tail_main and self.is64 and not self.single_stream:
+            if name in self.policy.tail_main and self.is64 and not self.policy.single_stream:
                 tail.append(wgrad)
             elif h_in >= 32:
                 self.fork_side()
@@ -998,20 +941,24 @@ class VAEEngine:
         self._join_side()
         self._join_side(wg2=True)
 
-    def encode_backward(self, x, buf, n=None, fc_chain=False):
+    def encode_backward(self, x, buf, n=None, fc_chain=False, dec_fc=()):
         """buf.dml (grad w.r.t. the interleaved mu/logvar output) -> encoder weight grads.  fc_chain: the three FC input
-        gradients were already computed by fc_chain_bwd (buf.gh2, gh1, ga_flat are final)."""
+        gradients were already computed by fc_chain_bwd (buf.gh2, gh1, ga_flat are final).  dec_fc: what the decode_backward
+        of this pass deferred."""
         B = x.shape[0] if n is None else n
         if not fc_chain:
             self._enc_fc_dgrads(buf, B)
         # weight gradients wait for the next fork (they only have to be done by the end of the backward pass): the
         # encoder's three FC layers + the decoder's three when decode_backward deferred them = one grouped launch
-        pend, self._fc_pending = [p_ for p_ in self._fc_pending if p_[4] == B], []
-        fc = self._enc_fc_wgrads(buf, B, pend)
+        dec_fc = list(dec_fc)
+        if any(p_[4] != B for p_ in dec_fc):
+            raise _lib.DvaeHipError("encode_backward over %d rows was handed the decoder's FC weight gradients of a pass over %d"
+                                    % (B, dec_fc[0][4]))
+        fc = self._enc_fc_wgrads(buf, B, dec_fc)
         layers = self._enc_layers(x, buf, B, bool(fc_chain) and self._ends(B))
-        if self._three(bool(fc_chain)) and len(pend) == 3:
+        if self._three(bool(fc_chain)) and len(dec_fc) == 3:
             self._encode_backward_3q(layers, fc)
-        elif self.eager_wgrad and not self.single_stream:
+        elif self.policy.eager_wgrad and not self.policy.single_stream:
             self._encode_backward_eager(layers, fc)
         else:
             self._encode_backward_batch(layers, fc, B)

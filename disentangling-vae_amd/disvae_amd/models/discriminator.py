@@ -144,7 +144,7 @@ class Discriminator(nn.Module):
         s = _stream() if stream is None else stream
         b = self._act_buffers(M) if acts is None else acts
         R = M if rows is None else rows
-        on_side = wgrad and side is not None and not side.single_stream
+        on_side = wgrad and side is not None and not side.policy.single_stream
         wsp = ptr(self._ws(ws))
         dy = g_logits
         dys = []

@@ -24,6 +24,7 @@ from .discriminator import Discriminator
 from ..graph import StepGraphs
 from ..parallel import scale_, copy_flat_
 from .._debug import knob
+from ..schedule import build_policy, replay_mode, switches
 
 LOSSES = ["VAE", "betaH", "betaB", "factor", "btcvae"]  # losses.py:17
 RECON_DIST = ["bernoulli", "laplace", "gaussian"]        # losses.py:18
@@ -136,17 +137,15 @@ class BaseLoss(abc.ABC):
         # single-process step on the concatenated batch); "local" = every rank's shard is its own minibatch
         # (what running the reference under DistributedDataParallel would compute: a different estimator)
         self.estimator = "global"
-        # how the device side of the native training iteration is issued (graph.py): None = eager
-        # Python; "plan" = recorded launch list (the same launches on the same streams, bit-identical
-        # results); "graph" = hipGraph; "auto" (default) = plan while the iteration is launch-bound
-        # (batch tensor <= AUTO_PLAN_ELEMS elements: measured cross-over), eager
-        # above.  Sharded steps replay too: collectives are recorded plan entries (parallel.py)
+        # how the device side of the native training iteration is issued: None (eager) / "plan" / "graph" / "auto"
+        # (schedule.replay_mode resolves it per step; read at construction: tests and bench.py assign it afterwards)
         mode = knob("DVAE_REPLAY", "auto")
         if mode not in ("plan", "graph", "eager", "auto"):
             raise ValueError("DVAE_REPLAY={!r}: expected one of auto, eager, plan, graph".format(mode))
         self.replay = {"plan": "plan", "graph": "graph", "eager": None, "auto": "auto"}[mode]
         self._graphs = StepGraphs()
         self._static = {}
+        self.policy_override = {}   # StepPolicy fields forced to a value (tests: an A/B partner without the environment)
         # dvae_event_record / dvae_event_wait slot of this loss object: "the estimator and the scalar loss of this step are final"
         self._ev_slot = _lib.next_event_slot()
 
@@ -161,66 +160,24 @@ class BaseLoss(abc.ABC):
             t.copy_(like, non_blocking=True)
         return t
 
-    # (round 6: up to 1024 images -- the same step time at 512 / 1024 images single process, 0.23-0.27 instead of 0.36 ms of host
-    # time per step; one rank of two of configs[3] (512 images through the sharded path) spends 0.55 ms of host per 0.63 ms step
-    # when it is issued eagerly: profiles/r06_s2_shard_world.txt)
-    AUTO_PLAN_ELEMS = 1024 * 3 * 64 * 64
-    # one HIP stream instead of two below this many input elements per step (engine.single_stream); DVAE_STREAMS=1|2 forces
-    # (round 2 measured the cross-over at 64 images, profiles/r02_run10_streams.txt; with the round-5 schedule two streams win at
-    # 32 and 64 images as well: 0.291 / 0.301 against 0.338 / 0.346 ms, profiles/r05_v26_sweep.txt; round 6: at 4 / 8 / 16 images
-    # too -- 0.306 -> 0.267, 0.312 -> 0.271, 0.315 -> 0.277 ms -- and at the 32x32 geometry level at 16 / 64 images, -3 % at 128:
-    # profiles/r06_s2_streams_small.txt.  Two streams at every size.)
-    SINGLE_STREAM_ELEMS = int(knob("DVAE_SINGLE_STREAM_ELEMS", 0))
-
-    # dependency-driven weight-gradient schedule (engine.eager_wgrad: a fork per layer) up to this many input elements per
-    # step; above, the batch-sized schedule (two forks per half of the backward pass).  Round 3 measured the two within noise
-    # of each other up to 384 images; with the round-5 kernels the batch-sized schedule wins at every batch measured (128
-    # images: 0.349 vs 0.359 ms, btcvae_dsprites 0.421 vs 0.433 ms: profiles/r05_v25_schedule_ab.txt) -- each fork costs the
-    # critical path an event and the small weight gradients it frees early are not what the iteration waits for
-    EAGER_WGRAD_ELEMS = int(knob("DVAE_EAGER_WGRAD_ELEMS", 0))
-    # weight gradients on TWO side streams (engine.three_streams) from this many batch rows per step (single process).  Measured
-    # (profiles/r06_s2_three1.txt, same box, three alternations): SLOWER for every beta-TCVAE step -- 64 / 128 / 256 / 512 / 1024
-    # images 0.288 -> 0.300, 0.328 -> 0.347, 0.435 -> 0.441, 0.634 -> 0.648, 1.050 -> 1.060 ms: whatever runs beside the main
-    # stream's chain of small kernels slows that chain by more than the side streams gain -- and faster only where the side
-    # stream also carries the discriminator's chain: factor 64x64x3 tensor 2048 1.853 -> 1.832 ms (FactorKLoss below)
-    THREE_STREAM_MIN_ROWS = 1 << 30
-    # sharded batches up to this many input elements per rank: ONE all-reduce of the whole gradient arena at the end instead of
-    # two overlapped spans (the step is a latency chain; every collective costs the host and both streams more than the
-    # overlap of 1 MB buys).  Round 6: at EVERY size -- as one rank of two (512 images) the two-span path takes 1.06-1.16 ms
-    # against 0.63 with one all-reduce (single process: 0.63), FactorVAE tensor 1024 / 512 per rank 1.31 / 0.93 against 1.18 / 0.83
-    # (profiles/r06_s2_shard_world.txt: mirrored world, C-ABI transport); the 2 MB arena is ~20 us of xGMI time, there is
-    # nothing worth overlapping.  (The spans stay reachable for A/B: DVAE_DEBUG=1 DVAE_SMALL_SHARD_ELEMS=<elements>.)
-    SMALL_SHARD_ELEMS = int(knob("DVAE_SMALL_SHARD_ELEMS", 1 << 40))
-
-    def _streams(self, model, data):
-        mode = knob("DVAE_STREAMS", "auto")
-        single = mode == "1" or (mode == "auto" and data.numel() <= self.SINGLE_STREAM_ELEMS)
-        model.engine.single_stream = bool(single) and self._world()[0] == 1
-        model.engine.eager_wgrad = data.numel() <= int(knob("DVAE_EAGER_WGRAD_ELEMS", self.EAGER_WGRAD_ELEMS))
-        model.engine.sharded = self._world()[0] > 1
-        model.engine.three_streams = (not single and self._world()[0] == 1
-                                      and data.shape[0] >= int(knob("DVAE_THREE_STREAM_MIN_ROWS", self.THREE_STREAM_MIN_ROWS)))
-        tm = knob("DVAE_TAIL_MAIN", "default")      # A/B (DVAE_DEBUG=1): which encoder weight gradients end the main stream
-        if tm != "default":
-            model.engine.tail_main = tuple(v for v in tm.split(",") if v)
-        return model.engine.single_stream
+    def _begin_step(self, model, data):
+        """This step's schedule.StepPolicy (built once per distinct step shape), handed to the engine."""
+        pol = build_policy(model.img_size, model.latent_dim, data.shape[0], switches(), self._world()[0], self.KIND,
+                           model.training, self.replay)
+        if self.policy_override:
+            pol = pol._replace(**self.policy_override)
+        model.engine.begin_step(pol)
+        return pol
 
     def _replay_mode(self, is_train, data):
-        # (sharded batches replay too: the collectives and the torch ops around them are recorded plan entries -- C-ABI calls
-        # with the RCCL transport, host callables re-entering their stream with torch.distributed: disvae_amd/parallel.py)
-        if not is_train:
-            return None
-        if self.replay == "auto":
-            return "plan" if data.numel() <= self.AUTO_PLAN_ELEMS else None
-        return self.replay
+        return replay_mode(self.replay, is_train, data.numel())
 
-    def _replay_key(self, model, data, injected):
-        """Everything a recorded launch freezes: buffers (allocation generation), arenas, the
-        batch pointer, the stream, and the few Python-side switches passed as scalars."""
+    def _replay_key(self, model, data, injected, pol):
+        """Everything a recorded launch freezes: buffers (allocation generation), arenas, the batch pointer, the stream, the
+        step's policy (every scheduling decision) and the few Python-side switches passed as scalars."""
         return (id(model), data.shape, data.data_ptr(), injected, _stream(), model.arena.flat.data_ptr(),
-                model.arena.grad.data_ptr(), _lib.ALLOC_GEN[0], self.rec_dist, getattr(self, "is_mss", None),
-                model.engine.single_stream, model.engine.eager_wgrad, model.engine.tail_main, id(self.comm), self.estimator,
-                model.engine.three_streams, model.engine.sharded)
+                model.arena.grad.data_ptr(), _lib.ALLOC_GEN[0], self.rec_dist, getattr(self, "is_mss", None), pol,
+                id(self.comm), self.estimator)
 
     @abc.abstractmethod
     def __call__(self, data, recon_data, latent_dist, is_train, storer, **kwargs):
@@ -280,17 +237,17 @@ class BaseLoss(abc.ABC):
             storer['kl_loss_' + str(i)].append(vals[_lib.kl0(D) + i])
 
     # ---- the parts of a native step (the skeleton: DESIGN.md, "The step skeleton") ---------------------------------------
-    def _run_step(self, model, data, inputs, injected, key_extra, fn):
+    def _run_step(self, model, data, pol, inputs, injected, key_extra, fn):
         """Replay dispatch: fn(data, *inputs) now, or recorded / replayed (graph.py).  A replay re-issues launches with frozen
         pointers: the injected `inputs` [(name, tensor or None)] go through static buffers; the batch pointer is part of the plan
         key (a hipGraph needs it static as well)."""
-        mode = self._replay_mode(model.training, data)
+        mode = pol.replay
         if not mode:
             return fn(data, *[t for _, t in inputs])
         if mode == "graph":
             data = self._static_buf("data", data)
         inputs = [t if t is None else self._static_buf(name, t) for name, t in inputs]
-        self._graphs.run(self._replay_key(model, data, injected) + key_extra, lambda: fn(data, *inputs), mode)
+        self._graphs.run(self._replay_key(model, data, injected, pol) + key_extra, lambda: fn(data, *inputs), mode)
 
     def _finish_loss(self, sc, klb, D, rowstats, rows, disc_sums, Bg, stream, on=None, xbuf=None):
         """The scalar epilogue on `stream`: partial sums -> sc.scal.  Single process: ONE launch.  Sharded: pack, sum-all-reduce
@@ -319,7 +276,7 @@ class BaseLoss(abc.ABC):
         after the fork point through the side stream (whose only queued work at that moment is the wait for that fork: no second
         event on this stream) -- and an event slot marks the lot.  Returns what fc_chain() calls first: the wait for the slot."""
         s = _stream()
-        sharded = self._world()[0] > 1
+        sharded = eng.policy.sharded
 
         def deferred():
             ss = eng._side_raw()
@@ -340,19 +297,18 @@ class BaseLoss(abc.ABC):
         launch for all six FC weight gradients (issued by encode_backward).  Sharded, two spans: the decoder's three are launched
         with the decoder's conv weight gradients -- every kernel that writes a decoder gradient goes to the side stream, so the
         all-reduce of the decoder span is ordered behind the SIDE stream and overlaps the encoder backward; this stream never
-        waits for it before the end.  Small shards (SMALL_SHARD_ELEMS): ONE all-reduce of the whole arena after the final join.
+        waits for it before the end.  Without spans (schedule.SMALL_SHARD_ELEMS): ONE all-reduce of the whole arena after the join.
         pending: handles of collectives already under way (FactorVAE: the discriminator's gradients), waited for last."""
-        world = self._world()[0]
-        spans = world > 1 and data.numel() > self.SMALL_SHARD_ELEMS
+        spans = eng.policy.grad_spans
         pending = list(pending)
-        eng.decode_backward(buf.z, buf, n=n, join=False, defer_fc_wgrad=not spans, fc_chain=fc_chain)
+        dec_fc = eng.decode_backward(buf.z, buf, n=n, join=False, defer_fc_wgrad=not spans, fc_chain=fc_chain)
         if spans:
             with torch.cuda.stream(eng.side_stream):
                 pending.append(self.comm.all_reduce_async(model.arena.span("decoder.")))
-        eng.encode_backward(data, buf, n=n, fc_chain=True)
+        eng.encode_backward(data, buf, n=n, fc_chain=True, dec_fc=dec_fc)
         if spans:
             pending.append(self.comm.all_reduce_async(model.arena.span("encoder.")))
-        elif world > 1:
+        elif eng.policy.sharded:
             self.comm.all_reduce(model.arena.grad)
         for h_ in pending:
             h_.wait()
@@ -515,10 +471,10 @@ class _SingleOptimizerLoss(BaseLoss):
         sc.set_coef_host(INV_B=1.0 / (B * self._world()[0]), **self._coefs(is_train))
         model.engine.stage(sc.coef, sc.coef_host)
         data = data.contiguous()
-        self._streams(model, data)
+        pol = self._begin_step(model, data)
         if self.KIND == _lib.LOSS_BTCVAE:
             sc.set_log_w(B * self._est_world()[0], self.n_data)
-        self._run_step(model, data, [("eps", eps)], eps is not None, (),
+        self._run_step(model, data, pol, [("eps", eps)], eps is not None, (),
                        lambda data, eps: self._device_step(data, model, sc, eps, is_train))
         if is_train:
             model.assign_grads()          # optimizer.zero_grad(); loss.backward()  (training.py:156-157)
@@ -529,7 +485,6 @@ class _SingleOptimizerLoss(BaseLoss):
     def _device_step(self, data, model, sc, eps, is_train):
         """Forward + loss + backward as one stream of launches; no host-dependent values."""
         eng = model.engine
-        eng._fork_hook = None                  # a hook left behind by a step that raised is dropped, not run (nor recorded)
         B, D = data.shape[0], model.latent_dim
         world = self._world()[0]
         Bg = B * world
@@ -541,10 +496,10 @@ class _SingleOptimizerLoss(BaseLoss):
             record_py(eps.normal_)             # = torch.randn_like (vae.py:67): same Philox consumption
         if not is_train:
             eps = None
-        eng.encode_convs(data, buf, chain=True)
+        ends = eng.encode_convs(data, buf, chain=True)
         # the FC core in one launch: lin1 -> lin2 -> mu_logvar -> reparameterise (+ KL partial blocks) -> lin1 -> lin2 -> lin3
         # (latent dimensions above 16: one launch per layer, kl_dim final at once and klb = 0 -- engine.fc_chain_fwd)
-        eng.fc_chain_fwd(buf, eps, sc.kl_dim, B, coef=sc.coef)
+        eng.fc_chain_fwd(buf, eps, sc.kl_dim, B, coef=sc.coef, ends=ends)
         klb = eng.kl_blocks(B)            # single process: the one-launch loss epilogue finishes the KL partials
         btc = self.KIND == _lib.LOSS_BTCVAE
         rowstats = dz = dmu = dlv = xbuf = None
@@ -557,16 +512,15 @@ class _SingleOptimizerLoss(BaseLoss):
             # the iteration, nothing may queue in front of its weight gradients)
             call("dvae_stream_order", s, eng._aux_raw())
         # decoder convT stack; its last layer also evaluates the reconstruction likelihood and dL/dlogit
-        eng.decode_convs(buf, B, fuse_loss=(data, self._rec_code(), sc.coef, sc.partials), chain=True)
+        eng.decode_convs(buf, B, fuse_loss=(data, self._rec_code(), sc.coef, sc.partials), ends=ends)
         if btc and world > 1:
             # sharded: this stream's launches are issued FIRST -- the exchanges make the side stream's part long to issue, and
             # at a hundred images per GPU the host is what the critical path would wait for
             rowstats, dz, dmu, dlv, xbuf = self._estimator(eng, buf, sc, B, D, is_train)
         # the scalar epilogue: deferred behind the estimator's backward kernels, which run past the end of the decoder forward
-        # (_defer_loss), for beta-TCVAE and for every sharded step (the all-reduce of the packed loss sums sits between its halves)
-        late_join = (is_train and not eng.single_stream and (btc or world > 1) and knob("DVAE_LATE_JOIN", "1") != "0")
+        # (_defer_loss), for beta-TCVAE and for every sharded step (StepPolicy.late_join)
         wait = None
-        if late_join:
+        if eng.policy.late_join:
             wait = self._defer_loss(eng, lambda stream, on: self._finish_loss(sc, klb, D, rowstats, B, None, Bg, stream, on, xbuf))
         else:
             if btc and world > 1:
@@ -711,9 +665,6 @@ class FactorKLoss(BaseLoss):
     kernels, including quirk Q1 (the encoder also receives d[0.5 CE(D(z1),0)]/dz1 because the
     reference does not detach d_z and steps the VAE optimizer after d_tc_loss.backward())."""
 
-    # the side stream carries the discriminator's chain as well: from 2048 rows per step the VAE's weight gradients go to two
-    # side streams (BaseLoss.THREE_STREAM_MIN_ROWS: tensor 2048 1.853 -> 1.832 ms, tensor 256 0.561 -> 0.592)
-    THREE_STREAM_MIN_ROWS = 2048
     KIND = _lib.LOSS_FACTOR
     STORED = (('recon_loss', _lib.S_REC), ('kl_loss', _lib.S_KL), ('loss', _lib.S_LOSS), ('tc_loss', _lib.S_TC),
               ('discrim_loss', _lib.S_DTC))
@@ -754,7 +705,6 @@ class FactorKLoss(BaseLoss):
         """Training iteration of FactorVAE as one stream of launches (no host-dependent values):
         VAE forward on both halves, discriminator on (z1, z_perm), both backward passes."""
         eng = model.engine
-        eng._fork_hook = None                  # a hook left behind by a step that raised is dropped, not run (nor recorded)
         disc = self.discriminator
         D = model.latent_dim
         Bh = data.size(0) // 2
@@ -771,12 +721,12 @@ class FactorKLoss(BaseLoss):
             record_py(eps12[Bh:].copy_, eps2)
         buf = eng.buffers(data.size(0))
         data = eng.input(data, buf)
-        eng.encode_convs(data, buf, n=2 * Bh, chain=True)                         # data1 and data2 in one pass
+        ends = eng.encode_convs(data, buf, n=2 * Bh, chain=True)                  # data1 and data2 in one pass
         # FC core of both halves in one launch; KL only over data1 with the half batch as denominator (losses.py:255-259),
         # decoder only for data1
-        eng.fc_chain_fwd(buf, eps12, sc.kl_dim, 2 * Bh, n_kl=Bh, n_dec=Bh, coef=sc.coef)
+        eng.fc_chain_fwd(buf, eps12, sc.kl_dim, 2 * Bh, n_kl=Bh, n_dec=Bh, coef=sc.coef, ends=ends)
         klb = eng.kl_blocks(2 * Bh)
-        eng.decode_convs(buf, Bh, fuse_loss=(data, self._rec_code(), sc.coef, sc.partials), chain=True)
+        eng.decode_convs(buf, Bh, fuse_loss=(data, self._rec_code(), sc.coef, sc.partials), ends=ends)
         # z_perm: permute across the (global) half batch, losses.py:287
         zin = sc.latent("disc_in", 2 * Bh, D)
         copy_flat_(zin[:Bh], buf.z[:Bh])
@@ -797,20 +747,20 @@ class FactorKLoss(BaseLoss):
         # the scalar epilogue (13 us; sharded: KL finish + pack + all-reduce of the packed sums + finalize) is first needed by
         # the FC chain's input gradients, after the discriminator's and the decoder's backward passes: deferred (_defer_loss)
         wait = None
-        if not eng.single_stream and knob("DVAE_LATE_JOIN", "1") != "0":
+        if eng.policy.late_join:
             wait = self._defer_loss(eng, lambda stream, on: self._finish_loss(sc, klb, D, None, 0, sc.disc_sums, Bh * world,
                                                                               stream, on))
         else:
             self._finish_loss(sc, klb, D, None, 0, sc.disc_sums, Bh * world, s)
         # discriminator backward of d_tc_loss (weight grads + dz), losses.py:303-304
         # (its six weight gradients: on the side stream, behind one fork after the input-gradient chain)
-        side_wg = not eng.single_stream and knob("DVAE_DISC_WGRAD_SIDE", "1") != "0"
+        side_wg = eng.policy.disc_wgrad_side
         # the second chain of input gradients (the tc term of vae_loss through D: first half, no weight gradients) depends on
         # nothing the first one computes and could run beside it on the engine's third stream.  Measured, NOT shipped (A/B under
         # DVAE_DEBUG=1, same box: factor_dsprites 0.583 vs 0.579-0.585 ms, factor_celeba 1.905 vs 1.885-1.892, tensor 512
         # 0.831 vs 0.788-0.819: profiles/r05_v35_disc_chain2_ab.txt): the fork and the join cost the critical path what the
         # overlap of two launch-bound chains buys, and at 2048 rows both chains fill the chip anyway.
-        par2 = (not eng.single_stream and world == 1 and knob("DVAE_DISC_CHAIN2_AUX", "0") == "1")
+        par2 = eng.policy.disc_chain2_aux
         dz_b = None
         if par2:
             call("dvae_stream_order", s, eng._aux_raw())
@@ -841,12 +791,12 @@ class FactorKLoss(BaseLoss):
         s = _stream()
         buf = eng.buffers(data.size(0))
         data = eng.input(data, buf)
-        eng.encode_convs(data, buf, n=Bh, chain=True)
+        ends = eng.encode_convs(data, buf, n=Bh, chain=True)
         # KL over data1 with the half batch as denominator (losses.py:255-259)
-        eng.fc_chain_fwd(buf, None, sc.kl_dim, Bh, coef=sc.coef)
+        eng.fc_chain_fwd(buf, None, sc.kl_dim, Bh, coef=sc.coef, ends=ends)
         if eng.kl_blocks(Bh):
             call("dvae_kl_finish", ptr(sc.kl_dim), eng.kl_blocks(Bh), ptr(sc.coef), D, s)
-        eng.decode_convs(buf, Bh, fuse_loss=(data, self._rec_code(), sc.coef, sc.partials), chain=True)
+        eng.decode_convs(buf, Bh, fuse_loss=(data, self._rec_code(), sc.coef, sc.partials), ends=ends)
         logits = disc.forward_raw(buf.z, Bh)
         g_dtc = sc.latent("g_dtc", 2 * Bh, 2)
         lg2 = sc.latent("lg2", 2 * Bh, 2)
@@ -870,7 +820,7 @@ class FactorKLoss(BaseLoss):
         sc.set_coef_host(INV_B=1.0 / (Bh * self._world()[0]), ANNEAL=anneal, BETA=self.gamma)
         model.engine.stage(sc.coef, sc.coef_host)       # ONE launch: this step's weight images + its loss coefficients
         data = data.contiguous()
-        self._streams(model, data)
+        pol = self._begin_step(model, data)
         if not is_train:
             self._eval_step(data, model, sc)
             self._store(storer, sc, D, self.STORED[:-1])
@@ -886,7 +836,7 @@ class FactorKLoss(BaseLoss):
         if slot is not None:
             slot[1] = torch.cuda.Event()
             slot[1].record()                          # the staging buffer is free again once this has passed
-        self._run_step(model, data, [("eps1", eps1), ("eps2", eps2)], noise is not None, (self.discriminator.arena.flat.data_ptr(),),
+        self._run_step(model, data, pol, [("eps1", eps1), ("eps2", eps2)], noise is not None, (self.discriminator.arena.flat.data_ptr(),),
                        lambda data, eps1, eps2: self._device_step(data, model, sc, eps1, eps2, perms))
         model.assign_grads()
         self.discriminator.assign_grads()

@@ -16,6 +16,7 @@ from .. import _lib
 from .._lib import call, ptr
 from ..utils.initialization import reference_init_
 from .._debug import knob
+from ..schedule import build_policy, switches
 
 MODELS = ["Burgess"]  # disvae/models/vae.py:12
 
@@ -241,6 +242,14 @@ def _check_input(model, x):
     return x.contiguous()
 
 
+def _begin_backward(model, rows):
+    """The engine of `model` with the default policy of a single-process pass over `rows` rows: the autograd-compatible entry
+    points schedule their backward passes by it, whatever the last native step left."""
+    eng = model.engine
+    eng.begin_step(build_policy(model.img_size, model.latent_dim, rows, switches()))
+    return eng
+
+
 def _zeros_scal(dev):
     return torch.zeros(_lib.NSCAL, dtype=torch.float32, device=dev)    # (dvae_reparam_kl_bwd reads the fixed slots only)
 
@@ -278,15 +287,16 @@ class _VAEFn(torch.autograd.Function):
         if model._fwd_version != ctx.version:
             raise _lib.DvaeHipError("backward through a stale forward: the engine workspace was overwritten by a "
                                     "later forward of the same model")
-        eng = model.engine
-        model.unalias_grads()
         B = x.shape[0]
+        eng = _begin_backward(model, B)
+        model.unalias_grads()
         buf = eng.buffers(B)
         s = _stream()
         dz = g_z.contiguous() if g_z is not None else None
+        dec_fc = []
         if ctx.decode and g_recon is not None:
             call("dvae_sigmoid_bwd", ptr(g_recon.contiguous()), ptr(buf.recon), ptr(buf.g_logit), buf.recon.numel(), s)
-            eng.decode_backward(buf.z, buf, defer_fc_wgrad=True)     # encode_backward below launches all six FC wgrads
+            dec_fc = eng.decode_backward(buf.z, buf, defer_fc_wgrad=True)     # encode_backward below launches all six FC wgrads
             if dz is not None:
                 call("dvae_add", ptr(buf.dz), ptr(dz), ptr(buf.dz), buf.dz.numel(), s)
             dz = buf.dz
@@ -306,7 +316,7 @@ class _VAEFn(torch.autograd.Function):
         gl = g_lv.contiguous() if g_lv is not None else None
         call("dvae_reparam_kl_bwd", ptr(dz), None, None, ptr(gm), ptr(gl), ptr(buf.mu), ptr(buf.logvar), ptr(ctx.eps), ptr(scal),
              ptr(coef), ptr(buf.dml), B, model.latent_dim, s)
-        eng.encode_backward(x, buf)
+        eng.encode_backward(x, buf, dec_fc=dec_fc)
         return (None, None, None, None) + tuple(_param_grads(model))
 
 
@@ -329,7 +339,7 @@ class _EncodeFn(torch.autograd.Function):
         model, x = ctx.model, ctx.x
         if model._fwd_version != ctx.version:
             raise _lib.DvaeHipError("backward through a stale forward")
-        eng = model.engine
+        eng = _begin_backward(model, x.shape[0])
         model.unalias_grads()
         buf = eng.buffers(x.shape[0])
         s = _stream()
@@ -366,7 +376,7 @@ class _DecodeFn(torch.autograd.Function):
         model, z = ctx.model, ctx.z
         if model._fwd_version != ctx.version:
             raise _lib.DvaeHipError("backward through a stale forward")
-        eng = model.engine
+        eng = _begin_backward(model, z.shape[0])
         model.unalias_grads()
         buf = eng.buffers(z.shape[0])
         s = _stream()

@@ -30,24 +30,30 @@ for _p in (ROOT, os.path.join(ROOT, "disentangling-vae_amd")):
 
 import torch  # noqa: E402
 
-from disvae_amd import _lib, engine as E  # noqa: E402
+from disvae_amd import _lib, engine as E, schedule as SCHED  # noqa: E402
 from disvae_amd.models.vae import init_specific_model  # noqa: E402
 
 # ---- the cases: the cross product of AXES, in this order ---------------------------------------------------------------
 AXES = {
     "geometry": [(3, 64, 64), (1, 64, 64), (1, 32, 32)],
     "latent_dim": [10, 17],                  # 17: per-layer FC launches, fuse_ends off
-    # both sides of every threshold in the code: early_thin mode 2 at 112-128, fcw_main_rows 129-320, fuse_ends_max_rows 256,
-    # FactorVAE's three-queue schedule from 2048
+    # both sides of every row threshold of disvae_amd/schedule.py: EARLY_THIN_2_ROWS 112-128, FCW_MAIN_ROWS 129-320,
+    # FUSE_ENDS_MAX_ROWS 256, THREE_STREAM_MIN_ROWS_FACTOR 2048
     "rows": [16, 112, 128, 129, 256, 257, 320, 321, 1024, 2048],
     "policy": ["default", "eager_wgrad", "single_stream", "three_streams", "sharded", "tail_main_none"],
     "dtype": ["float32", "uint8"],
     "calls": ["step", "step_nohook", "step_nodefer", "autograd", "autograd_hook", "decode", "encode"],
 }
-# the engine attributes BaseLoss._streams sets per step, per policy (everything else at its default)
-POLICY = {"default": {}, "eager_wgrad": {"eager_wgrad": True}, "single_stream": {"single_stream": True},
-          "three_streams": {"three_streams": True}, "sharded": {"sharded": True}, "tail_main_none": {"tail_main": ()}}
-_DEFAULTS = {"eager_wgrad": False, "single_stream": False, "three_streams": False, "sharded": False, "tail_main": E._TAIL_MAIN}
+# what schedule.build_policy is given, per policy: (debug switches off their shipped value, world size)
+POLICY = {"default": ({}, 1), "eager_wgrad": ({"DVAE_EAGER_WGRAD_ELEMS": str(1 << 40)}, 1),
+          "single_stream": ({"DVAE_STREAMS": "1"}, 1), "three_streams": ({"DVAE_THREE_STREAM_MIN_ROWS": "0"}, 1),
+          "sharded": ({}, 2), "tail_main_none": ({"DVAE_TAIL_MAIN": ""}, 1)}
+
+
+def policy(img, D, B, name):
+    """The StepPolicy of case (img, D, B, policy name)."""
+    over, world = POLICY[name]
+    return SCHED.build_policy(tuple(img), D, B, tuple(over.get(k, v) for k, v in SCHED.SWITCHES), world)
 
 
 def cases():
@@ -142,9 +148,7 @@ class Tracer:
 
     def trace(self, B, policy, dtype, calls):
         eng, buf, out = self.eng, self.buf, self.out
-        for k, v in dict(_DEFAULTS, **POLICY[policy]).items():
-            setattr(eng, k, v)
-        eng._fork_hook, eng._fc_pending = None, []
+        eng.begin_step(globals()["policy"](self.img, self.D, B, policy))
         buf.B = B
         x = self.x[dtype].expand((B,) + self.img)
         z = buf.z.expand(B, self.D)
@@ -157,11 +161,10 @@ class Tracer:
             if calls in ("step", "step_nodefer", "autograd_hook"):
                 eng.at_next_fork(lambda: out.append(("hook",)))
             if calls in ("step", "step_nohook", "step_nodefer"):       # the native step of the loss plugins
-                eng.decode_backward(z, buf, n=B, join=False, defer_fc_wgrad=calls != "step_nodefer", fc_chain=fc_chain)
-                eng.encode_backward(x, buf, n=B, fc_chain=True)
+                dec_fc = eng.decode_backward(z, buf, n=B, join=False, defer_fc_wgrad=calls != "step_nodefer", fc_chain=fc_chain)
+                eng.encode_backward(x, buf, n=B, fc_chain=True, dec_fc=dec_fc)
             elif calls in ("autograd", "autograd_hook"):                # models/vae.py: _VAEFn.backward
-                eng.decode_backward(z, buf, defer_fc_wgrad=True)
-                eng.encode_backward(x, buf)
+                eng.encode_backward(x, buf, dec_fc=eng.decode_backward(z, buf, defer_fc_wgrad=True))
             elif calls == "decode":                                     # _DecodeFn.backward
                 eng.decode_backward(z, buf)
             else:                                                       # _EncodeFn.backward

@@ -34,21 +34,21 @@ import schedule_trace as T  # noqa: E402  (also puts the package on sys.path)
 
 import torch  # noqa: E402
 
-from disvae_amd import _lib, engine as E, optim  # noqa: E402
+from disvae_amd import _lib, engine as E, optim, schedule as SCHED  # noqa: E402
 from disvae_amd.models import discriminator as DISC, losses as L, vae as V  # noqa: E402
 
 # ---- the cases ---------------------------------------------------------------------------------------------------------
-# one switch at a time against the default: (knob values, attributes set on the loss object)
+# one switch at a time against the default: the knob values schedule.build_policy is given
 SWITCHES = {
-    "default": ({}, {}),
-    "DVAE_STREAMS=1": ({"DVAE_STREAMS": "1"}, {}),
-    "DVAE_LATE_JOIN=0": ({"DVAE_LATE_JOIN": "0"}, {}),
-    "SMALL_SHARD_ELEMS=0": ({}, {"SMALL_SHARD_ELEMS": 0}),             # the two-span gradient exchange
-    "DVAE_DISC_WGRAD_SIDE=0": ({"DVAE_DISC_WGRAD_SIDE": "0"}, {}),
-    "DVAE_DISC_CHAIN2_AUX=1": ({"DVAE_DISC_CHAIN2_AUX": "1"}, {}),
-    "DVAE_FORK_HOOK=0": ({"DVAE_FORK_HOOK": "0"}, {}),
-    "eager_wgrad": ({"DVAE_EAGER_WGRAD_ELEMS": str(1 << 40)}, {}),
-    "DVAE_TAIL_MAIN=": ({"DVAE_TAIL_MAIN": ""}, {}),
+    "default": {},
+    "DVAE_STREAMS=1": {"DVAE_STREAMS": "1"},
+    "DVAE_LATE_JOIN=0": {"DVAE_LATE_JOIN": "0"},
+    "SMALL_SHARD_ELEMS=0": {"DVAE_SMALL_SHARD_ELEMS": "0"},             # the two-span gradient exchange
+    "DVAE_DISC_WGRAD_SIDE=0": {"DVAE_DISC_WGRAD_SIDE": "0"},
+    "DVAE_DISC_CHAIN2_AUX=1": {"DVAE_DISC_CHAIN2_AUX": "1"},
+    "DVAE_FORK_HOOK=0": {"DVAE_FORK_HOOK": "0"},
+    "eager_wgrad": {"DVAE_EAGER_WGRAD_ELEMS": str(1 << 40)},
+    "DVAE_TAIL_MAIN=": {"DVAE_TAIL_MAIN": ""},
 }
 AXES = {
     "loss": ["betaH", "betaB", "btcvae", "factor"],
@@ -56,7 +56,7 @@ AXES = {
     # (geometry, latent_dim): thinned from the 2 x 2 product -- the tuned geometry with the fused FC chain, the small one with per-layer FC launches
     "model": [((3, 64, 64), 10), ((1, 32, 32), 17)],
     # thinned: 128 / 2048 for FactorVAE (even; both sides of its THREE_STREAM_MIN_ROWS), 129 (odd) for the others -- no other row
-    # threshold is read in models/losses.py with replay off, and the engine's are schedule_trace's business
+    # threshold acts on the step outside the engine's backward pass with replay off, and those are schedule_trace's business
     "rows": [128, 129, 2048],
     "dtype": ["float32", "uint8"],
     "world": [(1, 0), (2, 0), (2, 1)],
@@ -234,8 +234,9 @@ class StepTracer:
             for mod in (E, L, DISC):
                 p(mod, "call", self._call)
                 p(mod, "_stream", self.stream)
-            for mod in (E, L):
+            for mod in (E, L, SCHED):
                 p(mod, "knob", lambda name, default: self.knobs.get(name, default))
+            p(SCHED, "enabled", lambda: True)            # (the switches are read afresh for every step)
             p(torch.cuda, "stream", self._on)
             p(torch.cuda, "current_stream", lambda *a: T._Stream(self.stream()))
             p(L, "scale_", lambda t, alpha: self.out.append(("scale_", t.data_ptr(), alpha, self.stream())))
@@ -371,13 +372,8 @@ class StepTracer:
         self.world = W
         self.unit = ("Bh", Bh) if factor else ("B", B)
         self.rows = [("Bh", Bh), ("2Bh", 2 * Bh), ("WBh", W * Bh)] if factor else [("B", B), ("WB", W * B)]
-        # every per-step attribute at its default, then the case's switch
-        eng.single_stream = eng.eager_wgrad = eng.three_streams = eng.sharded = False
-        eng.tail_main, eng._fork_hook, eng._fc_pending = E._TAIL_MAIN, None, []
         eng._fc_descs.clear()
-        self.knobs, attrs = SWITCHES[switch]
-        loss_f.__dict__.pop("SMALL_SHARD_ELEMS", None)
-        loss_f.__dict__.update(attrs)
+        self.knobs = SWITCHES[switch]
         loss_f.comm = FakeComm(self, W, rank) if W > 1 else None
         loss_f.estimator = estimator
         model.training = mode == "train"

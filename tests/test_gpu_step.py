@@ -394,8 +394,8 @@ def test_replay_matches_eager(loss, mode):
 @pytest.mark.parametrize("loss,img,B", [("btcvae", (3, 64, 64), 16), ("factor", (1, 64, 64), 24), ("VAE", (1, 32, 32), 9),
                                         ("betaB", (3, 64, 64), 300), ("betaH", (1, 64, 64), 1100)])
 def test_conv_ends_inside_the_chain_launches_change_nothing(loss, img, B):
-    """engine.fuse_ends (the 8x8 <-> 4x4 layers and their input gradients as prologue / epilogue of dvae_fc_chain_fwd / _bwd,
-    up to engine.fuse_ends_max_rows rows per step; encoders.py:76-81, decoders.py:73-76) against the same steps with those four
+    """StepPolicy.fuse_ends (the 8x8 <-> 4x4 layers and their input gradients as prologue / epilogue of dvae_fc_chain_fwd / _bwd,
+    up to its fuse_ends_max_rows rows per step; encoders.py:76-81, decoders.py:73-76) against the same steps with those four
     layers as launches of their own: same arithmetic, so losses and parameters after 4 steps are bit-identical.  The row limits
     are honoured: up to 256 rows both directions carry the conv ends (4 launches fewer per step), up to 1024 rows the forward
     chain only (2 fewer), above that none."""
@@ -403,9 +403,8 @@ def test_conv_ends_inside_the_chain_launches_change_nothing(loss, img, B):
     runs = []
     for fuse in (False, True):
         model, opt, loss_f = _native(loss, img, 21, 202599, 5e-4)
-        eng = model.engine
-        assert eng.fuse_ends, "the shipped configuration fuses the conv ends"
-        eng.fuse_ends = fuse
+        assert model.engine.policy.fuse_ends, "the shipped configuration fuses the conv ends"
+        loss_f.policy_override = {"fuse_ends": fuse}
         loss_f.replay = None                               # eager: every launch of every step goes through engine.call (counted)
         gen = torch.Generator().manual_seed(4)
         losses = []

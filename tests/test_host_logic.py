@@ -527,26 +527,39 @@ def test_any_latent_dim_is_accepted_for_every_loss(loss):
 
 def test_round6_schedule_policies():
     """Host-side decisions of round 6, no kernels: which steps carry the 8x8 <-> 4x4 conv layers inside the FC-chain launches
-    (engine.fuse_ends, up to fuse_ends_max_rows rows; never above 16 latents, where there is no chain launch), which steps put
+    (StepPolicy.fuse_ends, up to fuse_ends_max_rows rows; never above 16 latents, where there is no chain launch), which steps put
     their weight gradients on two side streams (FactorVAE from 2048 rows, the other losses never) and where convT3's weight
     gradient is forked; the dvae_fc_chain_*_args structs carry the conv-end fields behind the version-108 ones."""
-    from disvae_amd import _lib
+    from disvae_amd import _lib, schedule as P
     from disvae_amd.engine import VAEEngine
 
-    def engine(img, D):          # (model.engine refuses on a CPU model: the engine object itself is host-side state only)
-        m = init_specific_model("Burgess", img, D)
-        return VAEEngine(m.img_size, m.latent_dim, m.arena)
-    eng = engine((3, 64, 64), 10)
-    assert eng.fuse_ends and eng.fuse_ends_max_rows == 256 and eng.fuse_ends_max_rows_fwd == 1024
-    assert eng.early_thin_wgrad == 1 and eng.early_thin_auto and not eng.sharded and not eng.three_streams
-    assert eng._ends(1) and eng._ends(256) and not eng._ends(257) and not eng._ends(1024)
-    assert engine((1, 32, 32), 10).fuse_ends          # conv3 / convT1 are that geometry's 4x4 end
-    assert not engine((3, 64, 64), 17).fuse_ends      # per-layer FC launches above 16 latents
-    eng.three_streams = True
+    def policy(img, D, rows=128, **kw):
+        return P.build_policy(img, D, rows, P.switches(), **kw)
+    pol = policy((3, 64, 64), 10)
+    assert pol.fuse_ends and pol.fuse_ends_max_rows == 256 and pol.fuse_ends_max_rows_fwd == 1024
+    assert pol.early_thin_wgrad == 1 and pol.early_thin_auto and not pol.sharded and not pol.three_streams
+    assert pol.ends(1) and pol.ends(256) and not pol.ends(257) and not pol.ends(1024)
+    assert pol.ends_fwd(257) and pol.ends_fwd(1024) and not pol.ends_fwd(1025)
+    assert policy((1, 32, 32), 10).fuse_ends          # conv3 / convT1 are that geometry's 4x4 end
+    assert not policy((3, 64, 64), 17).fuse_ends      # per-layer FC launches above 16 latents
+    # (model.engine refuses on a CPU model: the engine object itself is host-side state only)
+    m = init_specific_model("Burgess", (3, 64, 64), 10)
+    eng = VAEEngine(m.img_size, m.latent_dim, m.arena)
+    eng.begin_step(pol._replace(three_streams=True))
     assert eng._three(True) and not eng._three(False)
-    eng.single_stream = True
+    eng.begin_step(eng.policy._replace(single_stream=True))
     assert not eng._three(True)
-    assert L.BaseLoss.THREE_STREAM_MIN_ROWS > 1 << 20 and L.FactorKLoss.THREE_STREAM_MIN_ROWS == 2048
+    assert P.THREE_STREAM_MIN_ROWS > 1 << 20 and P.THREE_STREAM_MIN_ROWS_FACTOR == 2048
+    for kind, rows, three in ((_lib.LOSS_FACTOR, 2048, True), (_lib.LOSS_FACTOR, 2046, False), (_lib.LOSS_BTCVAE, 2048, False),
+                              (_lib.LOSS_BETAH, 4096, False)):
+        assert policy((3, 64, 64), 10, rows, kind=kind).three_streams == three, (kind, rows)
+    assert not policy((3, 64, 64), 10, 2048, kind=_lib.LOSS_FACTOR, world=2).three_streams      # single process only
+    # where convT3's weight gradient is forked: mode 1, mode 2 at 112-128 rows of a single process, nowhere on one stream
+    assert [pol.early_thin(r) for r in (111, 112, 128, 129)] == [1, 2, 2, 1]
+    assert policy((3, 64, 64), 10, world=2).early_thin(128) == 1 and pol._replace(single_stream=True).early_thin(128) == 0
+    assert [pol.fcw_main_at(r) for r in (128, 129, 320, 321)] == [False, True, True, False]
+    # a policy is a value: equal inputs give the same object, and it is the replay key's entry for every decision
+    assert policy((3, 64, 64), 10) is pol and hash(pol) == hash(pol._replace()) and pol != pol._replace(late_join=True)
     f = [n for n, _ in _lib.FcChainFwdArgs._fields_]
     b = [n for n, _ in _lib.FcChainBwdArgs._fields_]
     assert f[-6:] == ["conv_in", "conv_w", "conv_b", "convT_w", "convT_b", "convT_out"] and f[-7] == "D"
