@@ -8,6 +8,7 @@ snapshots).  Objects are rebuilt only when a source / header is newer or the fla
 switches and the experimental kernel variants they select (tools/README.md); the default (shipped)
 library has none of them.
 """
+import glob
 import os
 import subprocess
 import sys
@@ -17,8 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib", "libdvae_hip.so")
-HEADERS = [os.path.join(SRC, "common.h"), os.path.join(SRC, "conv_mfma_common.h"), os.path.join(SRC, "wgrad_reduce.h"),
-           os.path.join(HERE, "..", "include", "dvae_hip.h")]
+HEADERS = sorted(glob.glob(os.path.join(SRC, "*.h"))) + [os.path.join(HERE, "..", "include", "dvae_hip.h")]
 SOURCES = ["conv_generic", "conv_mfma", "conv_down_dma", "conv_up_ws", "conv_wgrad_ws", "conv_thin", "conv_thin_ws", "conv_up_thin_mm", "linear", "linear_narrow", "gemm_dma", "linear_grouped", "fc_chain", "stage", "loss", "latent_wide",
            "metrics", "adam", "comm", "viz", "loglik", "plan", "capi"]
 DEBUG_SOURCES = []          # experimental kernel files: only in --debug builds

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../../include/dvae_hip.h"
+#include "wave_spec.h"
 
 namespace dvae {
 

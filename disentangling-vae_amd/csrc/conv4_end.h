@@ -21,8 +21,7 @@ __device__ __forceinline__ void c4_weight_image_issue(const float* __restrict__ 
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     const int base = (k * 8 + wv) * 256;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(img + base + lane * 4),
-                                     (__attribute__((address_space(3))) void*)(wl + base), 16, 0, 0);
+    lds_dma16_tracked(img + base + lane * 4, wl + base);
   }
 }
 

@@ -23,9 +23,6 @@ namespace dvae {
 
 __device__ __attribute__((aligned(16))) float k_zero16[4] = {0.f, 0.f, 0.f, 0.f};
 
-typedef const __attribute__((address_space(1))) void* gas_ptr;
-typedef __attribute__((address_space(3))) void* las_ptr;
-
 template <int HS>
 struct DmaGeo {
   using G = Geo<HS>;
@@ -37,13 +34,6 @@ struct DmaGeo {
   static_assert(NCHUNK <= NBLK * 64, "tile fits the padded buffer");
   static_assert(G::IMGS == 1, "one image per unit");
 };
-
-__device__ __forceinline__ void barrier_nofence() {
-  // the LDS-DMA transfers of the NEXT tile must stay in flight across the barrier: no fence (a __syncthreads() would wait
-  // for vmcnt(0)); the orderings that matter are established by explicit s_waitcnt on the loader side and by the data
-  // dependences MFMA <- ds_read on the compute side
-  asm volatile("s_barrier" ::: "memory");
-}
 
 template <int HS, bool MASK>
 __global__ __launch_bounds__(512) void k_down32dma(const float* __restrict__ big, const float* __restrict__ w,
@@ -89,7 +79,7 @@ __global__ __launch_bounds__(512) void k_down32dma(const float* __restrict__ big
       float* bt = smem + buf * D::BUF_FLOATS;
 #pragma unroll
       for (int k = 0; k < D::NPF; ++k) {
-        __builtin_amdgcn_global_load_lds((gas_ptr)src[k], (las_ptr)(bt + (k * 4 + lw) * 256), 16, 0, 0);
+        lds_dma16_tracked(src[k], bt + (k * 4 + lw) * 256);
         src[k] = (const float*)((const char*)src[k] + inc[k]);
       }
     };
@@ -97,9 +87,8 @@ __global__ __launch_bounds__(512) void k_down32dma(const float* __restrict__ big
     if (unit < n_units) issue(0);
     if (unit + stride < n_units) issue(1);
     // tile(unit0) must have landed before the first barrier
-    if (unit + stride < n_units) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    static_assert(D::NPF == 11, "the s_waitcnt immediates below assume 11 transfers per tile");
+    if (unit + stride < n_units) wait_vmcnt<D::NPF>();
+    else wait_vmcnt<0>();
     barrier_nofence();
     int buf = 0;
     for (; unit < n_units; unit += stride) {
@@ -107,8 +96,8 @@ __global__ __launch_bounds__(512) void k_down32dma(const float* __restrict__ big
       const int b2 = buf >= 1 ? buf - 1 : 2;        // (buf + 2) % 3
       const bool more = unit + 2 * stride < n_units;
       if (more && !(abl & 4)) issue(b2);
-      if (more && !(abl & 4)) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");   // all but the 11 newest: tile(unit + stride) has landed
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (more && !(abl & 4)) wait_vmcnt<D::NPF>();   // all but the NPF newest: tile(unit + stride) has landed
+      else wait_vmcnt<0>();
       if (!(abl & 16)) barrier_nofence();
       buf = buf == 2 ? 0 : buf + 1;
     }

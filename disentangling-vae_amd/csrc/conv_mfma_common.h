@@ -182,11 +182,10 @@ __device__ __forceinline__ void copy_weight_image(const float* __restrict__ img,
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int base = (k * 8 + wv) * 256;             // 256 floats = 64 lanes x 16 bytes; the LDS side is lane-linear
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(img + base + lane * 4),
-                                       (__attribute__((address_space(3))) void*)(wl + base), 16, 0, 0);
+      lds_dma16_tracked(img + base + lane * 4, wl + base);
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // LDS-DMA completes in vmcnt order; the barrier that follows publishes it
+  wait_vmcnt<0>();                                     // LDS-DMA completes in vmcnt order; the barrier that follows publishes it
 }
 
 __device__ __forceinline__ float epilogue_act(float v, int act) {

@@ -9,7 +9,7 @@
 //              wave-uniform (scalar loads -> SGPR operands), inputs staged in swizzled LDS.
 //   wgrad_thin (conv1 / convT3 wgrad): M = 32 cs, N = 16*C (cb,tap) columns, K = pixels.
 #include <stdlib.h>
-#include "common.h"
+#include "recon_epilogue.h"
 #include "wgrad_reduce.h"
 
 namespace dvae {
@@ -31,13 +31,8 @@ struct BigThinRegs {
   unsigned ok;                     // nothing may depend on a prefetched register before the MFMA phase is over)
 };
 
-// Input elements: fp32, or uint8 pixels as the datasets store them (dSprites imgs * 255, CelebA imread:
-// utils/datasets.py:204-213,282-291) converted on the fly with ToTensor's arithmetic, float(v) / 255 (IEEE
-// division: bit-identical to torchvision's .div(255)).  The batch then stays uint8 in HBM: the three kernels that
-// read the input image (conv1 forward, conv1 weight gradient, reconstruction likelihood) fetch 1 byte per pixel.
-__device__ __forceinline__ float to_unit(float v) { return v; }
-__device__ __forceinline__ float to_unit(uint8_t v) { return (float)v / 255.0f; }
-// the 256 possible results as a table in LDS: one ds_read instead of the ~10-instruction IEEE division per pixel
+// Input elements: to_unit (recon_epilogue.h).  Here the 256 possible results as a table in LDS: one ds_read instead of the
+// ~10-instruction IEEE division per pixel
 // (the staging code of these kernels is instruction-issue-bound, not bandwidth-bound)
 struct UnitLut {
   float t[256];
@@ -506,8 +501,7 @@ __global__ __launch_bounds__(128) void k_up_thin_pk(const float* __restrict__ sm
           const long o = ((((long)n * C + cb) * 64) + 2 * sy + py) * 64 + 2 * l;
           if (FUSE && bce_logit) {
             // sigmoid + Bernoulli likelihood straight from the logit (common.h: sigmoid_bce_logit), workgroup-uniform branch
-            float xt0 = tg[cb][py].x, xt1 = tg[cb][py].y;
-            if constexpr (sizeof(TT) != 4) { xt0 = xt0 / 255.0f; xt1 = xt1 / 255.0f; }
+            const float xt0 = raw_to_unit<TT>(tg[cb][py].x), xt1 = raw_to_unit<TT>(tg[cb][py].y);
             float p0, p1, gl0, gl1;
             lsum += sigmoid_bce_logit(v0, xt0, &p0, &gl0);
             lsum += sigmoid_bce_logit(v1, xt1, &p1, &gl1);
@@ -519,8 +513,7 @@ __global__ __launch_bounds__(128) void k_up_thin_pk(const float* __restrict__ sm
           else if (act == DVAE_ACT_RELU) { v0 = v0 > 0.f ? v0 : 0.f; v1 = v1 > 0.f ? v1 : 0.f; }
           *reinterpret_cast<float2*>(out + o) = make_float2(v0, v1);
           if (FUSE) {
-            float xt0 = tg[cb][py].x, xt1 = tg[cb][py].y;
-            if constexpr (sizeof(TT) != 4) { xt0 = xt0 / 255.0f; xt1 = xt1 / 255.0f; }     // = to_unit(uint8_t): ToTensor's division
+            const float xt0 = raw_to_unit<TT>(tg[cb][py].x), xt1 = raw_to_unit<TT>(tg[cb][py].y);
             float gl0, gl1, gr;
             lsum += recon_elem(v0, xt0, dist, &gl0, &gr);
             lsum += recon_elem(v1, xt1, dist, &gl1, &gr);
@@ -744,22 +737,27 @@ int launch_up_thin_recon_u8(const ConvArgs& a, const uint8_t* target, float* g, 
   return 0;
 }
 
+// the two launches of a thin weight gradient: partial sums of `grid` workgroups into ws, then their fixed-order reduction
+template <int C>
+static int wgrad_thin_reduce(const float* ws, float* dw, float* db, int bias_from_big, int grid, hipStream_t s) {
+  hipLaunchKernelGGL(k_wgrad_thin_reduce<C>, dim3(WT_REDUCE_BLOCKS(C)), dim3(256), 0, s, ws, dw, db, bias_from_big, grid);
+  DVAE_CHECK_LAUNCH();
+  return 0;
+}
+template <int C, typename TB>
+static int wgrad_thin_two_pass(const TB* big, const float* small, float* dw, float* db, int bias_from_big, int N, int n_units,
+                               int grid, float* ws, hipStream_t s) {
+  hipLaunchKernelGGL((k_wgrad_thin<C, TB>), dim3(grid), dim3(256), 0, s, big, small, ws, N, n_units);
+  DVAE_CHECK_LAUNCH();
+  return wgrad_thin_reduce<C>(ws, dw, db, bias_from_big, grid, s);
+}
+
 int launch_wgrad_thin_u8(const uint8_t* x, const float* small, float* dw, float* db, int N, int C, float* ws, hipStream_t s) {
   const int n_units = N * 8;
   const int grid = n_units < WT_MAX_BLOCKS ? n_units : WT_MAX_BLOCKS;
-  if (C == 1) {
-    hipLaunchKernelGGL((k_wgrad_thin<1, uint8_t>), dim3(grid), dim3(256), 0, s, x, small, ws, N, n_units);
-    DVAE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_wgrad_thin_reduce<1>, dim3(WT_REDUCE_BLOCKS(1)), dim3(256), 0, s, ws, dw, db, 0, grid);
-  } else if (C == 3) {
-    hipLaunchKernelGGL((k_wgrad_thin<3, uint8_t>), dim3(grid), dim3(256), 0, s, x, small, ws, N, n_units);
-    DVAE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_wgrad_thin_reduce<3>, dim3(WT_REDUCE_BLOCKS(3)), dim3(256), 0, s, ws, dw, db, 0, grid);
-  } else {
-    return 1;
-  }
-  DVAE_CHECK_LAUNCH();
-  return 0;
+  if (C == 1) return wgrad_thin_two_pass<1>(x, small, dw, db, 0, N, n_units, grid, ws, s);
+  if (C == 3) return wgrad_thin_two_pass<3>(x, small, dw, db, 0, N, n_units, grid, ws, s);
+  return 1;
 }
 
 int launch_wgrad_thin(const float* big, const float* small, float* dw, float* db, int bias_from_big, int N, int Cb,
@@ -767,12 +765,8 @@ int launch_wgrad_thin(const float* big, const float* small, float* dw, float* db
   if (!(Cb == 1 || Cb == 3) || Hs != 32) return 1;
   {                                                     // large batches: the wave-specialised kernel (conv_thin_ws.hip)
     int wgrid = 0;
-    if (launch_wgrad_thin_ws(big, small, ws, bias_from_big, N, Cb, &wgrid, s) == 0) {
-      if (Cb == 1) hipLaunchKernelGGL(k_wgrad_thin_reduce<1>, dim3(WT_REDUCE_BLOCKS(1)), dim3(256), 0, s, ws, dw, db, bias_from_big, wgrid);
-      else hipLaunchKernelGGL(k_wgrad_thin_reduce<3>, dim3(WT_REDUCE_BLOCKS(3)), dim3(256), 0, s, ws, dw, db, bias_from_big, wgrid);
-      DVAE_CHECK_LAUNCH();
-      return 0;
-    }
+    if (launch_wgrad_thin_ws(big, small, ws, bias_from_big, N, Cb, &wgrid, s) == 0)
+      return Cb == 1 ? wgrad_thin_reduce<1>(ws, dw, db, bias_from_big, wgrid, s) : wgrad_thin_reduce<3>(ws, dw, db, bias_from_big, wgrid, s);
   }
   const int n_units = N * 8;
   int grid = n_units < WT_MAX_BLOCKS ? n_units : WT_MAX_BLOCKS;
@@ -780,17 +774,8 @@ int launch_wgrad_thin(const float* big, const float* small, float* dw, float* db
     static const int cap = env_int("DVAE_WGRAD_THIN_GRID", WT_MAX_BLOCKS);   // debug builds: A/B of the persistent grid size
     if (cap > 0 && cap < grid) grid = cap;
   }
-  if (Cb == 1) {
-    hipLaunchKernelGGL(k_wgrad_thin<1>, dim3(grid), dim3(256), 0, s, big, small, ws, N, n_units);
-    DVAE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_wgrad_thin_reduce<1>, dim3(WT_REDUCE_BLOCKS(1)), dim3(256), 0, s, ws, dw, db, bias_from_big, grid);
-  } else {
-    hipLaunchKernelGGL(k_wgrad_thin<3>, dim3(grid), dim3(256), 0, s, big, small, ws, N, n_units);
-    DVAE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_wgrad_thin_reduce<3>, dim3(WT_REDUCE_BLOCKS(3)), dim3(256), 0, s, ws, dw, db, bias_from_big, grid);
-  }
-  DVAE_CHECK_LAUNCH();
-  return 0;
+  return Cb == 1 ? wgrad_thin_two_pass<1>(big, small, dw, db, bias_from_big, N, n_units, grid, ws, s)
+                 : wgrad_thin_two_pass<3>(big, small, dw, db, bias_from_big, N, n_units, grid, ws, s);
 }
 
 }  // namespace dvae

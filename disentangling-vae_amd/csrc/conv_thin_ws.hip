@@ -29,8 +29,6 @@
 #include "common.h"
 #include "wgrad_reduce.h"
 
-#pragma clang diagnostic ignored "-Winline-asm"     // dma16s names m0 in its clobber list on purpose
-
 namespace dvae {
 
 template <int C, int MODE>
@@ -52,20 +50,6 @@ struct ThinWsGeo {
   static constexpr int TOTAL = BIAS + 32;
   static_assert(STAGE % 4 == 0 && OST % 4 == 0, "16-byte alignment of the stages");
 };
-
-// one LDS-DMA transfer: every ACTIVE lane l of the wave moves 16 bytes from base + its own 32-bit offset to LDS byte
-// lds_addr + 16 l (inactive lanes leave their LDS bytes alone)
-// (called with all 64 lanes active: the lane mask is applied to EXEC around the instruction and EXEC is set back to all ones)
-__device__ __forceinline__ void dma16s(const void* sbase, unsigned voff, unsigned lds_addr, unsigned long long lanes) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_mov_b64 exec, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1\n\ts_mov_b64 exec, -1" ::"v"(voff),
-               "s"(sbase), "s"(lds_addr), "s"(lanes)
-               : "memory", "m0");
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void thin_barrier() { asm volatile("s_barrier" ::: "memory"); }
 
 // ABL (debug builds only, results invalid): timing ablations -- 1 no output stores, 2 no MFMAs, 4 no LDS-DMA transfers,
 // 16 no epilogue at all; variants with valid results: 32 compute waves at s_setprio 3, 64 helper waves at s_setprio 3
@@ -122,15 +106,15 @@ __global__ __launch_bounds__(512, 4) void k_down_thin_ws(const float* __restrict
         if (!(ABL & 1)) *reinterpret_cast<f32x4*>(bbase + (unsigned)dl * 16u) = bw;
         else asm volatile("" ::"v"(bw[0]));
       }
-      __builtin_amdgcn_s_waitcnt(0xC07F);                  // lgkmcnt(0): the stage is read before the next barrier
+      wait_lgkmcnt0();                                     // lgkmcnt(0): the stage is read before the next barrier
     };
-    thin_barrier();                                        // prologue barrier
+    barrier_nofence();                                     // prologue barrier
     int m = 0;
     for (int n = n0; n < N; n += ipi, ++m) {
-      thin_barrier();                                      // barrier m: output stage of unit m - 2 is complete
+      barrier_nofence();                                   // barrier m: output stage of unit m - 2 is complete
       if (m >= 2) drain(m & 1, n - 2 * ipi);
     }
-    thin_barrier();                                        // final barrier: both output stages are complete
+    barrier_nofence();                                     // final barrier: both output stages are complete
     if (m >= 2) drain(m & 1, n0 + (m - 2) * ipi);
     if (m >= 1) drain((m - 1) & 1, n0 + (m - 1) * ipi);
     return;
@@ -172,9 +156,9 @@ __global__ __launch_bounds__(512, 4) void k_down_thin_ws(const float* __restrict
       for (int k = 0; k < NPFM; ++k) {
         const int d = lw + 2 * k;                          // wave-uniform
         if (d < 3 * C) {
-          dma16s(ibase, voff[k], __builtin_amdgcn_readfirstlane(base + (unsigned)((d / 3) * G::PLANE + (d % 3) * 256) * 4u), lanes[k]);
+          lds_dma16_masked(ibase, voff[k], __builtin_amdgcn_readfirstlane(base + (unsigned)((d / 3) * G::PLANE + (d % 3) * 256) * 4u), lanes[k]);
         } else if (MODE == 2 && d == 3 * C) {
-          dma16s(bbase, voff[k], __builtin_amdgcn_readfirstlane(base + G::BITS_OFF * 4u), lanes[k]);
+          lds_dma16_masked(bbase, voff[k], __builtin_amdgcn_readfirstlane(base + G::BITS_OFF * 4u), lanes[k]);
         }
       }
       ibase += (long)ipi * C * 4096;
@@ -192,16 +176,16 @@ __global__ __launch_bounds__(512, 4) void k_down_thin_ws(const float* __restrict
     if (n + ipi < N) issue(1);
     if (n + 2 * ipi < N) issue(2);
     wait_landed((n + ipi < N) + (n + 2 * ipi < N));        // tile(n0) has landed
-    thin_barrier();                                        // prologue barrier
+    barrier_nofence();                                     // prologue barrier
     int buf = 0;
     for (; n < N; n += ipi) {
       // the compute waves read tile(n + ipi) next (stage buf + 1); stage buf + 3 = buf - 1 was released by the last barrier
       if (n + 3 * ipi < N) issue((buf + 3) & 3);
       wait_landed((n + 2 * ipi < N) + (n + 3 * ipi < N));  // tile(n + ipi) has landed
-      thin_barrier();
+      barrier_nofence();
       buf = nxt(buf);
     }
-    thin_barrier();                                        // final barrier
+    barrier_nofence();                                     // final barrier
     return;
   }
 
@@ -219,8 +203,8 @@ __global__ __launch_bounds__(512, 4) void k_down_thin_ws(const float* __restrict
   // output stage: pixel (wv * 32 + i) row of 32 floats, 16-byte chunk (2 g + h) at slot (2 g + h) ^ ((i >> 1) & 7)
   const int obase = (wv * 32 + i) * 32;
   const int osw = (i >> 1) & 7;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the only vector loads of these waves
-  thin_barrier();                                          // prologue barrier: tile(n0) is in stage 0
+  wait_vmcnt<0>();                                         // the only vector loads of these waves
+  barrier_nofence();                                       // prologue barrier: tile(n0) is in stage 0
 
   struct Ops {                                             // operands of one unit, as read from its tile
     float a[8 * C];
@@ -282,8 +266,8 @@ __global__ __launch_bounds__(512, 4) void k_down_thin_ws(const float* __restrict
   // (the next tile's stage is read even when there is no next unit: stale LDS, never used)
   auto unit = [&](Ops& oc, Ops& on, int nbuf, Pend& cur, const Pend& old, int ob, auto have_old) {
     constexpr bool HAVE_OLD = decltype(have_old)::value;
-    __builtin_amdgcn_s_waitcnt(0xC07F);                    // lgkmcnt(0): this unit's operands have returned (its tile is read)
-    thin_barrier();                                        // ... and the next tile has landed
+    wait_lgkmcnt0();                                       // lgkmcnt(0): this unit's operands have returned (its tile is read)
+    barrier_nofence();                                     // ... and the next tile has landed
     cur.word = oc.word >> (4 * h);
     read_word(nbuf, on);
     __builtin_amdgcn_sched_barrier(0);
@@ -329,8 +313,8 @@ __global__ __launch_bounds__(512, 4) void k_down_thin_ws(const float* __restrict
       n += ipi, buf = nxt(buf), ++m;
     }
   }
-  __builtin_amdgcn_s_waitcnt(0xC07F);                      // lgkmcnt(0): the last output stage is written
-  thin_barrier();                                          // final barrier
+  wait_lgkmcnt0();                                         // lgkmcnt(0): the last output stage is written
+  barrier_nofence();                                       // final barrier
 }
 
 // fp32 NCHW images only; returns 1 if the shape is not covered (the caller falls back to k_down_thin)
@@ -478,9 +462,9 @@ __global__ __launch_bounds__(512, 4) void k_wgrad_thin_ws(const float* __restric
 #pragma unroll
       for (int k = 0; k < NPFM; ++k) {
         const int d = lw + 4 * k;                          // wave-uniform
-        if (d < 16) dma16s(sbase, voff[k], __builtin_amdgcn_readfirstlane(base + (unsigned)d * 1024u), lanes[k]);
+        if (d < 16) lds_dma16_masked(sbase, voff[k], __builtin_amdgcn_readfirstlane(base + (unsigned)d * 1024u), lanes[k]);
         else if (d < G::NDMA)
-          dma16s(ibase, voff[k], __builtin_amdgcn_readfirstlane(base + (unsigned)(G::SM + ((d - 16) / 3) * G::PLANE + ((d - 16) % 3) * 256) * 4u), lanes[k]);
+          lds_dma16_masked(ibase, voff[k], __builtin_amdgcn_readfirstlane(base + (unsigned)(G::SM + ((d - 16) / 3) * G::PLANE + ((d - 16) % 3) * 256) * 4u), lanes[k]);
       }
       ibase += (long)ipi * C * 4096;
       sbase += (long)ipi * 32768;
@@ -497,19 +481,19 @@ __global__ __launch_bounds__(512, 4) void k_wgrad_thin_ws(const float* __restric
     if (n < N) issue(0);
     if (n + ipi < N) issue(1);
     wait_landed(n + ipi < N);                              // tile(n0) has landed
-    thin_barrier();                                        // prologue barrier
+    barrier_nofence();                                     // prologue barrier
     int buf = 0;
     for (; n < N; n += ipi) {
       // the compute waves read tile(n + ipi) next (stage buf + 1); stage buf + 2 was released by the last barrier
       const bool more = n + 2 * ipi < N;
       if (more) issue(buf >= 1 ? buf - 1 : 2);
       wait_landed(more);                                   // tile(n + ipi) has landed
-      thin_barrier();
+      barrier_nofence();
       buf = nxt(buf);
     }
-    thin_barrier();                                        // final barrier: every tile is consumed
-    thin_barrier();                                        // the reduction's barriers (the loaders take part: s_barrier counts
-    thin_barrier();                                        // every wave of the workgroup)
+    barrier_nofence();                                     // final barrier: every tile is consumed
+    barrier_nofence();                                     // the reduction's barriers (the loaders take part: s_barrier counts
+    barrier_nofence();                                     // every wave of the workgroup)
     return;
   }
 
@@ -532,7 +516,7 @@ __global__ __launch_bounds__(512, 4) void k_wgrad_thin_ws(const float* __restric
   float sumB[C];
 #pragma unroll
   for (int nt = 0; nt < C; ++nt) sumB[nt] = 0.f;
-  thin_barrier();                                          // prologue barrier: tile(n0) is in stage 0
+  barrier_nofence();                                       // prologue barrier: tile(n0) is in stage 0
 
   // Operands: the NEXT unit's are read under the current unit's MFMAs, step for step (the barrier in front of a unit says
   // that the next tile has landed).  A tile is therefore read completely one unit BEFORE its MFMAs run: the loaders refill
@@ -553,8 +537,8 @@ __global__ __launch_bounds__(512, 4) void k_wgrad_thin_ws(const float* __restric
   // the 8 steps of the unit whose operands are in `oc`; every step refills its registers with the next unit's operands (stage
   // `nbuf`; stale and unused if there is none)
   auto unit = [&](Ops& oc, int nbuf) {
-    __builtin_amdgcn_s_waitcnt(0xC07F);                    // lgkmcnt(0): this unit's operands have returned (its tile is read)
-    thin_barrier();                                        // ... and the next tile has landed
+    wait_lgkmcnt0();                                       // lgkmcnt(0): this unit's operands have returned (its tile is read)
+    barrier_nofence();                                     // ... and the next tile has landed
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
       if (BIAS_BIG) {
@@ -582,8 +566,8 @@ __global__ __launch_bounds__(512, 4) void k_wgrad_thin_ws(const float* __restric
       buf = nxt(buf);
     }
   }
-  __builtin_amdgcn_s_waitcnt(0xC07F);
-  thin_barrier();                                          // final barrier: every tile is consumed, the stages are free
+  wait_lgkmcnt0();
+  barrier_nofence();                                       // final barrier: every tile is consumed, the stages are free
 
   // cross-wave reduction in a fixed order through LDS: red[wave][slot][lane], slot = (mt * C + nt) * 4 + r, then the two
   // (one + C) bias partials
@@ -599,8 +583,8 @@ __global__ __launch_bounds__(512, 4) void k_wgrad_thin_ws(const float* __restric
   red[(wv * NSLOT + G::NACC + 1) * 64 + lane] = sumS[1];
 #pragma unroll
   for (int nt = 0; nt < C; ++nt) red[(wv * NSLOT + G::NACC + 2 + nt) * 64 + lane] = sumB[nt];
-  __builtin_amdgcn_s_waitcnt(0xC07F);
-  thin_barrier();
+  wait_lgkmcnt0();
+  barrier_nofence();
   constexpr int STRIDE = NT32 * 1024 + 32 + NT32 * 32;     // k_wgrad_thin's partial block: [nt32][cs][32] + sumS[32] + sumB[nt32][32]
   float* wsw = ws + (long)blockIdx.x * STRIDE;
   const int t4 = tid;                                      // 256 compute threads
@@ -631,7 +615,7 @@ __global__ __launch_bounds__(512, 4) void k_wgrad_thin_ws(const float* __restric
     }
     wsw[NT32 * 1024 + 32 + nidx] = v;
   }
-  thin_barrier();
+  barrier_nofence();
 }
 
 // fp32 images only; writes gridDim.x = *grid_out partial blocks in k_wgrad_thin's layout; returns 1 if not covered

@@ -24,7 +24,7 @@
 //     likelihood term, dL/dlogit -> recon and g_logit rows written whole.
 // Every output is a fixed-order sum (tap-major, 8 contraction steps per tap, 4 channels per step inside the MFMA); results
 // differ from k_up_thin_pk's in summation order only (tests: rtol 1e-5 of the layer scale against fp64).
-#include "common.h"
+#include "recon_epilogue.h"
 
 namespace dvae {
 
@@ -46,7 +46,7 @@ __device__ __forceinline__ float sigmoid_hw_mm(float v) { return sigmoid_aten(v)
 #define UTM_ABL 0        // 8 no output stores, 16 no tile loads
 #endif
 __device__ __forceinline__ void utm_barrier() {
-  if (UTM_VARIANT & 4) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  if (UTM_VARIANT & 4) { wait_lgkmcnt0(); barrier_nofence(); }
   else __syncthreads();
 }
 
@@ -218,8 +218,7 @@ __global__ __launch_bounds__(512, 4) void k_up_thin_mm(const float* __restrict__
     if (FUSE && !(UTM_VARIANT & (2 | 8 | 16))) load_targets();
     if (FUSE && sizeof(TT) != 4) {
 #pragma unroll
-      for (int k = 0; k < 3; ++k)     // ToTensor
-        tg[k] = f32x4{(float)tg8[k].x / 255.0f, (float)tg8[k].y / 255.0f, (float)tg8[k].z / 255.0f, (float)tg8[k].w / 255.0f};
+      for (int k = 0; k < 3; ++k) tg[k] = f32x4{to_unit(tg8[k].x), to_unit(tg8[k].y), to_unit(tg8[k].z), to_unit(tg8[k].w)};
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {

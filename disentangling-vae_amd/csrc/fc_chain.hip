@@ -198,9 +198,7 @@ __device__ __forceinline__ void l2_warm(const float* __restrict__ p, int nfloats
   // one transfer touches 64 different 64-byte sectors (16 bytes of each): 4 KB of the image per instruction
   const int nblk = nfloats >> 10;                   // 4 KB blocks
   for (int b = share + nshares * wv; b < nblk; b += nshares * nwaves)
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(p + (long)b * 1024 + lane * 16),
-                 "s"(lds_byte_addr)
-                 : "memory", "m0");
+    lds_dma16(p + (long)b * 1024 + lane * 16, lds_byte_addr);
 }
 
 struct FwdArgs { dvae_fc_chain_fwd_args a; };
@@ -321,7 +319,7 @@ __global__ __launch_bounds__(256 * KS) void k_fc_chain_fwd(const FwdArgs P) {
     f32x4 pf[Geo<4>::BIG_NPF];
     load_big<4>(pf, sd, a.conv_in, blockIdx.x * RG, a.n_enc);
     c4_weight_image_issue(a.conv_w, smem + LD::WL, tid);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // (the barrier inside the unit publishes the image)
+    wait_vmcnt<0>();                                          // (the barrier inside the unit publishes the image)
     float* a_out = const_cast<float*>(a.a_flat);
 #pragma unroll
     for (int u = 0; u < RG; ++u) {
@@ -544,7 +542,7 @@ __global__ __launch_bounds__(256 * KS) void k_fc_chain_bwd(const BwdArgs P) {
     f32x4 pf[Geo<4>::BIG_NPF];
     load_big<4>(pf, sd, a.convT_gout, blockIdx.x * RG, n);
     c4_weight_image_issue(a.convT_w, smem + LD::WL, tid);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     float* g_out = const_cast<float*>(a.gd3);
 #pragma unroll
     for (int u = 0; u < RG; ++u) {

@@ -29,23 +29,9 @@
 #include <type_traits>
 #include "common.h"
 
-// dma16 names m0 in its clobber list on purpose (the instruction takes its LDS base from m0)
-#pragma clang diagnostic ignored "-Winline-asm"
-
 namespace dvae {
 
 __device__ __attribute__((aligned(16))) float k_gdma_zero16[4] = {0.f, 0.f, 0.f, 0.f};
-
-// one LDS-DMA transfer: lane l of the wave moves 16 bytes from its own global address to LDS byte lds_addr + 16 l
-__device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds_addr) : "memory", "m0");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void gdma_barrier() { asm volatile("s_barrier" ::: "memory"); }
 
 // workgroup -> (tile row, tile column): linear tile order = (column block of 8, row, column within the block); the
 // workgroups of XCD x (blockIdx % 8 == x) take the x-th eighth of that order
@@ -150,34 +136,34 @@ __global__ __launch_bounds__(512) void k_gdma(const float* __restrict__ a, long 
       if (slab < nslab - 1) {
 #pragma unroll
         for (int p = 0; p < G::P; ++p) {
-          dma16(src[p], dst + p * 4096u);
+          lds_dma16(src[p], dst + p * 4096u);
           src[p] += step[p];
         }
       } else {                                             // last slab: chunks beyond the contraction come from the zero block
 #pragma unroll
         for (int p = 0; p < G::P; ++p)
-          dma16((tail_ok >> p) & 1u ? src[p] : reinterpret_cast<const char*>(k_gdma_zero16), dst + p * 4096u);
+          lds_dma16((tail_ok >> p) & 1u ? src[p] : reinterpret_cast<const char*>(k_gdma_zero16), dst + p * 4096u);
       }
     };
     // D slabs in flight; slabs 0 and 1 landed before the first barrier (slab 1 feeds the early reads of iteration 0)
 #pragma unroll
     for (int s = 0; s < D; ++s)
       if (s < nslab) issue(s, s);
-    if (nslab >= D) wait_vm<(D - 2) * G::P>();
-    else wait_vm<0>();
-    gdma_barrier();
+    if (nslab >= D) wait_vmcnt<(D - 2) * G::P>();
+    else wait_vmcnt<0>();
+    barrier_nofence();
     int isb = D;                                           // stage that receives slab s + D (= the stage slab s - 1 just left)
     for (int s = 0; s < nslab; ++s) {
       if (s + D < nslab) {
         issue(s + D, isb);
-        wait_vm<(D - 2) * G::P>();                         // all but the newest D - 2 slabs: slab s + 2 has landed
+        wait_vmcnt<(D - 2) * G::P>();                      // all but the newest D - 2 slabs: slab s + 2 has landed
       } else {
-        wait_vm<0>();
+        wait_vmcnt<0>();
       }
-      gdma_barrier();
+      barrier_nofence();
       isb = isb + 1 == G::NS ? 0 : isb + 1;
     }
-    if (NWK > 1) gdma_barrier();                           // the barrier of the final sum
+    if (NWK > 1) barrier_nofence();                        // the barrier of the final sum
     return;
   }
 
@@ -221,7 +207,7 @@ __global__ __launch_bounds__(512) void k_gdma(const float* __restrict__ a, long 
     }
   };
 
-  gdma_barrier();                                          // slabs 0 and 1 are in stages 0 and 1
+  barrier_nofence();                                       // slabs 0 and 1 are in stages 0 and 1
   rd(gd_lds, 0, 0);
   int cur = 0;
   for (int s = 0; s < nslab; ++s) {
@@ -242,7 +228,7 @@ __global__ __launch_bounds__(512) void k_gdma(const float* __restrict__ a, long 
       __builtin_amdgcn_sched_group_barrier(0x100, G::NACC + (B_JFAST ? 4 : 1), 0);   // the next round's DS reads first
       __builtin_amdgcn_sched_group_barrier(0x008, 4 * G::NACC, 0);                   // then this round's MFMAs
     }
-    gdma_barrier();                                        // slab s + 2 has landed; stage `cur` is released
+    barrier_nofence();                                     // slab s + 2 has landed; stage `cur` is released
     cur = nxt;
   }
 
@@ -301,7 +287,7 @@ __global__ __launch_bounds__(512) void k_gdma(const float* __restrict__ a, long 
     const f32x16 r = acc[0][0] + acc[0][NCH - 1];
 #pragma unroll
     for (int e = 0; e < 16; ++e) red[(wk * 16 + e) * 64 + lane] = r[e];
-    gdma_barrier();
+    barrier_nofence();
     f32x4 v;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -364,33 +350,33 @@ __global__ __launch_bounds__(512) void k_gdma_wg(const float* __restrict__ dy, c
       if (slab < nslab - 1) {
 #pragma unroll
         for (int p = 0; p < P; ++p) {
-          dma16(src[p], dst + p * 4096u);
+          lds_dma16(src[p], dst + p * 4096u);
           src[p] += step[p];
         }
       } else {
 #pragma unroll
         for (int p = 0; p < P; ++p)
-          dma16((tail_ok >> p) & 1u ? src[p] : reinterpret_cast<const char*>(k_gdma_zero16), dst + p * 4096u);
+          lds_dma16((tail_ok >> p) & 1u ? src[p] : reinterpret_cast<const char*>(k_gdma_zero16), dst + p * 4096u);
       }
     };
 #pragma unroll
     for (int s = 0; s < D; ++s)
       if (s < nslab) issue(s, s);
-    if (nslab >= D) wait_vm<(D - 2) * P>();
-    else wait_vm<0>();
-    gdma_barrier();
+    if (nslab >= D) wait_vmcnt<(D - 2) * P>();
+    else wait_vmcnt<0>();
+    barrier_nofence();
     int isb = D;
     for (int s = 0; s < nslab; ++s) {
       if (s + D < nslab) {
         issue(s + D, isb);
-        wait_vm<(D - 2) * P>();
+        wait_vmcnt<(D - 2) * P>();
       } else {
-        wait_vm<0>();
+        wait_vmcnt<0>();
       }
-      gdma_barrier();
+      barrier_nofence();
       isb = isb + 1 == NS ? 0 : isb + 1;
     }
-    gdma_barrier();                                        // the barrier of the final sum
+    barrier_nofence();                                     // the barrier of the final sum
     return;
   }
 
@@ -410,7 +396,7 @@ __global__ __launch_bounds__(512) void k_gdma_wg(const float* __restrict__ dy, c
     av[slot] = *reinterpret_cast<const f32x2*>(st + a_off + t * 128);
     bv[slot] = *reinterpret_cast<const f32x2*>(st + b_off + t * 128);
   };
-  gdma_barrier();
+  barrier_nofence();
   rd(gd_lds, 0, 0);
   int cur = 0;
   for (int s = 0; s < nslab; ++s) {
@@ -432,7 +418,7 @@ __global__ __launch_bounds__(512) void k_gdma_wg(const float* __restrict__ dy, c
       __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
       __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
     }
-    gdma_barrier();
+    barrier_nofence();
     cur = nxt;
   }
 
@@ -448,7 +434,7 @@ __global__ __launch_bounds__(512) void k_gdma_wg(const float* __restrict__ dy, c
     const float v = rs[q] + __shfl_xor(rs[q], 32, 64);
     if (h == 0) rsp[(wv * 2 + q) * 32 + i] = v;
   }
-  gdma_barrier();
+  barrier_nofence();
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int e = 4 * wv + u;

@@ -2,7 +2,7 @@
 // decoded samples per image, and the importance-weighted estimate of log p(x) (Burda et al.) folded over those rows.
 // Semantics restated in include/dvae_hip.h (dvae_recon_rows, dvae_iw_loglik).
 #include <math.h>
-#include "common.h"
+#include "recon_epilogue.h"
 
 namespace dvae {
 
@@ -11,19 +11,6 @@ namespace {
 constexpr int RR_THREADS = 256;
 constexpr int RR_ROWS = 8;                                 // reconstruction rows per workgroup (the target's reuse factor)
 constexpr int RR_SLICE = RR_THREADS;                       // 16-byte quads per column slice: one per thread (1024 elements)
-
-// target quad -> fp32 (uint8: ToTensor's float(v) / 255, as k_u8_to_f32)
-__device__ __forceinline__ f32x4 target_quad(const void* __restrict__ target, int u8, long q) {
-  f32x4 t;
-  if (u8) {
-    const uint32_t w = reinterpret_cast<const uint32_t*>(target)[q];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) t[j] = (float)((w >> (8 * j)) & 0xff) / 255.0f;
-  } else {
-    t = reinterpret_cast<const f32x4*>(target)[q];
-  }
-  return t;
-}
 
 // One workgroup per (image i, RR_ROWS consecutive samples k0 .., column slice c).  Thread t loads quad t of the slice of the
 // target ONCE into registers, then the same quad of the workgroup's (up to) RR_ROWS reconstruction rows -- all row loads issued
