@@ -5,7 +5,10 @@ step_trace.dropped), without a GPU and without the library.
 
 test_step_trace_matches_recorded compares entry by entry with tests/golden/step_launch_trace.json, recorded once from
 commit 6d5b14e (the last one before models/losses.py was reorganised into one step skeleton) and not regenerated since.
-test_step_invariants states what must hold of ANY step, independent of the fixture."""
+test_step_invariants states what must hold of ANY step, independent of the fixture.  Its invariant 1 (a launch off the main
+stream is ordered behind the main-stream launch that wrote its newest operand) is one direction of one kind of hazard; the
+general form -- every cross-stream read-after-write, write-after-read and write-after-write, from any stream, workspaces
+included -- is tests/test_schedule_hazards.py."""
 import itertools
 import json
 import os
