@@ -137,7 +137,10 @@ int dvae_stage_weights(const dvae_conv_image_desc* conv, int n_conv, const dvae_
 /* The last decoder layer on its staged pair records: recon[N,C,64,64] (NCHW) = sigmoid(convT(x[N,32,32,32] NHWC) + b)
  * (decoders.py:82); with target != NULL (fp32 [N,C,64,64], or uint8 pixels when target_is_u8) also the reconstruction
  * likelihood partial sums and g = coef[INV_B] * dLoss/dlogit, exactly as dvae_convT4s2_sigmoid_recon_fwd[_u8]
- * (losses.py:394-449) -- the same kernel structure with the multiply-adds issued as packed fp32 FMAs.             */
+ * (losses.py:394-449) -- the same kernel structure with the multiply-adds issued as packed fp32 FMAs.
+ * Alignment: x and img_pairs 16 bytes.  recon, g and a fp32 target AT LEAST 8 bytes, a uint8 target at least 2 (not checked
+ * by the entry point: the kernels store float2 and load float2 / uchar2).  At C = 3 the matrix-core kernel runs when recon,
+ * g and a fp32 target are 16-byte and a uint8 target 4-byte aligned; otherwise the packed-FMA kernel takes the call.   */
 int dvae_convT3_fwd_staged(const float* x, const float* img_pairs, const float* b, const void* target, int target_is_u8,
                            float* recon, float* g, int dist, const float* coef, float* partials, int N, int C,
                            void* stream);

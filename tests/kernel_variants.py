@@ -1,0 +1,342 @@
+"""Which test reaches which kernel (a plain data module, like the spec table of the memory-contract tests; checked without a GPU
+by tests/test_kernel_variants_host.py; derived by reading the launchers -- tools/kernel_trace_names.py reduces a kernel trace of
+tests/test_gpu_kernel_variants.py to the names to compare with).
+
+VARIANTS   one row per __global__ kernel instantiation of the SHIPPED library (build.py without --debug):
+             kernel   the demangled name as `nm -C` prints it behind dvae::__device_stub__, template arguments included
+                      (matched literally against the whole name);
+             entry    the C-ABI entry point(s) whose launcher selects it;
+             when     the argument condition, copied from the launcher;
+             where    the launch site, file:line under disentangling-vae_amd/csrc/;
+             test     node id of one GPU test that makes such a call, or None;
+             reason   test is None: why no call of the shipped library can reach the kernel.
+SWITCHES   numeric thresholds in the launchers: (launcher, variable, threshold, where, last shape of one side, its test id,
+           first shape of the other side, its test id -- a different id).
+OPEN_SWITCHES  thresholds read in the launchers that have no such pair yet.
+"""
+from collections import namedtuple
+
+Variant = namedtuple("Variant", "kernel entry when where test reason")
+Switch = namedtuple("Switch", "launcher variable threshold where below below_test above above_test")
+
+K = "tests/test_gpu_kernels.py::"
+V = "tests/test_gpu_kernel_variants.py::"
+B = "tests/test_gpu_bench_sizes.py::"
+FC = "tests/test_gpu_fused_core.py::"
+MB = "tests/test_gpu_mask_bits.py::"
+U8 = "tests/test_gpu_uint8_input.py::"
+MC = "tests/test_gpu_memory_contract.py::test_memory_contract"
+WL = "tests/test_gpu_wide_latent.py::"
+
+_DEBUG_ONLY = ("the wave-specialised kernel takes every shape this one covers; the launcher falls through to it only with %s=0, "
+               "an environment switch that exists in --debug builds only (common.h: env_off() is constant false)")
+_SMALL_ONLY = ("use_small() (linear.hip:559) returns true only for the forward with K % 4 == 0 unless DVAE_GEMM_SMALL is set, "
+               "which --debug builds only read")
+
+
+def _v(kernel, entry, when, where, test=None, reason=None):
+    return Variant(kernel, entry, when, where, test, reason)
+
+
+VARIANTS = [
+    # ---- adam.hip
+    _v("k_adam", "dvae_adam_step", "always; one launch per ADAM_MAX_T = 64 tensors", "adam.hip:91", V + "test_adam_at_the_table_split[65]"),
+    # ---- conv_down_dma.hip (launch_down_mfma32 -> launch_down_mfma32_dma: 32 <-> 32 channels, NHWC, Hs in {16, 8})
+    _v("k_down32dma<16, false>", "dvae_conv4s2_fwd, dvae_conv32_down", "Hs == 16, no mask", "conv_down_dma.hip:232", V + "test_conv32_at_the_persistent_grid_switch[64-16]"),
+    _v("k_down32dma<16, true>", "dvae_convT4s2_dgrad, dvae_conv32_down", "Hs == 16, mask", "conv_down_dma.hip:231", V + "test_conv32_at_the_persistent_grid_switch[65-16]"),
+    _v("k_down32dma<8, false>", "dvae_conv4s2_fwd, dvae_conv32_down", "Hs == 8, no mask", "conv_down_dma.hip:232", V + "test_conv32_at_the_persistent_grid_switch[256-8]"),
+    _v("k_down32dma<8, true>", "dvae_convT4s2_dgrad, dvae_conv32_down", "Hs == 8, mask", "conv_down_dma.hip:231", V + "test_conv32_at_the_persistent_grid_switch[257-8]"),
+    # ---- conv_generic.hip
+    _v("k_chansum", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "generic geometry, db != NULL, fewer than 2 position chunks", "conv_generic.hip:399", V + "test_generic_wgrad_at_the_chunk_switches[7]"),
+    _v("k_relayout", "dvae_relayout", "always", "conv_generic.hip:424", K + "test_relayout"),
+    _v("k_up_generic", "dvae_convT4s2_fwd, dvae_conv4s2_dgrad", "no tuned kernel applies or DVAE_FORCE_GENERIC=1", "conv_generic.hip:370", K + "test_convT_fwd_dgrad_wgrad[3-16-32-1-1-True]"),
+    _v("k_up_thin_px<1>", "dvae_convT4s2_fwd, dvae_conv4s2_dgrad", "Cs == 32, Cb == 1, small NHWC, not 64x64", "conv_generic.hip:364", K + "test_thin_ends_at_any_size_match_the_plain_generic_kernels[3-1-32]"),
+    _v("k_up_thin_px<3>", "dvae_convT4s2_fwd, dvae_conv4s2_dgrad", "Cs == 32, Cb == 3, small NHWC, not 64x64", "conv_generic.hip:365", K + "test_thin_ends_at_any_size_match_the_plain_generic_kernels[5-3-32]"),
+    _v("k_down_generic", "dvae_conv4s2_fwd, dvae_convT4s2_dgrad", "no tuned kernel applies or DVAE_FORCE_GENERIC=1", "conv_generic.hip:351", K + "test_conv_fwd_dgrad_wgrad[3-32-32-1-True]"),
+    _v("k_down_thin_px<1>", "dvae_conv4s2_fwd, dvae_convT4s2_dgrad", "Cs == 32, Cb == 1, NCHW -> NHWC, not 64x64", "conv_generic.hip:345", K + "test_thin_ends_at_any_size_match_the_plain_generic_kernels[3-1-32]"),
+    _v("k_down_thin_px<3>", "dvae_conv4s2_fwd, dvae_convT4s2_dgrad", "Cs == 32, Cb == 3, NCHW -> NHWC, not 64x64", "conv_generic.hip:346", K + "test_thin_ends_at_any_size_match_the_plain_generic_kernels[5-3-32]"),
+    _v("k_wgrad_generic", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "generic geometry, N * Hs * Ws / 1024 < 2 or no workspace", "conv_generic.hip:395", V + "test_generic_wgrad_at_the_chunk_switches[7]"),
+    _v("k_wgrad_generic_fin", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "generic geometry, N * Hs * Ws / 1024 >= 2, workspace", "conv_generic.hip:390", V + "test_generic_wgrad_at_the_chunk_switches[8]"),
+    _v("k_wgrad_generic_part", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "generic geometry, N * Hs * Ws / 1024 >= 2, workspace", "conv_generic.hip:386", V + "test_generic_wgrad_at_the_chunk_switches[8]"),
+    # ---- conv_mfma.hip
+    _v("k_up32<16, false>", "dvae_convT4s2_fwd, dvae_conv32_up", "Hs == 16, no mask, after launch_up_mfma32_ws declined", "conv_mfma.hip:414", None, _DEBUG_ONLY % "DVAE_UP_WS"),
+    _v("k_up32<16, true>", "dvae_conv4s2_dgrad, dvae_conv32_up", "Hs == 16, mask, after launch_up_mfma32_ws declined", "conv_mfma.hip:413", None, _DEBUG_ONLY % "DVAE_UP_WS"),
+    _v("k_up32<8, false>", "dvae_convT4s2_fwd, dvae_conv32_up", "Hs == 8, no mask, after launch_up_mfma32_ws declined", "conv_mfma.hip:414", None, _DEBUG_ONLY % "DVAE_UP_WS"),
+    _v("k_up32<8, true>", "dvae_conv4s2_dgrad, dvae_conv32_up", "Hs == 8, mask, after launch_up_mfma32_ws declined", "conv_mfma.hip:413", None, _DEBUG_ONLY % "DVAE_UP_WS"),
+    _v("k_up32<4, false>", "dvae_convT4s2_fwd, dvae_conv32_up", "Hs == 4, no mask (small side NHWC or NCHW)", "conv_mfma.hip:414", V + "test_conv32_at_the_persistent_grid_switch[1024-4]"),
+    _v("k_up32<4, true>", "dvae_conv4s2_dgrad, dvae_conv32_up", "Hs == 4, mask", "conv_mfma.hip:413", V + "test_conv32_at_the_persistent_grid_switch[1025-4]"),
+    _v("k_down32<4, false>", "dvae_conv4s2_fwd, dvae_conv32_down", "Hs == 4, no mask (output NHWC or NCHW)", "conv_mfma.hip:396", V + "test_conv32_at_the_persistent_grid_switch[1024-4]"),
+    _v("k_down32<4, true>", "dvae_convT4s2_dgrad, dvae_conv32_down", "Hs == 4, mask", "conv_mfma.hip:395", V + "test_conv32_at_the_persistent_grid_switch[1025-4]"),
+    _v("k_wgrad32<16>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "Hs == 16 with the small side NCHW or DVAE_WGRAD_WS=0", "conv_mfma.hip:433", None,
+       "run_wgrad (capi.hip:54) passes small_nchw = 1 for Hs == 4 only, and " + _DEBUG_ONLY % "DVAE_WGRAD_WS"),
+    _v("k_wgrad32<8>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "Hs == 8 with the small side NCHW or DVAE_WGRAD_WS=0", "conv_mfma.hip:433", None,
+       "run_wgrad (capi.hip:54) passes small_nchw = 1 for Hs == 4 only, and " + _DEBUG_ONLY % "DVAE_WGRAD_WS"),
+    _v("k_wgrad32<4>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "Hs == 4 (small side NHWC or NCHW)", "conv_mfma.hip:433", V + "test_wgrad32_at_the_reduction_form_switch[767-4-True-False]"),
+    _v("k_wgrad32_reduce<false>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "32 <-> 32 channels, N < WGR_LEAN_MIN_IMAGES = 768", "conv_mfma.hip:375", V + "test_wgrad32_at_the_reduction_form_switch[767-8-False-False]"),
+    _v("k_wgrad32_reduce<true>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "32 <-> 32 channels, N >= 768", "conv_mfma.hip:373", V + "test_wgrad32_at_the_reduction_form_switch[768-8-False-False]"),
+    # ---- conv_thin.hip (C = 1 / 3 <-> 32 channels, 64x64 <-> 32x32)
+    _v("k_up_thin<1, false, float>", "dvae_convT4s2_fwd", "Cb == 1, NHWC -> NCHW, no mask", "conv_thin.hip:697", K + "test_convT_fwd_dgrad_wgrad[3-32-1-0-3-False]"),
+    _v("k_up_thin<1, true, float>", "dvae_convT4s2_sigmoid_recon_fwd", "Cb == 1", "conv_thin.hip:709", K + "test_convT_sigmoid_recon_fused[3-1-32-gaussian-False]"),
+    _v("k_up_thin<1, true, unsigned char>", "dvae_convT4s2_sigmoid_recon_fwd_u8", "Cb == 1", "conv_thin.hip:734", U8 + "test_u8_kernels_equal_fp32_kernels_bitwise[3-1]"),
+    _v("k_up_thin<3, false, float>", "dvae_convT4s2_fwd", "Cb == 3, NHWC -> NCHW, no mask", "conv_thin.hip:698", K + "test_convT_fwd_dgrad_wgrad[5-32-3-0-3-False]"),
+    _v("k_up_thin<3, true, float>", "dvae_convT4s2_sigmoid_recon_fwd", "Cb == 3", "conv_thin.hip:710", K + "test_convT_sigmoid_recon_fused[5-3-32-bernoulli-False]"),
+    _v("k_up_thin<3, true, unsigned char>", "dvae_convT4s2_sigmoid_recon_fwd_u8", "Cb == 3", "conv_thin.hip:735", U8 + "test_u8_kernels_equal_fp32_kernels_bitwise[5-3]"),
+    _v("k_down_thin<1, 0, float>", "dvae_conv4s2_fwd", "Cb == 1, N < 192, no mask", "conv_thin.hip:684", V + "test_thin_ends_at_the_wave_specialised_switch[191-1]"),
+    _v("k_down_thin<1, 0, unsigned char>", "dvae_conv4s2_fwd_u8", "Cin == 1", "conv_thin.hip:721", U8 + "test_u8_kernels_equal_fp32_kernels_bitwise[3-1]"),
+    _v("k_down_thin<1, 1, float>", "dvae_convT4s2_dgrad", "Cb == 1, fp32 mask (any N)", "conv_thin.hip:684", V + "test_thin_ends_at_the_wave_specialised_switch[192-1]"),
+    _v("k_down_thin<1, 2, float>", "dvae_convT3_dgrad_bits", "Cout == 1, N < 192", "conv_thin.hip:684", V + "test_thin_ends_at_the_wave_specialised_switch[191-1]"),
+    _v("k_down_thin<1, 3, float>", "dvae_conv1_fwd_bits", "Cin == 1, fp32 input, N < 192", "conv_thin.hip:684", V + "test_thin_ends_at_the_wave_specialised_switch[191-1]"),
+    _v("k_down_thin<1, 3, unsigned char>", "dvae_conv1_fwd_bits", "Cin == 1, uint8 input", "conv_thin.hip:721", MB + "test_conv1_forward_emits_the_bit_plane[9-1-True]"),
+    _v("k_down_thin<3, 0, float>", "dvae_conv4s2_fwd", "Cb == 3, N < 192, no mask", "conv_thin.hip:686", V + "test_thin_ends_at_the_wave_specialised_switch[191-3]"),
+    _v("k_down_thin<3, 0, unsigned char>", "dvae_conv4s2_fwd_u8", "Cin == 3", "conv_thin.hip:722", U8 + "test_u8_kernels_equal_fp32_kernels_bitwise[5-3]"),
+    _v("k_down_thin<3, 1, float>", "dvae_convT4s2_dgrad", "Cb == 3, fp32 mask (any N)", "conv_thin.hip:686", V + "test_thin_ends_at_the_wave_specialised_switch[192-3]"),
+    _v("k_down_thin<3, 2, float>", "dvae_convT3_dgrad_bits", "Cout == 3, N < 192", "conv_thin.hip:686", V + "test_thin_ends_at_the_wave_specialised_switch[191-3]"),
+    _v("k_down_thin<3, 3, float>", "dvae_conv1_fwd_bits", "Cin == 3, fp32 input, N < 192", "conv_thin.hip:686", V + "test_thin_ends_at_the_wave_specialised_switch[191-3]"),
+    _v("k_down_thin<3, 3, unsigned char>", "dvae_conv1_fwd_bits", "Cin == 3, uint8 input", "conv_thin.hip:722", MB + "test_conv1_forward_emits_the_bit_plane[520-3-True]"),
+    _v("k_up_thin_pk<1, false, float>", "dvae_convT3_fwd_staged", "C == 1, no target", "conv_thin.hip:548", FC + "test_convT3_forward_on_staged_pair_records[3-1]"),
+    _v("k_up_thin_pk<1, true, float>", "dvae_convT3_fwd_staged", "C == 1, fp32 target", "conv_thin.hip:550", FC + "test_convT3_forward_on_staged_pair_records[3-1]"),
+    _v("k_up_thin_pk<1, true, unsigned char>", "dvae_convT3_fwd_staged", "C == 1, uint8 target", "conv_thin.hip:549", FC + "test_convT3_forward_on_staged_pair_records[3-1]"),
+    _v("k_up_thin_pk<3, false, float>", "dvae_convT3_fwd_staged", "C == 3, no target, recon / g / fp32 target not 16-byte or uint8 target not 4-byte aligned (k_up_thin_mm declines)", "conv_thin.hip:548", V + "test_convT3_staged_falls_back_to_the_packed_fma_kernel"),
+    _v("k_up_thin_pk<3, true, float>", "dvae_convT3_fwd_staged", "C == 3, fp32 target, recon / g / fp32 target not 16-byte or uint8 target not 4-byte aligned (k_up_thin_mm declines)", "conv_thin.hip:550", V + "test_convT3_staged_falls_back_to_the_packed_fma_kernel"),
+    _v("k_up_thin_pk<3, true, unsigned char>", "dvae_convT3_fwd_staged", "C == 3, uint8 target, recon / g / fp32 target not 16-byte or uint8 target not 4-byte aligned (k_up_thin_mm declines)", "conv_thin.hip:549", V + "test_convT3_staged_falls_back_to_the_packed_fma_kernel"),
+    _v("k_wgrad_thin<1, float>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "Cb == 1, N < 192", "conv_thin.hip:750", V + "test_thin_ends_at_the_wave_specialised_switch[191-1]"),
+    _v("k_wgrad_thin<1, unsigned char>", "dvae_conv4s2_wgrad_u8", "Cin == 1", "conv_thin.hip:750", U8 + "test_u8_kernels_equal_fp32_kernels_bitwise[3-1]"),
+    _v("k_wgrad_thin<3, float>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "Cb == 3, N < 192", "conv_thin.hip:750", V + "test_thin_ends_at_the_wave_specialised_switch[191-3]"),
+    _v("k_wgrad_thin<3, unsigned char>", "dvae_conv4s2_wgrad_u8", "Cin == 3", "conv_thin.hip:750", U8 + "test_u8_kernels_equal_fp32_kernels_bitwise[5-3]"),
+    _v("k_wgrad_thin_reduce<1>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad, dvae_conv4s2_wgrad_u8", "Cb == 1, behind either partial kernel", "conv_thin.hip:743", V + "test_thin_ends_at_the_wave_specialised_switch[192-1]"),
+    _v("k_wgrad_thin_reduce<3>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad, dvae_conv4s2_wgrad_u8", "Cb == 3, behind either partial kernel", "conv_thin.hip:743", V + "test_thin_ends_at_the_wave_specialised_switch[192-3]"),
+    # ---- conv_thin_ws.hip (N >= 192, 16-byte aligned buffers)
+    _v("k_down_thin_ws<1, 0, 0>", "dvae_conv4s2_fwd", "Cb == 1, N >= 192, no mask", "conv_thin_ws.hip:368", V + "test_thin_ends_at_the_wave_specialised_switch[192-1]"),
+    _v("k_down_thin_ws<1, 2, 0>", "dvae_convT3_dgrad_bits", "Cout == 1, N >= 192", "conv_thin_ws.hip:368", V + "test_thin_ends_at_the_wave_specialised_switch[192-1]"),
+    _v("k_down_thin_ws<1, 3, 0>", "dvae_conv1_fwd_bits", "Cin == 1, fp32 input, N >= 192", "conv_thin_ws.hip:368", V + "test_thin_ends_at_the_wave_specialised_switch[192-1]"),
+    _v("k_down_thin_ws<3, 0, 0>", "dvae_conv4s2_fwd", "Cb == 3, N >= 192, no mask", "conv_thin_ws.hip:370", V + "test_thin_ends_at_the_wave_specialised_switch[192-3]"),
+    _v("k_down_thin_ws<3, 2, 0>", "dvae_convT3_dgrad_bits", "Cout == 3, N >= 192", "conv_thin_ws.hip:370", V + "test_thin_ends_at_the_wave_specialised_switch[192-3]"),
+    _v("k_down_thin_ws<3, 3, 0>", "dvae_conv1_fwd_bits", "Cin == 3, fp32 input, N >= 192", "conv_thin_ws.hip:370", V + "test_thin_ends_at_the_wave_specialised_switch[192-3]"),
+    _v("k_wgrad_thin_ws<1, false, 0>", "dvae_conv4s2_wgrad", "Cb == 1, N >= 192, bias from the 32-channel side", "conv_thin_ws.hip:640", V + "test_thin_ends_at_the_wave_specialised_switch[192-1]"),
+    _v("k_wgrad_thin_ws<1, true, 0>", "dvae_convT4s2_wgrad", "Cb == 1, N >= 192, bias from the thin side", "conv_thin_ws.hip:640", V + "test_thin_ends_at_the_wave_specialised_switch[192-1]"),
+    _v("k_wgrad_thin_ws<3, false, 0>", "dvae_conv4s2_wgrad", "Cb == 3, N >= 192, bias from the 32-channel side", "conv_thin_ws.hip:641", V + "test_thin_ends_at_the_wave_specialised_switch[192-3]"),
+    _v("k_wgrad_thin_ws<3, true, 0>", "dvae_convT4s2_wgrad", "Cb == 3, N >= 192, bias from the thin side", "conv_thin_ws.hip:641", V + "test_thin_ends_at_the_wave_specialised_switch[192-3]"),
+    # ---- conv_up_thin_mm.hip (dvae_convT3_fwd_staged, C == 3, 16-byte aligned buffers)
+    _v("k_up_thin_mm<false, 0, float>", "dvae_convT3_fwd_staged", "C == 3, no target", "conv_up_thin_mm.hip:288", FC + "test_convT3_forward_on_staged_pair_records[3-3]"),
+    _v("k_up_thin_mm<true, 0, float>", "dvae_convT3_fwd_staged", "C == 3, fp32 target, bernoulli", "conv_up_thin_mm.hip:294", FC + "test_convT3_forward_on_staged_pair_records[3-3]"),
+    _v("k_up_thin_mm<true, 0, unsigned char>", "dvae_convT3_fwd_staged", "C == 3, uint8 target, bernoulli", "conv_up_thin_mm.hip:290", FC + "test_convT3_forward_on_staged_pair_records[3-3]"),
+    _v("k_up_thin_mm<true, 1, float>", "dvae_convT3_fwd_staged", "C == 3, fp32 target, gaussian", "conv_up_thin_mm.hip:295", FC + "test_convT3_forward_on_staged_pair_records[3-3]"),
+    _v("k_up_thin_mm<true, 1, unsigned char>", "dvae_convT3_fwd_staged", "C == 3, uint8 target, gaussian", "conv_up_thin_mm.hip:291", FC + "test_convT3_forward_on_staged_pair_records[3-3]"),
+    _v("k_up_thin_mm<true, 2, float>", "dvae_convT3_fwd_staged", "C == 3, fp32 target, laplace", "conv_up_thin_mm.hip:296", FC + "test_convT3_forward_on_staged_pair_records[3-3]"),
+    _v("k_up_thin_mm<true, 2, unsigned char>", "dvae_convT3_fwd_staged", "C == 3, uint8 target, laplace", "conv_up_thin_mm.hip:292", FC + "test_convT3_forward_on_staged_pair_records[3-3]"),
+    # ---- conv_up_ws.hip (32 <-> 32 channels, NHWC, Hs in {16, 8})
+    _v("k_up32ws<16, 0, false>", "dvae_convT4s2_fwd, dvae_conv32_up", "Hs == 16, no mask", "conv_up_ws.hip:374", V + "test_conv32_at_the_persistent_grid_switch[64-16]"),
+    _v("k_up32ws<16, 0, true>", "dvae_conv32_up_bits", "out_bits != NULL (ReLU forward that emits the bit plane)", "conv_up_ws.hip:369", MB + "test_conv32_up_bits_forward_and_input_gradient[300]"),
+    _v("k_up32ws<16, 1, false>", "dvae_conv4s2_dgrad, dvae_conv32_up", "Hs == 16, fp32 mask", "conv_up_ws.hip:372", V + "test_conv32_at_the_persistent_grid_switch[65-16]"),
+    _v("k_up32ws<16, 2, false>", "dvae_conv32_up_bits", "mask_bits != NULL", "conv_up_ws.hip:366", MB + "test_conv32_up_bits_forward_and_input_gradient[300]"),
+    _v("k_up32ws<8, 0, false>", "dvae_convT4s2_fwd, dvae_conv32_up", "Hs == 8, no mask", "conv_up_ws.hip:374", V + "test_conv32_at_the_persistent_grid_switch[256-8]"),
+    _v("k_up32ws<8, 1, false>", "dvae_conv4s2_dgrad, dvae_conv32_up", "Hs == 8, fp32 mask", "conv_up_ws.hip:372", V + "test_conv32_at_the_persistent_grid_switch[257-8]"),
+    # ---- conv_wgrad_ws.hip
+    _v("k_wgrad32ws<16>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "32 <-> 32 channels, NHWC, Hs == 16", "conv_wgrad_ws.hip:319", V + "test_conv_wgrad32_at_the_grid_cap[129-16]"),
+    _v("k_wgrad32ws<8>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "32 <-> 32 channels, NHWC, Hs == 8", "conv_wgrad_ws.hip:319", V + "test_conv_wgrad32_at_the_grid_cap[129-8]"),
+    # ---- gemm_dma.hip (try_gdma: Kc >= 256, N >= 128, aligned; tile from ceil(M / tile) * ceil(N / 64))
+    _v("k_gdma<128, 64, 32, 4, 1, false, 0>", "dvae_linear_fwd", "ceil(M / 128) * cols64 >= 224", "gemm_dma.hip:508", V + "test_discriminator_linear_at_the_tile_switches[1665]"),
+    _v("k_gdma<128, 64, 32, 4, 1, true, 0>", "dvae_linear_dgrad", "ceil(M / 128) * cols64 >= 224", "gemm_dma.hip:508", V + "test_discriminator_linear_at_the_tile_switches[1665]"),
+    _v("k_gdma<32, 32, 64, 3, 4, false, 0>", "dvae_linear_fwd", "ceil(M / 64) * cols64 < 192", "gemm_dma.hip:510", V + "test_discriminator_linear_at_the_tile_switches[704]"),
+    _v("k_gdma<32, 32, 64, 3, 4, true, 0>", "dvae_linear_dgrad", "ceil(M / 64) * cols64 < 192", "gemm_dma.hip:510", V + "test_discriminator_linear_at_the_tile_switches[704]"),
+    _v("k_gdma<64, 64, 64, 3, 1, false, 0>", "dvae_linear_fwd", "ceil(M / 64) * cols64 >= 192, ceil(M / 128) * cols64 < 224", "gemm_dma.hip:509", V + "test_discriminator_linear_at_the_tile_switches[705]"),
+    _v("k_gdma<64, 64, 64, 3, 1, true, 0>", "dvae_linear_dgrad", "ceil(M / 64) * cols64 >= 192, ceil(M / 128) * cols64 < 224", "gemm_dma.hip:509", V + "test_discriminator_linear_at_the_tile_switches[1664]"),
+    _v("k_gdma_wg<64, 3>", "dvae_linear_wgrad", "M >= 64, N % 4 == K % 4 == 0, >= 128 output tiles of 64x64", "gemm_dma.hip:527", V + "test_discriminator_linear_at_the_tile_switches[64]"),
+    # ---- latent_wide.hip (D > DVAE_MAX_D = 16)
+    _v("k_tcw_joint", "dvae_btcvae_fwd", "D > 16", "latent_wide.hip:240", WL + "test_btcvae_fwd_bwd_wide[4-100-True-17]"),
+    _v("k_kl_cols_wide", "dvae_reparam_kl_fwd", "D > 16, kl_dim != NULL", "latent_wide.hip:231", WL + "test_reparam_kl_wide[2-17]"),
+    _v("k_reparam_wide", "dvae_reparam_kl_fwd", "D > 16", "latent_wide.hip:228", WL + "test_reparam_kl_wide[2-17]"),
+    _v("k_tcw_bwd_cols", "dvae_btcvae_bwd", "D > 16", "latent_wide.hip:256", WL + "test_btcvae_fwd_bwd_wide[4-100-True-17]"),
+    _v("k_tcw_bwd_rows", "dvae_btcvae_bwd", "D > 16", "latent_wide.hip:253", WL + "test_btcvae_fwd_bwd_wide[4-100-True-17]"),
+    _v("k_tcw_rowstats", "dvae_btcvae_fwd", "D > 16", "latent_wide.hip:242", WL + "test_btcvae_fwd_bwd_wide[4-100-True-17]"),
+    # ---- linear.hip (try_fc32: contraction <= 512 and < 512 output tiles of 64x64; KP = the contraction rounded up)
+    _v("k_fc32<128, false, 0>", "dvae_linear_fwd", "64 < K <= 128, K % 4 == 0", "linear.hip:429", V + "test_linear_at_the_contraction_length_switches[128]"),
+    _v("k_fc32<128, true, 0>", "dvae_linear_dgrad", "64 < N <= 128, N % 4 == K % 4 == 0", "linear.hip:429", V + "test_linear_at_the_contraction_length_switches[68]"),
+    _v("k_fc32<128, true, 2>", "dvae_linear_dgrad", "64 < N <= 128, K % 4 != 0", "linear.hip:429", V + "test_linear_dgrad_into_a_narrow_unaligned_output[128]"),
+    _v("k_fc32<256, false, 0>", "dvae_linear_fwd", "128 < K <= 256, K % 4 == 0", "linear.hip:430", V + "test_linear_at_the_contraction_length_switches[132]"),
+    _v("k_fc32<256, true, 0>", "dvae_linear_dgrad", "128 < N <= 256, N % 4 == K % 4 == 0", "linear.hip:430", V + "test_linear_at_the_contraction_length_switches[256]"),
+    _v("k_fc32<256, true, 2>", "dvae_linear_dgrad", "128 < N <= 256, K % 4 != 0", "linear.hip:430", V + "test_linear_dgrad_into_a_narrow_unaligned_output[256]"),
+    _v("k_fc32<32, false, 0>", "dvae_linear_fwd", "K <= 32, K % 4 == 0, aligned", "linear.hip:427", V + "test_linear_at_the_contraction_length_switches[32]"),
+    _v("k_fc32<32, false, 1>", "dvae_linear_fwd", "K <= 32, K % 4 != 0 or unaligned", "linear.hip:416", V + "test_linear_dgrad_into_a_narrow_unaligned_output[32]"),
+    _v("k_fc32<32, true, 0>", "dvae_linear_dgrad", "N <= 32, N % 4 == K % 4 == 0", "linear.hip:427", V + "test_linear_at_the_contraction_length_switches[32]"),
+    _v("k_fc32<32, true, 2>", "dvae_linear_dgrad", "N <= 32, K % 4 != 0", "linear.hip:427", V + "test_linear_dgrad_into_a_narrow_unaligned_output[32]"),
+    _v("k_fc32<512, false, 0>", "dvae_linear_fwd", "256 < K <= 512, K % 4 == 0", "linear.hip:431", V + "test_linear_at_the_contraction_length_switches[260]"),
+    _v("k_fc32<512, true, 0>", "dvae_linear_dgrad", "256 < N <= 512, N % 4 == K % 4 == 0", "linear.hip:431", V + "test_linear_at_the_contraction_length_switches[512]"),
+    _v("k_fc32<512, true, 2>", "dvae_linear_dgrad", "256 < N <= 512, K % 4 != 0", "linear.hip:431", V + "test_linear_dgrad_into_a_narrow_unaligned_output[512]"),
+    _v("k_fc32<64, false, 0>", "dvae_linear_fwd", "32 < K <= 64, K % 4 == 0", "linear.hip:428", V + "test_linear_at_the_contraction_length_switches[36]"),
+    _v("k_fc32<64, true, 0>", "dvae_linear_dgrad", "32 < N <= 64, N % 4 == K % 4 == 0", "linear.hip:428", V + "test_linear_at_the_contraction_length_switches[64]"),
+    _v("k_fc32<64, true, 2>", "dvae_linear_dgrad", "32 < N <= 64, K % 4 != 0", "linear.hip:428", V + "test_linear_dgrad_into_a_narrow_unaligned_output[64]"),
+    _v("k_gemm<false, true>", "dvae_linear_wgrad", "M > 4096 or >= 512 output tiles, and not k_gdma_wg", "linear.hip:721", V + "test_linear_wgrad_at_the_batch_switches[4100]"),
+    _v("k_gemm<true, false>", "dvae_linear_fwd", "no other forward kernel applies (>= 512 output tiles with K < 256; K % 4 != 0 above 32)", "linear.hip:643", V + "test_linear_at_the_output_tile_count_switch[2048-64-1024-parts1]"),
+    _v("k_gemm<true, true>", "dvae_linear_dgrad", "no other input-gradient kernel applies (N > 512 into K < 128 columns; >= 512 output tiles)", "linear.hip:682", V + "test_linear_at_the_output_tile_count_switch[2048-1024-64-parts3]"),
+    _v("k_fcw32<256>", "dvae_linear_wgrad", "64 < M <= 4096, < 512 output tiles", "linear.hip:549", V + "test_linear_wgrad_at_the_batch_switches[65]"),
+    _v("k_fcw32<64>", "dvae_linear_wgrad", "M <= 64, < 512 output tiles", "linear.hip:541", V + "test_linear_wgrad_at_the_batch_switches[64]"),
+    _v("k_gemm32<false, false>", "dvae_linear_fwd, dvae_linear_dgrad, dvae_linear_wgrad", "use_small() and an unaligned contraction", "linear.hip:635", None, _SMALL_ONLY),
+    _v("k_gemm32<true, false>", "dvae_linear_dgrad", "use_small(), N % 4 == 0", "linear.hip:671", None, _SMALL_ONLY),
+    _v("k_gemm32<true, true>", "dvae_linear_fwd", "K > 512, K % 4 == 0, < 192 output tiles, N < 128 (not k_gdma)", "linear.hip:632", V + "test_linear_outside_the_lds_resident_kernels[40-1000-36]"),
+    _v("k_splitk_reduce", "dvae_linear_wgrad", "k_gemm<false, true> with a workspace and S > 1 contraction slices", "linear.hip:734", V + "test_linear_wgrad_at_the_batch_switches[4100]"),
+    _v("k_splitk_epilogue", "dvae_linear_fwd, dvae_linear_dgrad", "k_gemm<true, *> with a workspace and S > 1 contraction slices", "linear.hip:654", V + "test_linear_outside_the_lds_resident_kernels[40-301-36]"),
+    # ---- linear_grouped.hip
+    _v("k_fcw_grouped<128>", "dvae_linear_wgrad_grouped", "64 < max M <= 128", "linear_grouped.hip:166", V + "test_linear_wgrad_grouped_past_its_slab_switches[65]"),
+    _v("k_fcw_grouped<256>", "dvae_linear_wgrad_grouped", "max M > 128", "linear_grouped.hip:167", V + "test_linear_wgrad_grouped_past_its_slab_switches[129]"),
+    _v("k_fcw_grouped<64>", "dvae_linear_wgrad_grouped", "max M <= 64", "linear_grouped.hip:165", K + "test_linear_wgrad_grouped[64]"),
+    # ---- linear_narrow.hip
+    _v("k_narrow_out_fwd", "dvae_linear_fwd", "N <= 8, K >= 256, K % 4 == 0, aligned", "linear_narrow.hip:89", V + "test_narrow_output_linear_at_its_minimum_contraction[256]"),
+    _v("k_narrow_out_dgrad", "dvae_linear_dgrad", "N <= 8, K >= 256, K % 4 == 0, aligned", "linear_narrow.hip:102", V + "test_narrow_output_linear_at_its_minimum_contraction[256]"),
+    # ---- loglik.hip
+    _v("k_iw_loglik", "dvae_iw_loglik", "always", "loglik.hip:177", "tests/test_gpu_loglik.py::test_log_likelihood_vs_fp64_restatement[img0-10-37-64-bernoulli-False]"),
+    _v("k_recon_rows", "dvae_recon_rows", "always", "loglik.hip:158", "tests/test_gpu_loglik.py::test_recon_rows_vs_fp64_oracle[bernoulli-False-img0-1]"),
+    _v("k_recon_rows_finish", "dvae_recon_rows", "more than one slice of a row", "loglik.hip:163", "tests/test_gpu_loglik.py::test_recon_rows_vs_fp64_oracle[bernoulli-False-img1-1]"),
+    # ---- loss.hip
+    _v("k_add", "dvae_add", "always", "loss.hip:895", FC + "test_event_slots_order_a_late_consumer_after_marked_work"),
+    _v("k_axpby", "dvae_axpby", "always", "loss.hip:902", K + "test_data_parallel_glue_kernels"),
+    _v("k_set_coef", "dvae_set_coef", "always", "loss.hip:888", MC + "[set_coef]"),
+    _v("k_loss_pack", "dvae_loss_pack", "always", "loss.hip:827", K + "test_loss_epilogue_equals_pack_then_finalize[0-8]"),
+    _v("k_u8_to_f32", "dvae_u8_to_f32", "always", "loss.hip:880", U8 + "test_u8_to_f32_is_totensor"),
+    _v("k_btcvae_fwd<0>", "dvae_btcvae_fwd", "D <= 16, D != 10", "loss.hip:777", V + "test_btcvae_bwd_at_the_row_switch[513-6-True]"),
+    _v("k_btcvae_fwd<10>", "dvae_btcvae_fwd", "D == 10", "loss.hip:776", V + "test_btcvae_bwd_at_the_row_switch[513-10-True]"),
+    _v("k_recon_loss", "dvae_recon_loss, dvae_convT4s2_sigmoid_recon_fwd (two-pass shapes)", "always", "loss.hip:761", K + "test_recon_loss[bernoulli]"),
+    _v("k_reduce_sum", "dvae_reduce_sum", "always", "loss.hip:873", MC + "[reduce_sum-n7]"),
+    _v("k_swap_outer", "dvae_swap_outer", "always", "loss.hip:908", K + "test_data_parallel_glue_kernels"),
+    _v("k_btcvae_prep", "dvae_btcvae_fwd", "always", "loss.hip:773", V + "test_btcvae_bwd_at_the_row_switch[512-10-True]"),
+    _v("k_disc_losses", "dvae_disc_losses", "always", "loss.hip:820", K + "test_permute_dims_and_disc_losses"),
+    _v("k_sigmoid_bwd", "dvae_sigmoid_bwd", "always", "loss.hip:860", K + "test_recon_loss[bernoulli]"),
+    _v("k_permute_dims", "dvae_permute_dims", "always", "loss.hip:813", K + "test_permute_dims_and_disc_losses"),
+    _v("k_btcvae_bwd_wg<0>", "dvae_btcvae_bwd", "Bl <= 512, D <= 16, D != 10", "loss.hip:793", V + "test_btcvae_bwd_at_the_row_switch[512-6-True]"),
+    _v("k_btcvae_bwd_wg<10>", "dvae_btcvae_bwd", "Bl <= 512, D == 10", "loss.hip:791", V + "test_btcvae_bwd_at_the_row_switch[512-10-True]"),
+    _v("k_kl_normal_bwd", "dvae_kl_normal_bwd", "always", "loss.hip:867", MC + "[kl_normal_bwd-B7-D1]"),
+    _v("k_loss_epilogue", "dvae_loss_epilogue", "always", "loss.hip:846", K + "test_loss_epilogue_equals_pack_then_finalize[0-8]"),
+    _v("k_loss_finalize", "dvae_loss_finalize", "always", "loss.hip:853", K + "test_loss_epilogue_equals_pack_then_finalize[0-8]"),
+    _v("k_reparam_kl_bwd", "dvae_reparam_kl_bwd", "always", "loss.hip:753", K + "test_reparam_kl[8]"),
+    _v("k_reparam_kl_fwd", "dvae_reparam_kl_fwd", "D <= 16", "loss.hip:739", V + "test_reparam_kl_at_the_partial_block_switches[257]"),
+    _v("k_btcvae_bwd_cols<0>", "dvae_btcvae_bwd", "Bl > 512, D <= 16, D != 10", "loss.hip:805", V + "test_btcvae_bwd_at_the_row_switch[513-6-True]"),
+    _v("k_btcvae_bwd_cols<10>", "dvae_btcvae_bwd", "Bl > 512, D == 10", "loss.hip:803", V + "test_btcvae_bwd_at_the_row_switch[513-10-True]"),
+    _v("k_btcvae_bwd_rows<0>", "dvae_btcvae_bwd", "Bl > 512, D <= 16, D != 10", "loss.hip:800", V + "test_btcvae_bwd_at_the_row_switch[513-6-True]"),
+    _v("k_btcvae_bwd_rows<10>", "dvae_btcvae_bwd", "Bl > 512, D == 10", "loss.hip:798", V + "test_btcvae_bwd_at_the_row_switch[513-10-True]"),
+    _v("k_reparam_kl_finish", "dvae_reparam_kl_fwd, dvae_kl_finish", "kl_dim and coef given", "loss.hip:742", V + "test_reparam_kl_at_the_partial_block_switches[257]"),
+    # ---- metrics.hip
+    _v("k_entropy_lse", "dvae_latent_entropy", "always", "metrics.hip:119", "tests/test_gpu_metrics.py::test_entropy_kernel_vs_oracle[17-3-5]"),
+    _v("k_entropy_prep", "dvae_latent_entropy", "always", "metrics.hip:117", "tests/test_gpu_metrics.py::test_entropy_kernel_vs_oracle[17-3-5]"),
+    _v("k_entropy_finish", "dvae_latent_entropy", "always", "metrics.hip:121", "tests/test_gpu_metrics.py::test_entropy_kernel_vs_oracle[17-3-5]"),
+    # ---- stage.hip, viz.hip
+    _v("k_stage_weights", "dvae_stage_weights", "at least one image or the coefficients", "stage.hip:137", FC + "test_stage_weights_layouts_and_coefficients"),
+    _v("k_image_grid_u8", "dvae_image_grid_u8", "always", "viz.hip:111", "tests/test_gpu_visualize.py::test_grid_kernel_matches_make_grid[3-32]"),
+    # ---- fc_chain.hip (<DEPTH = 8, KS = 2, RG, CONV>: RG = 1 up to 1024 rows, 2 above; CONV = the conv ends in the launch)
+    _v("k_fc_chain_bwd<8, 2, 1, false>", "dvae_fc_chain_bwd", "n <= 1024, no conv ends", "fc_chain.hip:788", V + "test_fc_chain_at_the_row_group_switch[1024-10-False]"),
+    _v("k_fc_chain_bwd<8, 2, 1, true>", "dvae_fc_chain_bwd", "n <= 1024, convT_gout given", "fc_chain.hip:783", V + "test_fc_chain_at_the_row_group_switch[1024-10-True]"),
+    _v("k_fc_chain_bwd<8, 2, 2, false>", "dvae_fc_chain_bwd", "n > 1024, no conv ends", "fc_chain.hip:788", V + "test_fc_chain_at_the_row_group_switch[1025-10-False]"),
+    _v("k_fc_chain_bwd<8, 2, 2, true>", "dvae_fc_chain_bwd", "n > 1024, convT_gout given", "fc_chain.hip:783", V + "test_fc_chain_at_the_row_group_switch[1025-10-True]"),
+    _v("k_fc_chain_fwd<8, 2, 1, false>", "dvae_fc_chain_fwd", "n_enc <= 1024, no conv ends", "fc_chain.hip:768", V + "test_fc_chain_at_the_row_group_switch[1024-10-False]"),
+    _v("k_fc_chain_fwd<8, 2, 1, true>", "dvae_fc_chain_fwd", "n_enc <= 1024, conv_in given", "fc_chain.hip:763", V + "test_fc_chain_at_the_row_group_switch[1024-10-True]"),
+    _v("k_fc_chain_fwd<8, 2, 2, false>", "dvae_fc_chain_fwd", "n_enc > 1024, no conv ends", "fc_chain.hip:768", V + "test_fc_chain_at_the_row_group_switch[1025-10-False]"),
+    _v("k_fc_chain_fwd<8, 2, 2, true>", "dvae_fc_chain_fwd", "n_enc > 1024, conv_in given", "fc_chain.hip:763", V + "test_fc_chain_at_the_row_group_switch[1025-10-True]"),
+]
+
+
+def _s(launcher, variable, threshold, where, below, below_test, above, above_test):
+    return Switch(launcher, variable, threshold, where, below, below_test, above, above_test)
+
+
+_BTC = V + "test_btcvae_bwd_at_the_row_switch"
+_THIN = V + "test_thin_ends_at_the_wave_specialised_switch"
+_KC = V + "test_linear_at_the_contraction_length_switches"
+_DISC = V + "test_discriminator_linear_at_the_tile_switches"
+_TILES = V + "test_linear_at_the_output_tile_count_switch"
+_GRID = V + "test_conv32_at_the_persistent_grid_switch"
+_CAP = V + "test_conv_wgrad32_at_the_grid_cap"
+_RED = V + "test_wgrad32_at_the_reduction_form_switch"
+_CHAIN = V + "test_fc_chain_at_the_row_group_switch"
+_SMALL = V + "test_linear_forward_at_the_small_kernel_limits"
+_SPLIT = V + "test_linear_at_the_contraction_slice_switches"
+_RGRID = V + "test_linear_split_contraction_at_the_reduction_grid_cap"
+_DMAMIN = V + "test_linear_at_the_dma_kernel_minima"
+_ELT = V + "test_elementwise_kernels_at_their_grid_caps"
+
+SWITCHES = [
+    _s("launch_btcvae_bwd", "Bl", "BTC_WG_MAX_ROWS = 512", "loss.hip:790", "Bl = 512, D = 10", _BTC + "[512-10-True]", "Bl = 513, D = 10", _BTC + "[513-10-True]"),
+    _s("launch_btcvae_bwd", "Bl (run-time D)", "BTC_WG_MAX_ROWS = 512", "loss.hip:790", "Bl = 512, D = 6", _BTC + "[512-6-True]", "Bl = 513, D = 6", _BTC + "[513-6-True]"),
+    _s("launch_btcvae_bwd", "Bl of a row shard (Bl < Bg)", "BTC_WG_MAX_ROWS = 512", "loss.hip:790", "Bg = 1100, rows [0, 500)",
+       V + "test_btcvae_bwd_sharded_with_more_than_512_local_rows[0-500]", "Bg = 1100, rows [500, 1100)",
+       V + "test_btcvae_bwd_sharded_with_more_than_512_local_rows[500-600]"),
+    _s("reparam_kl_blocks", "ceil(B / 256)", "1 | 2 blocks", "loss.hip:833", "B = 256", V + "test_reparam_kl_at_the_partial_block_switches[256]",
+       "B = 257", V + "test_reparam_kl_at_the_partial_block_switches[257]"),
+    _s("reparam_kl_blocks", "ceil(B / 256)", "RK_BLOCKS = 64", "loss.hip:834", "B = 16384", V + "test_reparam_kl_at_the_partial_block_switches[16384]",
+       "B = 16385", V + "test_reparam_kl_at_the_partial_block_switches[16385]"),
+    _s("launch_down_thin_ws", "N", "192", "conv_thin_ws.hip:323", "N = 191, C = 1", _THIN + "[191-1]", "N = 192, C = 1", _THIN + "[192-1]"),
+    _s("launch_down_thin_ws", "N (3 channels)", "192", "conv_thin_ws.hip:323", "N = 191, C = 3", _THIN + "[191-3]", "N = 192, C = 3", _THIN + "[192-3]"),
+    _s("launch_wgrad_thin_ws", "N", "192", "conv_thin_ws.hip:624", "N = 191", _THIN + "[191-3]", "N = 192", _THIN + "[192-3]"),
+    _s("launch_wgrad_ws_t", "N (grid cap on)", "128", "conv_wgrad_ws.hip:305", "N = 128, HS 16", _CAP + "[128-16]", "N = 129, HS 16", _CAP + "[129-16]"),
+    _s("launch_wgrad_ws_t", "N (grid cap off)", "320", "conv_wgrad_ws.hip:305", "N = 320, HS 16", _CAP + "[320-16]", "N = 321, HS 16", _CAP + "[321-16]"),
+    _s("launch_wgrad_ws_t", "N (grid cap on, HS 8)", "128", "conv_wgrad_ws.hip:305", "N = 128, HS 8", _CAP + "[128-8]", "N = 129, HS 8", _CAP + "[129-8]"),
+    _s("launch_wgrad_ws_t", "N (grid cap off, HS 8)", "320", "conv_wgrad_ws.hip:305", "N = 320, HS 8", _CAP + "[320-8]", "N = 321, HS 8", _CAP + "[321-8]"),
+    _s("launch_wgrad32_reduce", "N", "WGR_LEAN_MIN_IMAGES = 768", "conv_mfma.hip:372", "N = 767, HS 8", _RED + "[767-8-False-False]", "N = 768, HS 8", _RED + "[768-8-False-False]"),
+    _s("launch_wgrad32_reduce", "N (behind k_wgrad32<4>, NHWC)", "768", "conv_mfma.hip:372", "N = 767, HS 4", _RED + "[767-4-False-False]", "N = 768, HS 4", _RED + "[768-4-False-False]"),
+    _s("launch_wgrad32_reduce", "N (behind k_wgrad32<4>, NCHW small side)", "768", "conv_mfma.hip:372", "N = 767, HS 4", _RED + "[767-4-True-True]", "N = 768, HS 4", _RED + "[768-4-True-True]"),
+    _s("launch_down_dma_t / launch_up_ws_t", "units = N * Hs * Hs / 64", "256 (HS 16)", "conv_down_dma.hip:222", "N = 64", _GRID + "[64-16]", "N = 65", _GRID + "[65-16]"),
+    _s("launch_down_dma_t / launch_up_ws_t", "units", "256 (HS 8)", "conv_up_ws.hip:348", "N = 256", _GRID + "[256-8]", "N = 257", _GRID + "[257-8]"),
+    _s("launch_down_t<4> / launch_up_t<4>", "units = ceil(N / 4)", "256", "conv_mfma.hip:387", "N = 1024", _GRID + "[1024-4]", "N = 1025", _GRID + "[1025-4]"),
+    _s("launch_wgrad_generic", "chunks = N * Hs * Ws / 1024", "2", "conv_generic.hip:385", "N = 7 (16x16)", V + "test_generic_wgrad_at_the_chunk_switches[7]",
+       "N = 8", V + "test_generic_wgrad_at_the_chunk_switches[8]"),
+    _s("launch_wgrad_generic", "chunks", "64", "conv_generic.hip:384", "N = 256 (64 chunks)", V + "test_generic_wgrad_at_the_chunk_switches[256]",
+       "N = 260 (65 -> 64)", V + "test_generic_wgrad_at_the_chunk_switches[260]"),
+    _s("fc_chain_rows", "n", "FCC_R4_MAX_ROWS = 1024", "fc_chain.hip:748", "n = 1024", _CHAIN + "[1024-10-False]", "n = 1025", _CHAIN + "[1025-10-False]"),
+    _s("fc_chain_rows", "n (with the conv ends)", "1024", "fc_chain.hip:748", "n = 1024", _CHAIN + "[1024-10-True]", "n = 1025", _CHAIN + "[1025-10-True]"),
+    _s("fc_chain_rows", "n (run-time D)", "1024", "fc_chain.hip:748", "n = 1024, D = 6", _CHAIN + "[1024-6-True]", "n = 1025, D = 6", _CHAIN + "[1025-6-True]"),
+    _s("try_fc32", "Kc", "32", "linear.hip:427", "K = N = 32", _KC + "[32]", "K = N = 36", _KC + "[36]"),
+    _s("try_fc32", "Kc", "64", "linear.hip:428", "K = N = 64", _KC + "[64]", "K = N = 68", _KC + "[68]"),
+    _s("try_fc32", "Kc", "128", "linear.hip:429", "K = N = 128", _KC + "[128]", "K = N = 132", _KC + "[132]"),
+    _s("try_fc32", "Kc", "256", "linear.hip:430", "K = N = 256", _KC + "[256]", "K = N = 260", _KC + "[260]"),
+    _s("try_fc32", "Kc", "512", "linear.hip:412", "K = N = 512", _KC + "[512]", "K = N = 516", _KC + "[516]"),
+    _s("try_fc32", "output tiles (forward)", "512", "linear.hip:413", "2048 x 960", _TILES + "[2048-64-960-parts0]", "2048 x 1024", _TILES + "[2048-64-1024-parts1]"),
+    _s("try_fc32", "output tiles (input gradient)", "512", "linear.hip:413", "2048 x 960", _TILES + "[2048-960-64-parts2]", "2048 x 1024", _TILES + "[2048-1024-64-parts3]"),
+    _s("try_fcw32", "output tiles", "512", "linear.hip:536", "960 x 2048", _TILES + "[40-2048-960-parts4]", "1024 x 2048", _TILES + "[40-2048-1024-parts5]"),
+    _s("try_fcw32", "M", "64", "linear.hip:538", "M = 64", V + "test_linear_wgrad_at_the_batch_switches[64]", "M = 65", V + "test_linear_wgrad_at_the_batch_switches[65]"),
+    _s("try_fcw32", "M", "4096", "linear.hip:534", "M = 4096", V + "test_linear_wgrad_at_the_batch_switches[4096]", "M = 4100", V + "test_linear_wgrad_at_the_batch_switches[4100]"),
+    _s("try_gdma_wgrad", "M", "64", "gemm_dma.hip:517", "M = 63", _DISC + "[63]", "M = 64", _DISC + "[64]"),
+    _s("try_gdma", "ceil(M / 64) * cols64", "192", "gemm_dma.hip:489", "M = 704", _DISC + "[704]", "M = 705", _DISC + "[705]"),
+    _s("try_gdma", "ceil(M / 128) * cols64", "224", "gemm_dma.hip:489", "M = 1664", _DISC + "[1664]", "M = 1665", _DISC + "[1665]"),
+    _s("try_narrow_fwd / try_narrow_dgrad", "K", "256", "linear_narrow.hip:88", "K = 252", V + "test_narrow_output_linear_at_its_minimum_contraction[252]",
+       "K = 256", V + "test_narrow_output_linear_at_its_minimum_contraction[256]"),
+    _s("try_narrow_fwd / try_narrow_dgrad", "N", "NARROW_MAX = 8", "linear_narrow.hip:88", "N = 8", V + "test_linear_outside_the_lds_resident_kernels[100-256-8]",
+       "N = 9", V + "test_linear_outside_the_lds_resident_kernels[100-256-9]"),
+    _s("launch_linear_wgrad_grouped", "max M", "64", "linear_grouped.hip:165", "M = 64", K + "test_linear_wgrad_grouped[64]", "M = 65", V + "test_linear_wgrad_grouped_past_its_slab_switches[65]"),
+    _s("launch_linear_wgrad_grouped", "max M", "128", "linear_grouped.hip:166", "M = 128", K + "test_linear_wgrad_grouped[128]", "M = 129", V + "test_linear_wgrad_grouped_past_its_slab_switches[129]"),
+    _s("launch_adam", "nt", "ADAM_MAX_T = 64", "adam.hip:80", "64 tensors", V + "test_adam_at_the_table_split[64]", "65 tensors", V + "test_adam_at_the_table_split[65]"),
+    # ---- linear.hip behind try_fc32 / try_gdma
+    _s("use_small", "Kc", "4096", "linear.hip:567", "K = 4096", _SMALL + "[40-4096-36]", "K = 4100", _SMALL + "[40-4100-36]"),
+    _s("use_small", "tiles64", "192", "linear.hip:567", "6080 x 100 (190 tiles)", _SMALL + "[6080-516-100]", "6081 x 100 (192)", _SMALL + "[6081-516-100]"),
+    _s("pick_split", "Kc / (2 S) (S = 1 | 2)", "64", "linear.hip:615", "K = 127", _SPLIT + "[40-127-36-parts0]", "K = 129", _SPLIT + "[40-129-36-parts1]"),
+    _s("pick_split", "Kc / (2 S) (S = 8 | 16)", "64", "linear.hip:615", "K = 1023", _SPLIT + "[40-1023-36-parts2]", "K = 1025", _SPLIT + "[40-1025-36-parts3]"),
+    _s("pick_split", "S", "16", "linear.hip:615", "K = 1025 (S = 16 wanted)", _SPLIT + "[40-1025-36-parts3]", "K = 2049 (32 wanted)", _SPLIT + "[40-2049-36-parts4]"),
+    _s("pick_split", "tiles * S", "256", "linear.hip:615", "1024 x 960 (240 tiles)", _SPLIT + "[1024-129-960-parts5]", "1024 x 1024 (256)", _SPLIT + "[1024-129-1024-parts6]"),
+    _s("launch_linear_wgrad", "M / (2 S)", "64", "linear.hip:717", "M = 127", _SPLIT + "[127-513-512-parts7]", "M = 129", _SPLIT + "[129-513-512-parts8]"),
+    _s("launch_linear_fwd", "k_splitk_epilogue grid", "1024", "linear.hip:653", "512 x 512", _RGRID + "[512-301-512-parts0]", "512 x 516", _RGRID + "[512-301-516-parts1]"),
+    _s("launch_linear_dgrad", "k_splitk_epilogue grid", "1024", "linear.hip:692", "512 x 512", _RGRID + "[512-512-301-parts2]", "512 x 516", _RGRID + "[512-516-301-parts3]"),
+    _s("launch_linear_wgrad", "k_splitk_reduce grid", "1024", "linear.hip:733", "512 x 511", _RGRID + "[300-511-512-parts4]", "512 x 513", _RGRID + "[300-513-512-parts5]"),
+    _s("try_gdma", "Kc", "256", "gemm_dma.hip:482", "K = 252", _DMAMIN + "[2048-252-1024-parts0]", "K = 256", _DMAMIN + "[2048-256-1024-parts1]"),
+    _s("try_gdma", "N (forward)", "128", "gemm_dma.hip:482", "N = 124", _DMAMIN + "[40-516-124-parts2]", "N = 128", _DMAMIN + "[40-516-128-parts3]"),
+    _s("try_gdma", "N (input gradient: the K columns)", "128", "gemm_dma.hip:482", "K = 124", _DMAMIN + "[40-124-516-parts4]", "K = 128", _DMAMIN + "[40-128-516-parts5]"),
+    _s("try_gdma_wgrad", "output tiles", "128", "gemm_dma.hip:518", "512 x 960 (120)", _DMAMIN + "[100-960-512-parts6]", "512 x 1024 (128)", _DMAMIN + "[100-1024-512-parts7]"),
+    _s("try_narrow_dgrad", "blocks", "4096", "linear_narrow.hip:101", "M = 16384", V + "test_narrow_input_gradient_at_its_grid_cap[16384]",
+       "M = 16388", V + "test_narrow_input_gradient_at_its_grid_cap[16388]"),
+    # ---- loss.hip, loglik.hip
+    _s("launch_sigmoid_bwd", "workgroups", "4096", "loss.hip:859", "n = 2^20", _ELT + "[0]", "n = 2^20 + 1", _ELT + "[1]"),
+    _s("launch_u8_to_f32", "workgroups", "4096", "loss.hip:879", "n = 2^24", _ELT + "[0]", "n = 2^24 + 16", _ELT + "[1]"),
+    _s("launch_add", "workgroups", "2048", "loss.hip:894", "n = 2^19", _ELT + "[0]", "n = 2^19 + 1", _ELT + "[1]"),
+    _s("launch_axpby", "workgroups", "2048", "loss.hip:901", "n = 2^19", _ELT + "[0]", "n = 2^19 + 1", _ELT + "[1]"),
+]
+
+# Thresholds read in the launchers that have NO entry above yet: no case sits at the flip, and which existing tests fall on
+# which side has not been established.  (launcher, variable, threshold, where)
+OPEN_SWITCHES = [
+    ("pick_split / launch_linear_wgrad", "S * (output + 4096) floats against the workspace", "dvae_conv_wgrad_ws_floats()", "linear.hip:616"),
+    ("launch_down_thin / launch_down_thin_u8", "n_units = 8 N", "1536 (N = 192 | 193)", "conv_thin.hip:679"),
+    ("launch_up_thin_recon / launch_up_thin_recon_u8", "n_units = 8 N", "1536 (N = 192 | 193)", "conv_thin.hip:708"),
+    ("launch_up_thin_staged", "n_units = 8 N (k_up_thin_pk)", "1536 (N = 192 | 193)", "conv_thin.hip:545"),
+    ("launch_wgrad_thin_u8 / launch_wgrad_thin", "n_units = 8 N", "WT_MAX_BLOCKS", "conv_thin.hip:757"),
+    ("launch_wgrad32 (k_wgrad32<4>)", "units", "WG_MAX_BLOCKS", "conv_mfma.hip:425"),
+    ("launch_up_thin_mm", "n_units = 3 N", "512 (N = 170 | 171)", "conv_up_thin_mm.hip:278"),
+    ("grid_for", "workgroups of the shape-generic conv kernels", "8192", "conv_generic.hip:330"),
+    ("launch_recon_rows", "nslice", "1 | 2 (k_recon_rows_finish)", "loglik.hip:147"),
+    ("k_adam", "tensor elements", "ADAM_CHUNK = 4096 (4096 | 4097 elements sit in both cases of test_adam_at_the_table_split)", "adam.hip:87"),
+]

@@ -74,7 +74,7 @@ def _native(loss, img, seed, n_data, lr, lr_disc):
     model = init_specific_model("Burgess", img, 10)
     opt = torch.optim.Adam(model.parameters(), lr=lr)
     loss_f = get_loss_f(loss, n_data=n_data, device=torch.device(DEV), lr_disc=lr_disc, **HP)
-    loss_f.replay = None            # the eager launch sequence = what bench.py times at these sizes
+    loss_f.replay = None            # the eager launch sequence (bench.py's `auto` replays a recorded plan up to 1024 images)
     model.to(DEV)
     model.train()
     return model, opt, loss_f

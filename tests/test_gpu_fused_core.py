@@ -351,7 +351,7 @@ def test_convT3_forward_on_staged_pair_records(N, C):
         check(p1.sum(), p0.sum().cpu(), rtol=1e-5, what="fused loss sum dist %d" % dist)
         if C == 1:
             assert torch.equal(r2, r1) and torch.equal(g2, g1) and torch.equal(p2, p1), "uint8 target == ToTensor(target), dist %d" % dist
-        else:       # fp32 targets: the matrix-core kernel; uint8 targets: the packed-FMA kernel (another summation order)
+        else:       # both on the matrix-core kernel; the uint8 target's values are converted in another place
             check(r2, r1.cpu(), what="uint8-target recon dist %d" % dist, **tol)
             check(g2, g1.cpu(), rtol=1e-4, atol_rel=2e-6, what="uint8-target dL/dlogit dist %d" % dist)
             check(p2.sum(), p1.sum().cpu(), rtol=1e-5, what="uint8-target loss sum dist %d" % dist)

@@ -1,0 +1,146 @@
+"""No GPU: tests/kernel_variants.py is complete and its test ids exist.
+
+* every __global__ kernel instantiation of the built library (the dvae::__device_stub__ symbols `nm -C` lists: one host stub
+  per instantiation; only NAMES are read) matches exactly one row of VARIANTS, and every row matches an instantiation -- a
+  kernel added to csrc/ without a row, or a row left behind by a removed kernel, fails here;
+* every row names a GPU test or a reason, every numeric switch two tests, and pytest collects every id named;
+* tools/kernel_trace_names.py reduces a kernel trace to the same spelling of the names."""
+import os
+import re
+import shutil
+import subprocess
+import sys
+from collections import Counter
+
+import pytest
+
+import kernel_variants as KV
+from disvae_amd import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_trace_names as KT  # noqa: E402
+
+_STUB = re.compile(r"__device_stub__(\w+(?:<[^(]*>)?)\(")
+
+
+def stub_names(nm_output):
+    """demangled `nm -C` text -> sorted kernel instantiations, e.g. 'k_fc32<32, false, 0>'."""
+    out = set()
+    for line in nm_output.splitlines():
+        m = _STUB.search(line.replace("(anonymous namespace)::", ""))
+        if m:
+            out.add(m.group(1))
+    return sorted(out)
+
+
+@pytest.fixture(scope="module")
+def instantiations():
+    lib = os.path.abspath(_lib.LIB_PATH)
+    if not os.path.exists(lib):
+        pytest.fail("libdvae_hip.so is not built (python disentangling-vae_amd/build.py)")
+    nm = shutil.which("nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
+    assert nm, "no nm on this machine"
+    names = stub_names(subprocess.run([nm, "-C", lib], capture_output=True, text=True, check=True).stdout)
+    assert len(names) > 100, names
+    return names
+
+
+def test_stub_name_parser():
+    text = ("0000000000233c50 T dvae::__device_stub__k_adam(dvae::AdamTable, float, float)\n"
+            "0000000000219070 W void dvae::__device_stub__k_up_thin<1, true, unsigned char>(float const*, int)\n"
+            "00000000002357c0 t dvae::(anonymous namespace)::__device_stub__k_iw_loglik(float const*, long)\n"
+            "0000000000000000 T dvae_version\n")
+    assert stub_names(text) == ["k_adam", "k_iw_loglik", "k_up_thin<1, true, unsigned char>"]
+
+
+def test_every_kernel_instantiation_has_exactly_one_row(instantiations):
+    rows = Counter(v.kernel for v in KV.VARIANTS)
+    twice = sorted(k for k, n in rows.items() if n > 1)
+    assert not twice, "rows listed twice: %s" % twice
+    missing = [k for k in instantiations if k not in rows]
+    assert not missing, "kernel instantiations of the built library without a row in tests/kernel_variants.py: %s" % missing
+    stale = sorted(k for k in rows if k not in instantiations)
+    assert not stale, "rows of tests/kernel_variants.py that match no kernel of the built library: %s" % stale
+
+
+def test_every_row_names_a_test_or_a_reason_and_cites_its_launch_site():
+    csrc = os.path.join(ROOT, "disentangling-vae_amd", "csrc")
+    lines = {}
+    for v in KV.VARIANTS:
+        assert (v.test is None) != (v.reason is None), v.kernel
+        assert v.entry and v.when, v.kernel
+        f, _, ln = v.where.partition(":")
+        if f not in lines:
+            with open(os.path.join(csrc, f)) as fh:
+                lines[f] = fh.read().split("\n")
+        assert 0 < int(ln) <= len(lines[f]) and lines[f][int(ln) - 1].strip(), (v.kernel, v.where)
+        assert v.kernel.split("<")[0] in "\n".join(lines[f]), (v.kernel, v.where)     # (the line itself may be a launch macro's use)
+    def cited(where):
+        f, _, ln = where.partition(":")
+        if f not in lines:
+            with open(os.path.join(csrc, f)) as fh:
+                lines[f] = fh.read().split("\n")
+        return 0 < int(ln) <= len(lines[f]) and bool(lines[f][int(ln) - 1].strip())
+    for s in KV.SWITCHES:
+        assert s.below_test and s.above_test and s.below and s.above, s
+        assert s.below_test != s.above_test, s                      # one test id PER SIDE
+        assert cited(s.where), s
+    for o in KV.OPEN_SWITCHES:
+        assert len(o) == 4 and all(o) and cited(o[3]), o
+
+
+def test_every_named_test_is_collected():
+    ids = {v.test for v in KV.VARIANTS if v.test} | {t for s in KV.SWITCHES for t in (s.below_test, s.above_test)}
+    assert all(i.startswith("tests/test_gpu_") for i in ids)
+    files = sorted({i.split("::")[0] for i in ids})
+    r = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + files, cwd=ROOT,
+                       capture_output=True, text=True)
+    collected = {line.strip() for line in r.stdout.splitlines() if "::" in line}
+    assert collected, r.stdout[-2000:] + r.stderr[-2000:]
+    missing = sorted(ids - collected)
+    assert not missing, "test ids named in tests/kernel_variants.py that pytest does not collect: %s" % missing
+
+
+TRACE_SAMPLE = '''"Kind","Agent_Id","Queue_Id","Kernel_Id","Kernel_Name","Correlation_Id","Start_Timestamp","End_Timestamp"
+"KERNEL_DISPATCH",4,1,10,"void dvae::k_fc32<32, false, 0>(float const*, long, float const*, long, float*, long, int, int, int, float const*, int, float const*, int)",1,100,200
+"KERNEL_DISPATCH",4,1,11,"dvae::k_adam(dvae::AdamTable, float, float, float, float, float, float, float, float) [clone .kd]",2,300,400
+"KERNEL_DISPATCH",4,1,10,"void dvae::k_fc32<32, false, 0>(float const*, long, float const*, long, float*, long, int, int, int, float const*, int, float const*, int)",3,500,600
+"KERNEL_DISPATCH",4,1,12,"void at::native::vectorized_elementwise_kernel<4, at::native::FillFunctor<float>, std::array<char*, 1ul> >(int, at::native::FillFunctor<float>, std::array<char*, 1ul>)",4,700,800
+"KERNEL_DISPATCH",4,1,13,"dvae::(anonymous namespace)::k_recon_rows(float const*, void const*, int, int, int, int, long, int, float*, float*).kd",5,900,950
+"KERNEL_DISPATCH",4,1,14,"void dvae::k_up_thin<1, true, unsigned char>(float const*, int)",6,960,990
+'''
+
+
+def test_trace_reduction_tool(tmp_path):
+    p = tmp_path / "x_kernel_trace.csv"
+    p.write_text(TRACE_SAMPLE)
+    seen = KT.reduce_trace(str(p))
+    assert dict(seen) == {"k_fc32<32, false, 0>": 2, "k_adam": 1, "k_recon_rows": 1, "k_up_thin<1, true, unsigned char>": 1}
+    rows = {v.kernel for v in KV.VARIANTS}
+    assert set(seen) <= rows                                      # the tool spells names as the table does
+    assert any(k.startswith("at::native::") for k in KT.reduce_trace(str(p), everything=True))
+    out = tmp_path / "out.txt"
+    assert KT.main(["sample=" + str(p), "--out", str(out)]) == 0
+    text = out.read_text().split("\n")
+    assert text[0] == "# sample: 4 kernels, 5 launches" and text[1].split() == ["1", "k_adam"]
+    # an unlabelled path that contains '=' is a path; a label ends at the FIRST '='
+    d = tmp_path / "a=b"
+    d.mkdir()
+    q = d / "y=z_kernel_trace.csv"
+    q.write_text(TRACE_SAMPLE)
+    assert KT.split_label(str(q)) == (str(q), str(q))
+    assert KT.split_label("run1=" + str(q)) == ("run1", str(q))
+    assert KT.split_label("plain.csv") == ("plain.csv", "plain.csv")
+    assert KT.main([str(q), "--out", str(out)]) == 0 and out.read_text().startswith("# %s: 4 kernels" % q)
+
+
+def test_committed_trace_shows_every_kernel_the_table_gives_to_the_new_file():
+    """profiles/kernel_variant_trace.txt = tools/kernel_trace_names.py on a kernel trace of tests/test_gpu_kernel_variants.py
+    alone: every kernel whose row names a test of that file was launched in that run, and every name in the trace has a row."""
+    with open(os.path.join(ROOT, "profiles", "kernel_variant_trace.txt")) as f:
+        seen = {line.split(None, 1)[1].strip() for line in f if line.strip() and not line.startswith("#")}
+    claimed = {v.kernel for v in KV.VARIANTS if v.test and v.test.startswith(KV.V)}
+    assert len(claimed) > 80
+    assert not sorted(claimed - seen), "rows that name a test of the file, but the kernel is not in its trace"
+    assert not sorted(seen - {v.kernel for v in KV.VARIANTS}), "traced kernels without a row"
