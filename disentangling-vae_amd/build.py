@@ -1,12 +1,13 @@
-"""Build libdvae_hip.so (gfx950) in-tree: hipcc cross-compiles without a GPU.
+"""Build libdvae_hip.so and libdvae_eval_hip.so (gfx950) in-tree: hipcc cross-compiles without a GPU.
 
     python disentangling-vae_amd/build.py [--force] [--debug]
 
-The .so lands in disentangling-vae_amd/lib/ (git-ignored, but it travels with gpurun
-snapshots).  Objects are rebuilt only when a source / header is newer or the flags changed.
+The libraries land in disentangling-vae_amd/lib/ (git-ignored build products).  Objects are rebuilt only
+when a source / header is newer or the flags changed.
 --debug (or DVAE_BUILD_DEBUG=1) adds -DDVAE_DEBUG_SWITCHES: the A/B / timing-ablation environment
 switches and the experimental kernel variants they select (tools/README.md); the default (shipped)
-library has none of them.
+library has none of them.  libdvae_eval_hip.so (include/dvae_eval_hip.h: the evaluation-side kernels,
+csrc/elbo_decomp.hip) is a second target with the same flags and the same up-to-date logic under its own stamp.
 """
 import glob
 import os
@@ -22,6 +23,10 @@ HEADERS = sorted(glob.glob(os.path.join(SRC, "*.h"))) + [os.path.join(HERE, ".."
 SOURCES = ["conv_generic", "conv_mfma", "conv_down_dma", "conv_up_ws", "conv_wgrad_ws", "conv_thin", "conv_thin_ws", "conv_up_thin_mm", "linear", "linear_narrow", "gemm_dma", "linear_grouped", "fc_chain", "stage", "loss", "latent_wide",
            "metrics", "adam", "comm", "viz", "loglik", "plan", "capi"]
 DEBUG_SOURCES = []          # experimental kernel files: only in --debug builds
+# the evaluation-side library: its own sources, header and stamp; nothing of it is linked into libdvae_hip.so
+EVAL_LIB = os.path.join(HERE, "lib", "libdvae_eval_hip.so")
+EVAL_SOURCES = ["elbo_decomp"]
+EVAL_HEADERS = HEADERS + [os.path.join(HERE, "..", "include", "dvae_eval_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 
@@ -29,22 +34,15 @@ def _newer(a, b):
     return (not os.path.exists(b)) or os.path.getmtime(a) > os.path.getmtime(b)
 
 
-def build(force=False, verbose=True, debug=None):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if debug is None:
-        debug = os.environ.get("DVAE_BUILD_DEBUG", "0") == "1"
-    os.makedirs(OBJ, exist_ok=True)
-    os.makedirs(os.path.dirname(LIB), exist_ok=True)
-    flags = FLAGS + (["-DDVAE_DEBUG_SWITCHES"] if debug else [])
-    sources = SOURCES + (DEBUG_SOURCES if debug else [])
-    stamp = os.path.join(OBJ, "flags.txt")
+def _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose):
+    """Compile `sources` (objects rebuilt only when a source / header is newer or the stamped flags changed) and link `lib`."""
     want = " ".join(flags + sources)
     if not os.path.exists(stamp) or open(stamp).read() != want:
         force = True
     jobs = []
     for s in sources:
         src, obj = os.path.join(SRC, s + ".hip"), os.path.join(OBJ, s + ".o")
-        if force or _newer(src, obj) or any(_newer(h, obj) for h in HEADERS):
+        if force or _newer(src, obj) or any(_newer(h, obj) for h in headers):
             jobs.append([hipcc] + flags + ["-c", src, "-o", obj])
 
     def run(cmd):
@@ -58,10 +56,24 @@ def build(force=False, verbose=True, debug=None):
             if verbose and err.strip():
                 sys.stderr.write(err)
     objs = [os.path.join(OBJ, s + ".o") for s in sources]
-    if force or jobs or not os.path.exists(LIB):
-        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl"])
+    if force or jobs or not os.path.exists(lib):
+        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + ["-ldl"])
     with open(stamp, "w") as f:
         f.write(want)
+    return lib
+
+
+def build(force=False, verbose=True, debug=None):
+    """Build both libraries; returns the path of libdvae_hip.so."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if debug is None:
+        debug = os.environ.get("DVAE_BUILD_DEBUG", "0") == "1"
+    os.makedirs(OBJ, exist_ok=True)
+    os.makedirs(os.path.dirname(LIB), exist_ok=True)
+    flags = FLAGS + (["-DDVAE_DEBUG_SWITCHES"] if debug else [])
+    sources = SOURCES + (DEBUG_SOURCES if debug else [])
+    _build_target(hipcc, LIB, sources, HEADERS, flags, os.path.join(OBJ, "flags.txt"), force, verbose)
+    _build_target(hipcc, EVAL_LIB, EVAL_SOURCES, EVAL_HEADERS, flags, os.path.join(OBJ, "flags_eval.txt"), force, verbose)
     return LIB
 
 

@@ -1,0 +1,59 @@
+"""ctypes binding of libdvae_eval_hip.so (the C-ABI declared in include/dvae_eval_hip.h): the evaluation-side kernels.
+
+A second library next to libdvae_hip.so (_lib.py), loaded lazily on first use.  As there, the library is the product: no CPU
+or PyTorch fallback, a missing shared object or symbol fails loudly.  Calls go straight to the library -- they are never
+recorded into a launch plan (graph.py replays the training step only).
+"""
+import ctypes
+import os
+
+from ._lib import DvaeHipError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("DVAE_EVAL_HIP_LIB", os.path.join(_HERE, "..", "lib", "libdvae_eval_hip.so"))
+
+VERSION = 1                  # DVAE_EVAL_VERSION
+JOINT_CHUNK = 2048           # DVAE_EVAL_JOINT_CHUNK: data points per workgroup of the joint log-density kernel (at least)
+JOINT_MAX_CHUNKS = 256       # DVAE_EVAL_JOINT_MAX_CHUNKS
+
+_p = ctypes.c_void_p
+_i = ctypes.c_int
+_l = ctypes.c_long
+
+# name -> argtypes (all return int unless listed in _RESTYPE)
+SIGNATURES = {
+    "dvae_eval_version": [],
+    "dvae_eval_last_error": [],
+    "dvae_eval_joint_logq_ws_floats": [_l, _i, _l],
+    "dvae_eval_joint_logq": [_p, _p, _p, _l, _i, _l, _p, _p, _p, _p],
+    "dvae_eval_sample_terms": [_p, _p, _p, _p, _l, _i, _l, _p, _p, _p, _p],
+}
+_RESTYPE = {"dvae_eval_last_error": ctypes.c_char_p, "dvae_eval_joint_logq_ws_floats": ctypes.c_size_t}
+
+_lib = None
+
+
+def lib():
+    """Load (once) and return the ctypes handle; raises if the library is absent."""
+    global _lib
+    if _lib is None:
+        path = os.path.abspath(LIB_PATH)
+        if not os.path.exists(path):
+            raise DvaeHipError(
+                "libdvae_eval_hip.so not found at %s -- build it with `python disentangling-vae_amd/build.py` "
+                "(there is no CPU / PyTorch fallback for the evaluation kernels)" % path)
+        h = ctypes.CDLL(path)
+        for name, argtypes in SIGNATURES.items():
+            fn = getattr(h, name)  # AttributeError if the symbol is missing: fail loudly
+            fn.argtypes = argtypes
+            fn.restype = _RESTYPE.get(name, ctypes.c_int)
+        _lib = h
+    return _lib
+
+
+def call(name, *args):
+    """Call an int-returning entry point, raise on a non-zero status."""
+    h = lib()
+    rc = getattr(h, name)(*args)
+    if rc != 0:
+        raise DvaeHipError("%s failed (%d): %s" % (name, rc, h.dvae_eval_last_error().decode()))

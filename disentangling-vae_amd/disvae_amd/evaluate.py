@@ -23,7 +23,7 @@ from timeit import default_timer
 import numpy as np
 import torch
 
-from . import _lib
+from . import _evallib, _lib
 from ._lib import call, ptr
 from .engine import _stream
 from .likelihood import _ScorePasses, check_rec_dist, log_likelihood
@@ -34,6 +34,7 @@ TEST_LOSSES_FILE = "test_losses.log"
 METRICS_FILENAME = "metrics.log"
 METRIC_HELPERS_FILE = "metric_helpers.pth"
 LOG_LIKELIHOOD_FILE = "log_likelihood.log"
+ELBO_DECOMPOSITION_FILE = "elbo_decomposition.log"
 
 
 class Evaluator:
@@ -48,9 +49,11 @@ class Evaluator:
         self.reference_early_return = reference_early_return
         self.logger.info("Testing Device: {}".format(self.device))
 
-    def __call__(self, data_loader, is_metrics=False, is_losses=True, is_log_likelihood=False, n_samples=128):
+    def __call__(self, data_loader, is_metrics=False, is_losses=True, is_log_likelihood=False, n_samples=128,
+                 is_decomposition=False, n_samples_decomposition=10000):
         """evaluate.py:60-95.  is_log_likelihood: also write compute_log_likelihood(data_loader, n_samples) to
-        log_likelihood.log (the return value stays the reference's (metric, losses))."""
+        log_likelihood.log; is_decomposition: also write compute_elbo_decomposition(data_loader, n_samples_decomposition) to
+        elbo_decomposition.log (the return value stays the reference's (metric, losses))."""
         start = default_timer()
         is_still_training = self.model.training
         self.model.eval()
@@ -73,6 +76,12 @@ class Evaluator:
             self.logger.info('Log-likelihood: {}'.format(ll))
             os.makedirs(self.save_dir, exist_ok=True)
             save_metadata(ll, self.save_dir, filename=LOG_LIKELIHOOD_FILE)
+        if is_decomposition:
+            self.logger.info('Computing the ELBO decomposition over the data set...')
+            dec = self.compute_elbo_decomposition(data_loader, n_samples=n_samples_decomposition)
+            self.logger.info('ELBO decomposition: {}'.format(dec))
+            os.makedirs(self.save_dir, exist_ok=True)
+            save_metadata(dec, self.save_dir, filename=ELBO_DECOMPOSITION_FILE)
         if is_still_training:
             self.model.train()
         self.logger.info('Finished evaluating after {:.1f} min.'.format((default_timer() - start) / 60))
@@ -107,6 +116,89 @@ class Evaluator:
                  for data, _ in dataloader]
         per_image = torch.cat(parts).cpu().double()
         return {"log_likelihood": per_image.mean().item(), "n_samples": int(n_samples), "rec_dist": rec_dist}
+
+    # ------------------------------------------------------------------ ELBO decomposition over the data set
+    def compute_elbo_decomposition(self, dataloader, n_samples=10000, seed=0, sample_idx=None, eps=None):
+        """Decomposition of the data-set average of KL[q(z|x_n) || p(z)] (Chen et al. 2018, section 3) into index-code mutual
+        information, total correlation and dimension-wise KL, each against the aggregate posterior q(z) = 1/N sum_n q(z|x_n)
+        of ALL N images of the loader, estimated on S = n_samples samples z_s = mu_n(s) + exp(logvar_n(s) / 2) eps_s of S
+        distinct images n(s) (n_samples=None: S = N, every image once in data-set order -- the paper's full estimate):
+
+            H_z    = -1/S sum_s log q(z_s)                  joint entropy       (dvae_eval_joint_logq)
+            H_z_d  = [-1/S sum_s log q_d(z_sd) for d]       marginal entropies  (dvae_latent_entropy on the [D, S] image of z)
+            H_zCx  = -1/S sum_s log q(z_s | x_n(s))         conditional entropy (dvae_eval_sample_terms)
+            mi     = H_z - H_zCx
+            tc     = sum_d H_z_d - H_z
+            dw_kl  = -sum_d H_z_d - 1/S sum_s log p(z_s)
+            kl     = mi + tc + dw_kl                        (= 1/S sum_s [log q(z_s | x_n(s)) - log p(z_s)])
+
+        Unlike the minibatch mi_loss / tc_loss / dw_kl_loss of the training log these do not depend on a batch size or a loss.
+        The draws (rows = randperm(N)[:S], eps ~ N(0, I)) come from a private generator seeded with `seed`: the same seed gives
+        the same bits, the global random states are untouched; sample_idx ([S] rows, each in [0, N)) / eps ([S, D]) inject
+        them.  Train / eval mode is restored.  The handful of scalars is combined on the host."""
+        # every size is known and checked before any device work: a DataLoader tells the length of its data set, a plain
+        # sequence of batches is counted
+        ds = getattr(dataloader, "dataset", None)
+        n = len(ds) if ds is not None else sum(len(x) for x, _ in dataloader)
+        dim = int(self.model.latent_dim)
+        if sample_idx is not None:
+            sample_idx = torch.as_tensor(sample_idx).to(torch.int64).reshape(-1)
+            n_samples = int(sample_idx.numel())
+        S = n if n_samples is None else int(n_samples)
+        if S < 1:
+            raise ValueError("n_samples must be >= 1 (or None for the whole data set), got %r" % (n_samples,))
+        if S > n:
+            raise ValueError("n_samples=%d exceeds the %d images of the data set (samples are drawn without replacement)" % (S, n))
+        if eps is not None and tuple(eps.shape) != (S, dim):
+            raise ValueError("eps must have shape (%d, %d), got %s" % (S, dim, tuple(eps.shape)))
+        if sample_idx is not None and not (0 <= int(sample_idx.min()) and int(sample_idx.max()) < n):
+            raise ValueError("sample_idx must hold rows in [0, %d)" % n)            # (the kernels do not check them)
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            table = _LatentTable(*self._encode_dataset(dataloader))
+        finally:
+            if was_training:
+                self.model.train()
+        if table.n != n:
+            raise ValueError("the loader yielded %d images, its data set has %d" % (table.n, n))
+        dev = table.mean.device
+        gen = torch.Generator(device=dev).manual_seed(int(seed))
+        if sample_idx is not None:
+            rows = sample_idx.to(dev)
+        elif n_samples is None:
+            rows = torch.arange(n, device=dev)
+        else:
+            rows = torch.randperm(n, generator=gen, device=dev)[:S].contiguous()
+        noise = torch.randn(S, dim, generator=gen, device=dev) if eps is None else eps.to(dev, torch.float32).contiguous()
+        mean_s, logvar_s = table.select(rows)
+        z = (mean_s + torch.exp(0.5 * logvar_s) * noise).contiguous()
+
+        E = _evallib.lib()
+        out = torch.empty(3 * S + 3 + dim, dtype=torch.float32, device=dev)       # logqz, logqz_condx, logpz, H_z, 2 means, H_z_d
+        logqz, logqz_condx, logpz = out[:S], out[S:2 * S], out[2 * S:3 * S]
+        scal = out[3 * S:]
+        ws = torch.empty(max(E.dvae_eval_joint_logq_ws_floats(n, dim, S), _lib.lib().dvae_latent_entropy_ws_floats(n, dim, S)),
+                         dtype=torch.float32, device=dev)
+        st = _stream()
+        _evallib.call("dvae_eval_joint_logq", ptr(z), ptr(table.mean), ptr(table.logvar), n, dim, S, ptr(ws), ptr(logqz),
+                      ptr(scal), st)
+        _evallib.call("dvae_eval_sample_terms", ptr(z), ptr(noise), ptr(table.logvar), ptr(rows), n, dim, S, ptr(logqz_condx),
+                      ptr(logpz), scal.data_ptr() + 4, st)
+        # dvae_latent_entropy reads a [D, S] image whose row d must hold the S samples of z_d: the TRANSPOSED copy of the [S, D]
+        # samples.  This deliberately differs from _entropies below, which hands over the gathered [S, D] block as it lies in
+        # memory to reproduce the reference's MIG numbers (its .view is a reshape that mixes dimensions): here there is no
+        # reference to match, a reshape would evaluate q_d at samples of other dimensions and tc would not be 0 at D = 1.
+        z_ds = z.t().contiguous()
+        call("dvae_latent_entropy", ptr(z_ds), ptr(table.mean), ptr(table.logvar), n, dim, S, ptr(ws), scal.data_ptr() + 12, st)
+        host = [float(v) for v in scal.cpu().double()]                           # ONE device->host copy
+        H_z, mean_logqz_condx, mean_logpz, H_z_d = host[0], host[1], host[2], host[3:]
+        H_zCx = -mean_logqz_condx
+        mi = H_z - H_zCx
+        tc = math.fsum(H_z_d) - H_z
+        dw_kl = -math.fsum(H_z_d) - mean_logpz
+        return {"H_z": H_z, "H_z_d": H_z_d, "H_zCx": H_zCx, "mi": mi, "tc": tc, "dw_kl": dw_kl, "kl": mi + tc + dw_kl,
+                "n_samples": S, "n_data": n}
 
     # ------------------------------------------------------------------ MIG / AAM (evaluate.py:119-317)
     def compute_metrics(self, dataloader, sample_idx=None, n_samples=10000):
