@@ -13,6 +13,12 @@
   arithmetic (mutual information, sort, MIG, AAM) stays on the host as in the reference.
 * Importance-weighted log-likelihood (``compute_log_likelihood``, new): the mean over the data set of likelihood.log_likelihood
   (K samples per image, a private seeded generator), written to log_likelihood.log by ``__call__(is_log_likelihood=True)``.
+* FactorVAE score (Kim & Mnih 2018, section 4) and beta-VAE score (Higgins et al. 2017, section 3), new
+  (``compute_factor_scores`` / ``factor_scores_from_table``): rows of the table of posterior means drawn with one factor of
+  variation fixed, the statistic of the 15 000 gathered groups (variance per dimension / mean absolute pair difference) and the
+  majority vote as HIP launches on the table where it lies (libdvae_score_hip.so); only the [K, D] vote matrices, the variance
+  vector and the beta-VAE classifier's [V, D] features cross to the host.  Definitions and defaults: disentanglement_lib's
+  factor_vae.py / beta_vae.py.  Written to factor_scores.log by ``__call__(is_scores=True)``.
 """
 import logging
 import math
@@ -23,7 +29,7 @@ from timeit import default_timer
 import numpy as np
 import torch
 
-from . import _evallib, _lib
+from . import _evallib, _lib, _scorelib
 from ._lib import call, ptr
 from .engine import _stream
 from .likelihood import _ScorePasses, check_rec_dist, log_likelihood
@@ -35,6 +41,7 @@ METRICS_FILENAME = "metrics.log"
 METRIC_HELPERS_FILE = "metric_helpers.pth"
 LOG_LIKELIHOOD_FILE = "log_likelihood.log"
 ELBO_DECOMPOSITION_FILE = "elbo_decomposition.log"
+FACTOR_SCORES_FILE = "factor_scores.log"
 
 
 class Evaluator:
@@ -50,10 +57,11 @@ class Evaluator:
         self.logger.info("Testing Device: {}".format(self.device))
 
     def __call__(self, data_loader, is_metrics=False, is_losses=True, is_log_likelihood=False, n_samples=128,
-                 is_decomposition=False, n_samples_decomposition=10000):
+                 is_decomposition=False, n_samples_decomposition=10000, is_scores=False):
         """evaluate.py:60-95.  is_log_likelihood: also write compute_log_likelihood(data_loader, n_samples) to
         log_likelihood.log; is_decomposition: also write compute_elbo_decomposition(data_loader, n_samples_decomposition) to
-        elbo_decomposition.log (the return value stays the reference's (metric, losses))."""
+        elbo_decomposition.log; is_scores: also write compute_factor_scores(data_loader) to factor_scores.log (the return value
+        stays the reference's (metric, losses))."""
         start = default_timer()
         is_still_training = self.model.training
         self.model.eval()
@@ -82,6 +90,12 @@ class Evaluator:
             self.logger.info('ELBO decomposition: {}'.format(dec))
             os.makedirs(self.save_dir, exist_ok=True)
             save_metadata(dec, self.save_dir, filename=ELBO_DECOMPOSITION_FILE)
+        if is_scores:
+            self.logger.info('Computing the FactorVAE and beta-VAE scores...')
+            scores = self.compute_factor_scores(data_loader)
+            self.logger.info('Disentanglement scores: {}'.format(scores))
+            os.makedirs(self.save_dir, exist_ok=True)
+            save_metadata(scores, self.save_dir, filename=FACTOR_SCORES_FILE)
         if is_still_training:
             self.model.train()
         self.logger.info('Finished evaluating after {:.1f} min.'.format((default_timer() - start) / 60))
@@ -200,6 +214,35 @@ class Evaluator:
         return {"H_z": H_z, "H_z_d": H_z_d, "H_zCx": H_zCx, "mi": mi, "tc": tc, "dw_kl": dw_kl, "kl": mi + tc + dw_kl,
                 "n_samples": S, "n_data": n}
 
+    # ------------------------------------------------------------------ FactorVAE / beta-VAE scores
+    def compute_factor_scores(self, dataloader, n_train=10000, n_eval=5000, batch_size=64, n_variance=10000,
+                              active_threshold=0.05, seed=0, draws=None):
+        """FactorVAE score and beta-VAE score of the model (factor_scores_from_table below, on the posterior means of the whole
+        data set through the native encoder).  Requirements of compute_metrics: ``dataloader.dataset`` exposes ``lat_sizes`` /
+        ``lat_names``, the loader iterates the data set in factor order and the data set enumerates ``lat_sizes``.  Every size
+        is checked before any device work; train / eval mode is restored.  Returns {"factor_vae_train", "factor_vae_eval",
+        "beta_vae_train", "beta_vae_eval", "n_active", "n_train", "n_eval", "batch_size"}."""
+        ds = getattr(dataloader, "dataset", None)
+        if not (hasattr(ds, "lat_sizes") and hasattr(ds, "lat_names")):
+            raise ValueError("Dataset needs to have known true factors of variations to compute the metric. This does not "
+                             "seem to be the case for {}".format(type(ds).__name__))
+        lat_sizes = [int(k) for k in ds.lat_sizes]
+        n = int(np.prod(lat_sizes))
+        _check_score_sizes(n, lat_sizes, n_train, n_eval, batch_size, n_variance)
+        if hasattr(ds, "__len__") and len(ds) != n:
+            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (len(ds), lat_sizes))
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            mean, _logvar = self._encode_dataset(dataloader)
+        finally:
+            if was_training:
+                self.model.train()
+        if mean.shape[0] != n:
+            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (mean.shape[0], lat_sizes))
+        return factor_scores_from_table(mean, lat_sizes, n_train=n_train, n_eval=n_eval, batch_size=batch_size,
+                                        n_variance=n_variance, active_threshold=active_threshold, seed=seed, draws=draws)
+
     # ------------------------------------------------------------------ MIG / AAM (evaluate.py:119-317)
     def compute_metrics(self, dataloader, sample_idx=None, n_samples=10000):
         """Mutual Information Gap and Axis Alignment Metric of the model on a data set with known, balanced factors of
@@ -299,3 +342,204 @@ def disentanglement_scores(H_z, H_zCv, lat_sizes):
     aam_k = torch.where(best > 0, (best - others).clamp(min=0) / best, torch.zeros_like(best))
     return {"marginal_entropies": H_z, "cond_entropies": H_zCv, "mig_k": mig_k, "mig": mig_k.mean(),
             "aam_k": aam_k, "aam": aam_k.mean()}
+
+
+# ---------------------------------------------------------------------- FactorVAE / beta-VAE scores on a table of means
+def _check_score_sizes(n, lat_sizes, n_train, n_eval, batch_size, n_variance):
+    if len(lat_sizes) < 1 or min(lat_sizes) < 1:
+        raise ValueError("lat_sizes must hold positive sizes, got %s" % (lat_sizes,))
+    if max(lat_sizes) < 2:
+        raise ValueError("no factor of variation takes two values or more: lat_sizes=%s" % (lat_sizes,))
+    if int(n_train) < 1 or int(n_eval) < 1:
+        raise ValueError("n_train and n_eval must be >= 1, got %r and %r" % (n_train, n_eval))
+    if int(batch_size) < 2:
+        raise ValueError("batch_size must be >= 2 (a variance needs two points), got %r" % (batch_size,))
+    if min(n, int(n_variance)) < 2:
+        raise ValueError("the global variance needs two rows or more: n_variance=%r on %d images" % (n_variance, n))
+
+
+def draw_fixed_factor_rows(lat_sizes, n_groups, batch_size, generator, device="cpu", paired=False):
+    """Rows of a data set that enumerates ``lat_sizes`` in row-major order, drawn in ``n_groups`` groups of ``batch_size``
+    with one factor of variation held fixed.  Per group a factor k is drawn uniformly among the factors with two values or
+    more; every member gets independent uniform values of every factor (with replacement: N never limits the group), and
+    column k is then overwritten --
+
+    * paired=False (FactorVAE): with ONE value per group.  Returns (factor int32 [V], rows int64 [V, L]).
+    * paired=True (beta-VAE): a second, independent set of values is drawn for the b side and the a side's column k is copied
+      into it member by member (each PAIR shares its value).  Returns (factor, rows_a, rows_b).
+
+    A row is sum_j value_j * stride_j.  All draws come from ``generator`` (a torch.Generator of ``device``)."""
+    sizes = [int(k) for k in lat_sizes]
+    V, L, K = int(n_groups), int(batch_size), len(sizes)
+    eligible = [k for k, size in enumerate(sizes) if size >= 2]
+    if not eligible:
+        raise ValueError("no factor of variation takes two values or more: lat_sizes=%s" % (sizes,))
+    strides = [int(np.prod(sizes[j + 1:])) for j in range(K)]
+    opts = dict(generator=generator, device=device)
+
+    def uniform_values(*shape):
+        return torch.stack([torch.randint(size, shape, **opts) for size in sizes], dim=-1)          # [..., K] int64
+
+    pick = torch.randint(len(eligible), (V,), **opts)
+    factor = torch.tensor(eligible, dtype=torch.int64, device=device)[pick]                         # [V]
+    column = factor.view(V, 1, 1).expand(V, L, 1)
+    values = uniform_values(V, L)
+    stride_t = torch.tensor(strides, dtype=torch.int64, device=device)
+    if not paired:
+        fixed = uniform_values(V).gather(1, factor.view(V, 1))                                      # [V, 1]: one value per group
+        values.scatter_(2, column, fixed.view(V, 1, 1).expand(V, L, 1))
+        return factor.to(torch.int32), (values * stride_t).sum(-1).contiguous()
+    values_b = uniform_values(V, L)
+    values_b.scatter_(2, column, values.gather(2, column))
+    return factor.to(torch.int32), (values * stride_t).sum(-1).contiguous(), (values_b * stride_t).sum(-1).contiguous()
+
+
+def fit_logistic_regression(features, labels, n_classes, C=1.0, max_iter=500, tolerance_grad=1e-8):
+    """Multinomial logistic regression in fp64 on the CPU: minimise mean cross-entropy + ||W||^2 / (2 C n) with an unpenalised
+    bias (sklearn's default objective) from zero, by L-BFGS with a strong-Wolfe line search until the largest absolute gradient
+    entry is below ``tolerance_grad`` or ``max_iter`` iterations have passed.  features [n, D], labels [n] in [0, n_classes).
+    Returns (W [n_classes, D], b [n_classes]) as fp64 tensors.  The objective is strictly convex in W: the optimum is unique."""
+    X = torch.as_tensor(features, dtype=torch.float64, device="cpu")
+    y = torch.as_tensor(labels, dtype=torch.int64, device="cpu")
+    n, dim = X.shape
+    W = torch.zeros(n_classes, dim, dtype=torch.float64, requires_grad=True)
+    b = torch.zeros(n_classes, dtype=torch.float64, requires_grad=True)
+    opt = torch.optim.LBFGS([W, b], lr=1.0, max_iter=int(max_iter), max_eval=25 * int(max_iter), tolerance_grad=tolerance_grad,
+                            tolerance_change=0.0, history_size=100, line_search_fn="strong_wolfe")
+
+    def closure():
+        opt.zero_grad()
+        loss = torch.nn.functional.cross_entropy(X @ W.t() + b, y) + (W * W).sum() / (2.0 * C * n)
+        loss.backward()
+        return loss
+    opt.step(closure)
+    return W.detach(), b.detach()
+
+
+def _classifier_accuracy(W, b, classes, features, labels):
+    """Share of rows whose arg-max logit (the lowest class on ties) is their label; classes[i] = the label of logit i."""
+    logits = torch.as_tensor(features, dtype=torch.float64) @ W.t() + b
+    pred = classes[torch.argmax(logits, dim=1)]
+    return float((pred == labels).double().mean().item())
+
+
+def factor_scores_from_table(mean, lat_sizes, n_train=10000, n_eval=5000, batch_size=64, n_variance=10000,
+                             active_threshold=0.05, seed=0, draws=None, return_details=False):
+    """FactorVAE score and beta-VAE score of a representation given as the fp32 [N, D] table ``mean`` (on the GPU) of a data
+    set that enumerates ``lat_sizes`` in row-major order.
+
+    FactorVAE: var = unbiased variance per dimension over min(N, n_variance) rows drawn without replacement
+    (dvae_score_group_var, one group); active[d] = sqrt(var[d]) >= active_threshold.  For the train and the eval set: groups
+    of ``batch_size`` rows with one factor fixed (draw_fixed_factor_rows), their variance per dimension divided by var
+    (dvae_score_group_var), the active dimension with the smallest value votes for the group's factor (dvae_score_vote).  The
+    classifier is c[d] = argmax_k votes_train[k, d] (the lowest k on ties); factor_vae_train = sum_d max_k votes_train[k, d] /
+    n_train, factor_vae_eval = sum_d votes_eval[c[d], d] / n_eval; both 0 without an active dimension.
+
+    beta-VAE: per group of ``batch_size`` PAIRS that share one factor's value the mean |z_a - z_b| per dimension
+    (dvae_score_pair_absdiff) is one feature vector labelled with the factor; fit_logistic_regression on the train set (classes
+    = the factors that occur in it), the scores are its accuracies on the train and the eval features.
+
+    Draws come from a private generator seeded with ``seed`` (the same seed gives the same bits, the global random states are
+    untouched).  ``draws`` injects them, each key on its own: "variance_rows" ([n] rows), "factor_vae_train" /
+    "factor_vae_eval" ((factor, rows)), "beta_vae_train" / "beta_vae_eval" ((factor, rows_a, rows_b)); injected rows and
+    factors are range-checked here (the kernels do not).  return_details=True: (scores, details) with the host copies of var,
+    active, the vote matrices, the classifier, the beta-VAE features / labels and (W, b)."""
+    lat_sizes = [int(k) for k in lat_sizes]
+    K = len(lat_sizes)
+    if mean.dim() != 2:
+        raise ValueError("mean must be an [N, D] table, got shape %s" % (tuple(mean.shape),))
+    n, dim = int(mean.shape[0]), int(mean.shape[1])
+    _check_score_sizes(n, lat_sizes, n_train, n_eval, batch_size, n_variance)
+    if n != int(np.prod(lat_sizes)):
+        raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (n, lat_sizes))
+    if dim < 1:
+        raise ValueError("mean must have one latent dimension or more")
+    if not mean.is_cuda:
+        raise _lib.DvaeHipError("factor_scores_from_table needs the table on the GPU (there is no CPU / PyTorch fallback for "
+                                "the score kernels)")
+    n_train, n_eval, L = int(n_train), int(n_eval), int(batch_size)
+    dev = mean.device
+    table = mean.detach().to(torch.float32).contiguous()
+    draws = dict(draws or {})
+    unknown = set(draws) - {"variance_rows", "factor_vae_train", "factor_vae_eval", "beta_vae_train", "beta_vae_eval"}
+    if unknown:
+        raise ValueError("unknown draws: %s" % sorted(unknown))
+    gen = torch.Generator(device=dev).manual_seed(int(seed))
+
+    def rows_of(t, shape=None):
+        t = torch.as_tensor(t).to(dev, torch.int64).contiguous()
+        if (shape is not None and tuple(t.shape) != shape) or t.numel() == 0 or not (0 <= int(t.min()) and int(t.max()) < n):
+            raise ValueError("injected rows must have shape %s and lie in [0, %d)" % (shape, n))
+        return t
+
+    def factor_of(t, V):
+        t = torch.as_tensor(t).to(dev, torch.int32).contiguous()
+        if tuple(t.shape) != (V,) or not (0 <= int(t.min()) and int(t.max()) < K):
+            raise ValueError("injected factors must have shape (%d,) and lie in [0, %d)" % (V, K))
+        return t
+
+    def drawn(key, V, paired):
+        if key in draws:
+            got = draws[key]
+            if len(got) != (3 if paired else 2):
+                raise ValueError("draws[%r] must be %s" % (key, "(factor, rows_a, rows_b)" if paired else "(factor, rows)"))
+            return (factor_of(got[0], V),) + tuple(rows_of(r, (V, L)) for r in got[1:])
+        return draw_fixed_factor_rows(lat_sizes, V, L, gen, device=dev, paired=paired)
+
+    S = _scorelib.lib()
+    st = _stream()
+
+    def group_var(rows, inv_scale):
+        V, Lg = rows.shape
+        ws = torch.empty(max(S.dvae_score_group_var_ws_floats(n, dim, V, Lg), 1), dtype=torch.float32, device=dev)
+        out = torch.empty(V, dim, dtype=torch.float32, device=dev)
+        _scorelib.call("dvae_score_group_var", ptr(table), ptr(rows), n, dim, V, Lg, ptr(inv_scale), ptr(ws), ptr(out), st)
+        return out
+
+    # ---- FactorVAE
+    if "variance_rows" in draws:
+        var_rows = rows_of(draws["variance_rows"]).view(1, -1)
+        if var_rows.shape[1] < 2:
+            raise ValueError("the global variance needs two rows or more")
+    else:
+        var_rows = torch.randperm(n, generator=gen, device=dev)[:min(n, int(n_variance))].contiguous().view(1, -1)
+    var_dev = group_var(var_rows, None).view(dim)
+    var = var_dev.cpu().numpy()                                                        # [D] fp32 -> host
+    active = np.sqrt(var.astype(np.float64)) >= float(active_threshold)
+    active_dev = torch.from_numpy(active.astype(np.int32)).to(dev)
+    inv_scale = (1.0 / var_dev).contiguous()
+    votes = {}
+    for key, V in (("train", n_train), ("eval", n_eval)):
+        factor, rows = drawn("factor_vae_" + key, V, paired=False)
+        stat = group_var(rows, inv_scale)
+        argmin = torch.empty(V, dtype=torch.int32, device=dev)
+        votes[key] = torch.empty(K, dim, dtype=torch.int32, device=dev)
+        _scorelib.call("dvae_score_vote", ptr(stat), ptr(factor), ptr(active_dev), V, dim, K, ptr(argmin), ptr(votes[key]), st)
+    votes_train, votes_eval = votes["train"].cpu().numpy().astype(np.int64), votes["eval"].cpu().numpy().astype(np.int64)
+    classifier = votes_train.argmax(axis=0)                                            # [D], the lowest k on ties
+    factor_vae_train = float(votes_train.max(axis=0).sum()) / n_train
+    factor_vae_eval = float(votes_eval[classifier, np.arange(dim)].sum()) / n_eval
+
+    # ---- beta-VAE
+    feats, labels = {}, {}
+    for key, V in (("train", n_train), ("eval", n_eval)):
+        factor, rows_a, rows_b = drawn("beta_vae_" + key, V, paired=True)
+        out = torch.empty(V, dim, dtype=torch.float32, device=dev)
+        _scorelib.call("dvae_score_pair_absdiff", ptr(table), ptr(rows_a), ptr(rows_b), n, dim, V, L, ptr(out), st)
+        feats[key], labels[key] = out, factor
+    feats = {k: v.cpu().double() for k, v in feats.items()}
+    labels = {k: v.cpu().to(torch.int64) for k, v in labels.items()}
+    classes = torch.unique(labels["train"])                                            # sorted
+    if classes.numel() > 1:
+        W, b = fit_logistic_regression(feats["train"], torch.searchsorted(classes, labels["train"]), classes.numel())
+    else:                                                                              # one class: nothing to fit
+        W, b = torch.zeros(1, dim, dtype=torch.float64), torch.zeros(1, dtype=torch.float64)
+    scores = {"factor_vae_train": factor_vae_train, "factor_vae_eval": factor_vae_eval,
+              "beta_vae_train": _classifier_accuracy(W, b, classes, feats["train"], labels["train"]),
+              "beta_vae_eval": _classifier_accuracy(W, b, classes, feats["eval"], labels["eval"]),
+              "n_active": int(active.sum()), "n_train": n_train, "n_eval": n_eval, "batch_size": L}
+    if not return_details:
+        return scores
+    return scores, {"var": var, "active": active, "votes_train": votes_train, "votes_eval": votes_eval, "classifier": classifier,
+                    "features_train": feats["train"], "features_eval": feats["eval"], "labels_train": labels["train"],
+                    "labels_eval": labels["eval"], "classes": classes, "W": W, "b": b}
