@@ -314,3 +314,5 @@ static inline constexpr int env_int(const char*, int dflt) { return dflt; }
 #endif
 
 }  // namespace dvae
+
+#include "latent_math.h"

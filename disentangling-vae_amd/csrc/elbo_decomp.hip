@@ -39,7 +39,6 @@ void set_error(const char* fmt, ...) {
 
 namespace {
 
-#define EVAL_LOG2PI 1.8378770664093453f
 #define JOINT_TARGET_WGS 2048          // workgroups that fill the device: 256 CUs x 8 (4 waves each)
 #define JOINT_WIDE_LDS_D 48            // run-time-D kernel: z of a workgroup in LDS up to this D (48 KB), re-read from memory above
 
@@ -55,23 +54,9 @@ __global__ __launch_bounds__(256) void k_joint_prep(const float* __restrict__ mu
     const float l = real ? lv[n * D + d] : 0.f;
     r[d] = real ? mu[n * D + d] : 0.f;
     r[DP + d] = real ? expf(-l) : 0.f;
-    if (real) c += -0.5f * (EVAL_LOG2PI + l);
+    if (real) c += gauss_c(l);
   }
   r[2 * DP] = n < N ? c : -INFINITY;
-}
-
-// online logsumexp over 8 densities: the shift guard of k_entropy_lse (metrics.hip) -- when every density so far is -inf
-// (an overflowing square, a padding record) shift by 0, so that exp(-inf - shift) = 0 instead of exp(-inf + inf) = NaN
-__device__ __forceinline__ void lse_fold8(const float (&v)[8], float& m, float& acc) {
-  float mx = m;
-#pragma unroll
-  for (int u = 0; u < 8; ++u) mx = fmaxf(mx, v[u]);
-  const float sh = mx > -INFINITY ? mx : 0.f;
-  float t = 0.f;
-#pragma unroll
-  for (int u = 0; u < 8; ++u) t += __expf(v[u] - sh);
-  acc = acc * __expf(m - sh) + t;
-  m = mx;
 }
 
 // part[c][0][s] = running max, part[c][1][s] = sum of exp(density - max) over the chunk's data points
@@ -150,8 +135,7 @@ __global__ __launch_bounds__(256) void k_joint_finish(const float* __restrict__ 
   float m = -INFINITY, acc = 0.f;
   for (int c = 0; c < chunks; ++c) {
     const float m2 = part[(long)c * 2 * S + s], a2 = part[(long)c * 2 * S + S + s];
-    if (m2 > m) { acc = acc * __expf(m - m2) + a2; m = m2; }
-    else if (m2 > -INFINITY) { acc += a2 * __expf(m2 - m); }
+    m = lse_merge(m, acc, m2, a2);
   }
   logqz[s] = m + logf(acc) - logf((float)N);                  // (m = -inf, acc = 0: -inf)
 }
@@ -166,8 +150,8 @@ __global__ __launch_bounds__(256) void k_sample_terms(const float* __restrict__ 
   float qc = 0.f, pz = 0.f;
   for (int d = 0; d < D; ++d) {
     const float e = eps[s * D + d], zz = z[s * D + d];
-    qc += -0.5f * (EVAL_LOG2PI + l[d]) - 0.5f * (e * e);
-    pz += -0.5f * EVAL_LOG2PI - 0.5f * (zz * zz);
+    qc += gauss_c(l[d]) - 0.5f * (e * e);
+    pz += -0.5f * LOG2PI - 0.5f * (zz * zz);
   }
   logqz_condx[s] = qc;
   logpz[s] = pz;

@@ -412,7 +412,7 @@ __global__ __launch_bounds__(256 * KS) void k_fc_chain_fwd(const FwdArgs P) {
           if (row0 + r < a.n_enc) {
             if (a.eps) zz = m + expf(0.5f * lv) * a.eps[o];
             a.mu[o] = m; a.logvar[o] = lv; a.z[o] = zz;
-            if (row0 + r < a.n_kl) kl = 0.5f * (-1.f - lv + m * m + expf(lv));
+            if (row0 + r < a.n_kl) kl = kl_elem(m, lv);
           }
         }
         tB[r * FCC_XS + d] = zz;
@@ -613,7 +613,7 @@ __global__ __launch_bounds__(256 * KS) void k_fc_chain_bwd(const BwdArgs P) {
   fill256<DEPTH, KS, 64>(L, re2, a.w_e2 + col * 4, CS);   // encoder lin2's stream: independent of the latent glue below
   load_mask(a.h2);
   __syncthreads();
-  // ---- reparameterisation + KL backward (k_reparam_kl_bwd's arithmetic) -> dml[8][2D] (interleaved) -> tB, zero padded
+  // ---- reparameterisation + KL backward (reparam_kl_bwd_elem, as k_reparam_kl_bwd) -> dml[8][2D] (interleaved) -> tB, zero padded
   {
     const float klw = a.scal[DVAE_S_KLW] * a.coef[DVAE_C_INV_B];
     const int dp2 = (D2 + 3) & ~3;
@@ -630,9 +630,7 @@ __global__ __launch_bounds__(256 * KS) void k_fc_chain_bwd(const BwdArgs P) {
           if (a.dz2) g += a.dz2[o];
           if (a.dz3) g += a.dz3[o];
           const float m = a.mu[o], lv = a.logvar[o];
-          dm = g + klw * m;
-          dl = klw * 0.5f * (expf(lv) - 1.f);
-          if (a.eps) dl += g * a.eps[o] * 0.5f * expf(0.5f * lv);
+          reparam_kl_bwd_elem(klw, m, lv, g, a.eps, o, &dm, &dl);
           if (a.dmu_x) dm += a.dmu_x[o];
           if (a.dlv_x) dl += a.dlv_x[o];
           a.dml[(long)(row0 + r) * D2 + 2 * d] = dm;

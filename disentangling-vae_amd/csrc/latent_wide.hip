@@ -12,31 +12,6 @@
 
 namespace dvae {
 
-#define LOG2PI_W 1.8378770664093453f
-
-// math.py:66-72 with M+1 == B: column 0 <- 1/N, column 1 <- strat, then W[M-1,0] <- strat   (= log_w_ij of loss.hip)
-__device__ __forceinline__ float log_w_ij_w(int i, int j, int Bg, float lN, float lS, float lM) {
-  if (j == 0) return (i == Bg - 2) ? lS : lN;
-  if (j == 1) return lS;
-  return lM;
-}
-
-// fixed-order sum / max over the 256 threads of a workgroup (4 waves); every thread gets the result.  `red`: 4 floats of LDS.
-__device__ __forceinline__ float block_sum_w(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();                              // `red` may still be read from a previous use
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ float block_max_w(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
 // ---- reparameterisation (vae.py:52-71), elementwise; ml[B,2D] interleaved (encoders.py:87) ----------------------------
 __global__ void k_reparam_wide(const float* __restrict__ ml, const float* __restrict__ eps, float* __restrict__ mu,
                                float* __restrict__ logvar, float* __restrict__ z, long n, int D) {
@@ -57,9 +32,9 @@ __global__ __launch_bounds__(256) void k_kl_cols_wide(const float* __restrict__ 
   float acc = 0.f;
   for (int b = threadIdx.x; b < B; b += 256) {
     const float m = mu[(long)b * D + d], lv = logvar[(long)b * D + d];
-    acc += 0.5f * (-1.f - lv + m * m + expf(lv));
+    acc += kl_elem(m, lv);
   }
-  const float t = block_sum_w(acc, red);
+  const float t = block_sum4(acc, red);
   if (threadIdx.x == 0) kl[d] = t * coef[DVAE_C_INV_B];
 }
 
@@ -74,13 +49,13 @@ __global__ __launch_bounds__(256) void k_tcw_joint(const float* __restrict__ z, 
   const int j = blockIdx.x * 256 + threadIdx.x;
   const int il = blockIdx.y, i = row0 + il;
   if (j >= Bg) return;
-  const float lN = is_mss ? log_w[0] : 0.f, lS = is_mss ? log_w[1] : 0.f, lM = is_mss ? log_w[2] : 0.f;
-  const float lw = log_w_ij_w(i, j, Bg, lN, lS, lM);
+  const LogW w = load_log_w(is_mss, log_w);
+  const float lw = log_w_ij(i, j, Bg, w);
   const float* muT = tmp; const float* cT = tmp + (long)D * Bg; const float* ivT = tmp + (long)2 * D * Bg;
   float acc = 0.f;
   for (int d = 0; d < D; ++d) {
     const float diff = z[(long)i * D + d] - muT[(long)d * Bg + j];
-    const float ld = (cT[(long)d * Bg + j] - 0.5f * (diff * diff * ivT[(long)d * Bg + j])) + lw;
+    const float ld = gauss_logdens(diff, cT[(long)d * Bg + j], ivT[(long)d * Bg + j]) + lw;
     acc += ld;
   }
   S[(long)il * Bg + j] = acc;
@@ -96,24 +71,24 @@ __global__ __launch_bounds__(256) void k_tcw_rowstats(const float* __restrict__ 
   __shared__ float red[4];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int il = blockIdx.x, i = row0 + il;
-  const float lN = is_mss ? log_w[0] : 0.f, lS = is_mss ? log_w[1] : 0.f, lM = is_mss ? log_w[2] : 0.f;
+  const LogW w = load_log_w(is_mss, log_w);
   const float* muT = tmp; const float* cT = tmp + (long)D * Bg; const float* ivT = tmp + (long)2 * D * Bg;
   const float* Srow = S + (long)il * Bg;
   // joint: logsumexp_j S[il][j] -- maximum first, then one exponential per column
   float m = -INFINITY;
   for (int j = tid; j < Bg; j += 256) m = fmaxf(m, Srow[j]);
-  const float M = block_max_w(m, red);
+  const float M = block_max4(m, red);
   const float sh = M > -INFINITY ? M : 0.f;     // a row of -inf: exp(-inf - 0) = 0 instead of exp(-inf + inf) = NaN
   float s = 0.f;
   for (int j = tid; j < Bg; j += 256) s += __expf(Srow[j] - sh);
-  const float lqz = sh + logf(block_sum_w(s, red));
+  const float lqz = sh + logf(block_sum4(s, red));
   // marginals: wave wv owns the dimensions wv, wv + 4, ...
   for (int d = wv; d < D; d += 4) {
     const float zi = z[(long)i * D + d];
     float md = -INFINITY;
     for (int j = lane; j < Bg; j += 64) {
       const float diff = zi - muT[(long)d * Bg + j];
-      const float ld = (cT[(long)d * Bg + j] - 0.5f * (diff * diff * ivT[(long)d * Bg + j])) + log_w_ij_w(i, j, Bg, lN, lS, lM);
+      const float ld = gauss_logdens(diff, cT[(long)d * Bg + j], ivT[(long)d * Bg + j]) + log_w_ij(i, j, Bg, w);
       md = fmaxf(md, ld);
     }
     md = wave_max(md);
@@ -121,7 +96,7 @@ __global__ __launch_bounds__(256) void k_tcw_rowstats(const float* __restrict__ 
     float sd = 0.f;
     for (int j = lane; j < Bg; j += 64) {
       const float diff = zi - muT[(long)d * Bg + j];
-      const float ld = (cT[(long)d * Bg + j] - 0.5f * (diff * diff * ivT[(long)d * Bg + j])) + log_w_ij_w(i, j, Bg, lN, lS, lM);
+      const float ld = gauss_logdens(diff, cT[(long)d * Bg + j], ivT[(long)d * Bg + j]) + log_w_ij(i, j, Bg, w);
       sd += __expf(ld - shd);
     }
     sd = wave_sum(sd);
@@ -134,8 +109,8 @@ __global__ __launch_bounds__(256) void k_tcw_rowstats(const float* __restrict__ 
     for (int d = 0; d < D; ++d) {
       const float zi = z[(long)i * D + d], mm = mu[(long)i * D + d], l = lv[(long)i * D + d];
       const float diff = zi - mm;
-      log_qzCx += -0.5f * (LOG2PI_W + l) - 0.5f * (diff * diff * expf(-l));
-      log_pz += -0.5f * LOG2PI_W - 0.5f * (zi * zi);
+      log_qzCx += gauss_logdens_lv(diff, l);
+      log_pz += -0.5f * LOG2PI - 0.5f * (zi * zi);
       const float lse = lse_d[d];
       rs[4 + d] = lse;
       log_prod += lse;
@@ -158,10 +133,8 @@ __global__ __launch_bounds__(256) void k_tcw_bwd_rows(const float* __restrict__ 
   const int il = blockIdx.x, d = blockIdx.y * 4 + wv;
   if (d >= D) return;                           // (no workgroup barrier below)
   const int i = row0 + il;
-  const float lN = is_mss ? log_w[0] : 0.f, lS = is_mss ? log_w[1] : 0.f, lM = is_mss ? log_w[2] : 0.f;
-  const float alpha = coef[DVAE_C_ALPHA], beta = coef[DVAE_C_BETA], gam = coef[DVAE_C_GAMMA] * coef[DVAE_C_ANNEAL];
-  const float invB = 1.f / (float)Bg;
-  const float cP = (beta - alpha) * invB, cQ = (gam - beta) * invB;
+  const LogW w = load_log_w(is_mss, log_w);
+  const TcCoef k = load_tc_coef(coef, Bg);
   const float* muT = tmp + (long)d * Bg; const float* cT = tmp + (long)(D + d) * Bg; const float* ivT = tmp + (long)(2 * D + d) * Bg;
   const float* Srow = S + (long)il * Bg;
   const float* rs = rowstats + (long)il * rstride;
@@ -172,15 +145,15 @@ __global__ __launch_bounds__(256) void k_tcw_bwd_rows(const float* __restrict__ 
     const float iv = ivT[j];
     const float diff = zi - muT[j];
     const float r = diff * iv;
-    const float ld = (cT[j] - 0.5f * (diff * diff * iv)) + log_w_ij_w(i, j, Bg, lN, lS, lM);
-    const float G = cP * __expf(Srow[j] - lqz) + cQ * __expf(ld - lse);
+    const float ld = gauss_logdens(diff, cT[j], iv) + log_w_ij(i, j, Bg, w);
+    const float G = k.cP * __expf(Srow[j] - lqz) + k.cQ * __expf(ld - lse);
     g -= G * r;
   }
   g = wave_sum(g);
   if (lane == 0) {
     // diagonal terms: alpha * log q(z_i|x_i) / B  and  -gamma' * log p(z_i) / B
     const float r = (zi - mu[(long)i * D + d]) * expf(-lv[(long)i * D + d]);
-    dz[(long)il * D + d] = g - alpha * invB * r + gam * invB * zi;
+    dz[(long)il * D + d] = g - k.alpha * k.invB * r + k.gam * k.invB * zi;
   }
 }
 
@@ -194,28 +167,26 @@ __global__ __launch_bounds__(256) void k_tcw_bwd_cols(const float* __restrict__ 
   const int j = blockIdx.x * 256 + threadIdx.x;
   const int d = blockIdx.y;
   if (j >= Bg) return;
-  const float lN = is_mss ? log_w[0] : 0.f, lS = is_mss ? log_w[1] : 0.f, lM = is_mss ? log_w[2] : 0.f;
-  const float alpha = coef[DVAE_C_ALPHA], beta = coef[DVAE_C_BETA], gam = coef[DVAE_C_GAMMA] * coef[DVAE_C_ANNEAL];
-  const float invB = 1.f / (float)Bg;
-  const float cP = (beta - alpha) * invB, cQ = (gam - beta) * invB;
+  const LogW w = load_log_w(is_mss, log_w);
+  const TcCoef k = load_tc_coef(coef, Bg);
   const float mj = mu[(long)j * D + d], lj = lv[(long)j * D + d];
-  const float ivj = expf(-lj), cj = -0.5f * (LOG2PI_W + lj);
+  const float ivj = expf(-lj), cj = gauss_c(lj);
   float gm = 0.f, gl = 0.f;
   for (int il = 0; il < Bl; ++il) {
     const int i = row0 + il;
     const float* rs = rowstats + (long)il * rstride;
     const float diff = z[(long)i * D + d] - mj;
     const float r = diff * ivj;
-    const float ld = (cj - 0.5f * (diff * diff * ivj)) + log_w_ij_w(i, j, Bg, lN, lS, lM);
-    const float G = cP * __expf(S[(long)il * Bg + j] - rs[1]) + cQ * __expf(ld - rs[4 + d]);
+    const float ld = gauss_logdens(diff, cj, ivj) + log_w_ij(i, j, Bg, w);
+    const float G = k.cP * __expf(S[(long)il * Bg + j] - rs[1]) + k.cQ * __expf(ld - rs[4 + d]);
     gm += G * r;
     gl += G * (-0.5f + 0.5f * r * diff);
   }
   if (j >= row0 && j < row0 + Bl) {             // diagonal term alpha * log q(z_j|x_j) / B
     const float diff = z[(long)j * D + d] - mj;
     const float r = diff * ivj;
-    gm += alpha * invB * r;
-    gl += alpha * invB * (-0.5f + 0.5f * r * diff);
+    gm += k.alpha * k.invB * r;
+    gl += k.alpha * k.invB * (-0.5f + 0.5f * r * diff);
   }
   dmu[(long)j * D + d] = gm;
   dlv[(long)j * D + d] = gl;

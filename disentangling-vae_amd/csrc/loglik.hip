@@ -59,7 +59,7 @@ __global__ __launch_bounds__(RR_THREADS) void k_recon_rows(const float* __restri
   }
   __syncthreads();
   if (tid < nr) {
-    const float v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+    const float v = block_sum4_read(red, tid);
     if (nslice == 1) rec_rows[row0 + tid] = v;
     else part[(row0 + tid) * nslice + c] = v;
   }
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(64 * IW_WAVES) void k_iw_loglik(const float* __rest
   if (kl) {
     for (int d = lane; d < D; d += 64) {
       const float m = mu[i * D + d], lv = logvar[i * D + d];
-      kl[i * D + d] = 0.5f * (-1.f - lv + m * m + expf(lv));
+      kl[i * D + d] = kl_elem(m, lv);
     }
   }
   if (!state) return;

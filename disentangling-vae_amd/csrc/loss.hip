@@ -7,8 +7,6 @@
 
 namespace dvae {
 
-#define LOG2PI 1.8378770664093453f
-
 // ---- reparam + KL ----------------------------------------------------------------------------
 // elementwise part over B*D threads; the per-dim KL sums go through per-workgroup partials
 // ([64][16] floats, fixed order) and a one-wave finishing kernel
@@ -31,7 +29,7 @@ __global__ __launch_bounds__(256) void k_reparam_kl_fwd(const float* __restrict_
         float zz = m;
         if (eps) zz = m + expf(0.5f * lv) * eps[(long)b * D + d];
         z[(long)b * D + d] = zz;
-        kl[d] += 0.5f * (-1.f - lv + m * m + expf(lv));
+        kl[d] += kl_elem(m, lv);
       }
     }
   }
@@ -43,7 +41,7 @@ __global__ __launch_bounds__(256) void k_reparam_kl_fwd(const float* __restrict_
     if (lane == 0) red[wv][d] = v;
   }
   __syncthreads();
-  if (tid < 16) kl_part[blockIdx.x * 16 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+  if (tid < 16) kl_part[blockIdx.x * 16 + tid] = block_sum4_read(red, tid);
 }
 
 // fixed-order sum of `nblk` per-workgroup KL partial blocks ([nblk][16] floats) by a 256-thread workgroup: thread t adds
@@ -86,9 +84,8 @@ __global__ void k_reparam_kl_bwd(const float* __restrict__ dz, const float* __re
   float g = dz ? dz[idx] : 0.f;
   if (dz2) g += dz2[idx];                 // gradients reaching z by other routes (TC estimator, discriminator)
   if (dz3) g += dz3[idx];
-  float dm = g + klw * m;
-  float dl = klw * 0.5f * (expf(lv) - 1.f);
-  if (eps) dl += g * eps[idx] * 0.5f * expf(0.5f * lv);
+  float dm, dl;
+  reparam_kl_bwd_elem(klw, m, lv, g, eps, idx, &dm, &dl);
   if (dmu_x) dm += dmu_x[idx];
   if (dlv_x) dl += dlv_x[idx];
   const long b = idx / D; const int d = idx % D;
@@ -122,28 +119,11 @@ __global__ __launch_bounds__(256) void k_recon_loss(const float* __restrict__ re
   float v = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  if (threadIdx.x == 0) partials[blockIdx.x] = block_sum4_read(red);
 }
 
 // ---- beta-TCVAE ------------------------------------------------------------------------------
 #define BTC_WG_MAX_ROWS 512      // local rows up to which the backward passes run a workgroup per row / column
-__device__ __forceinline__ float log_w_ij(int i, int j, int Bg, float lN, float lS, float lM) {
-  // math.py:66-72 with M+1 == B: column 0 <- 1/N, column 1 <- strat, then W[M-1,0] <- strat
-  if (j == 0) return (i == Bg - 2) ? lS : lN;
-  if (j == 1) return lS;
-  return lM;
-}
-
-// online logsumexp (branch-free push: the wave never diverges; __expf = v_exp_f32(x*log2e))
-__device__ __forceinline__ void lse_push(float& m, float& s, float v) {
-  const float mn = fmaxf(m, v);
-  s = s * __expf(m - mn) + __expf(v - mn);
-  m = mn;
-}
-__device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
-  if (m2 > m) { s = s * __expf(m - m2) + s2; m = m2; }
-  else if (m2 > -INFINITY) { s += s2 * __expf(m2 - m); }
-}
 
 // per-column constants of the Gaussian log-density, TRANSPOSED ([D][Bg]) so that the lanes of a wave
 // (consecutive columns j) read 256 contiguous bytes:  muT = mu, cT = -0.5 (log 2pi + logvar),
@@ -155,7 +135,7 @@ __global__ void k_btcvae_prep(const float* __restrict__ mu, const float* __restr
   const int j = idx / D, d = idx % D;
   const float l = lv[idx];
   tmp[(long)d * Bg + j] = mu[idx];
-  tmp[(long)(D + d) * Bg + j] = -0.5f * (LOG2PI + l);
+  tmp[(long)(D + d) * Bg + j] = gauss_c(l);
   tmp[(long)(2 * D + d) * Bg + j] = expf(-l);
 }
 
@@ -172,7 +152,7 @@ __global__ __launch_bounds__(256) void k_btcvae_fwd(const float* __restrict__ z,
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int il = blockIdx.x;
   const int i = row0 + il;
-  const float lN = is_mss ? log_w[0] : 0.f, lS = is_mss ? log_w[1] : 0.f, lM = is_mss ? log_w[2] : 0.f;
+  const LogW w = load_log_w(is_mss, log_w);
   const float* muT = tmp; const float* cT = tmp + (long)D * Bg; const float* ivT = tmp + (long)2 * D * Bg;
   float zi[DM];
 #pragma unroll
@@ -182,12 +162,12 @@ __global__ __launch_bounds__(256) void k_btcvae_fwd(const float* __restrict__ z,
   for (int d = 0; d < DM; ++d) if (DT != 0 || d < D) { md[d] = -INFINITY; sd[d] = 0.f; }
 #pragma unroll 2
   for (int j = threadIdx.x; j < Bg; j += 256) {
-    const float lw = log_w_ij(i, j, Bg, lN, lS, lM);
+    const float lw = log_w_ij(i, j, Bg, w);
     float S = 0.f;
 #pragma unroll
     for (int d = 0; d < DM; ++d) if (DT != 0 || d < D) {
       const float diff = zi[d] - muT[(long)d * Bg + j];
-      const float ld = (cT[(long)d * Bg + j] - 0.5f * (diff * diff * ivT[(long)d * Bg + j])) + lw;
+      const float ld = gauss_logdens(diff, cT[(long)d * Bg + j], ivT[(long)d * Bg + j]) + lw;
       S += ld;
       lse_push(md[d], sd[d], ld);
     }
@@ -229,7 +209,7 @@ __global__ __launch_bounds__(256) void k_btcvae_fwd(const float* __restrict__ z,
     for (int d = 0; d < DM; ++d) if (DT != 0 || d < D) {
       const float m = mu[(long)i * D + d], l = lv[(long)i * D + d];
       const float diff = zi[d] - m;
-      log_qzCx += -0.5f * (LOG2PI + l) - 0.5f * (diff * diff * expf(-l));
+      log_qzCx += gauss_logdens_lv(diff, l);
       log_pz += -0.5f * LOG2PI - 0.5f * (zi[d] * zi[d]);
       const float lse = fin[1 + d];
       rs[4 + d] = lse;
@@ -256,10 +236,8 @@ __global__ __launch_bounds__(256) void k_btcvae_bwd_rows(const float* __restrict
   const int il = blockIdx.x * 4 + wv;
   if (il >= Bl) return;
   const int i = row0 + il;
-  const float lN = is_mss ? log_w[0] : 0.f, lS = is_mss ? log_w[1] : 0.f, lM = is_mss ? log_w[2] : 0.f;
-  const float alpha = coef[DVAE_C_ALPHA], beta = coef[DVAE_C_BETA], gam = coef[DVAE_C_GAMMA] * coef[DVAE_C_ANNEAL];
-  const float invB = 1.f / (float)Bg;
-  const float cP = (beta - alpha) * invB, cQ = (gam - beta) * invB;
+  const LogW w = load_log_w(is_mss, log_w);
+  const TcCoef k = load_tc_coef(coef, Bg);
   const float* muT = tmp; const float* cT = tmp + (long)D * Bg; const float* ivT = tmp + (long)2 * D * Bg;
   const float* rs = rowstats + (long)il * DVAE_ROWSTATS;
   const float lqz = rs[1];
@@ -268,7 +246,7 @@ __global__ __launch_bounds__(256) void k_btcvae_bwd_rows(const float* __restrict
   for (int d = 0; d < DM; ++d) if (DT != 0 || d < D) { zi[d] = z[(long)i * D + d]; lse[d] = rs[4 + d]; g[d] = 0.f; }
 #pragma unroll 2
   for (int j = lane; j < Bg; j += 64) {
-    const float lw = log_w_ij(i, j, Bg, lN, lS, lM);
+    const float lw = log_w_ij(i, j, Bg, w);
     float ld[DM], r[DM];
     float S = 0.f;
 #pragma unroll
@@ -276,13 +254,13 @@ __global__ __launch_bounds__(256) void k_btcvae_bwd_rows(const float* __restrict
       const float iv = ivT[(long)d * Bg + j];
       const float diff = zi[d] - muT[(long)d * Bg + j];
       r[d] = diff * iv;
-      ld[d] = (cT[(long)d * Bg + j] - 0.5f * (diff * diff * iv)) + lw;
+      ld[d] = gauss_logdens(diff, cT[(long)d * Bg + j], iv) + lw;
       S += ld[d];
     }
     const float P = __expf(S - lqz);
 #pragma unroll
     for (int d = 0; d < DM; ++d) if (DT != 0 || d < D) {
-      const float G = cP * P + cQ * __expf(ld[d] - lse[d]);
+      const float G = k.cP * P + k.cQ * __expf(ld[d] - lse[d]);
       g[d] -= G * r[d];
     }
   }
@@ -294,7 +272,7 @@ __global__ __launch_bounds__(256) void k_btcvae_bwd_rows(const float* __restrict
       // diagonal terms: alpha * log q(z_i|x_i) / B  and  -gamma' * log p(z_i) / B
       const float m = mu[(long)i * D + d], l = lv[(long)i * D + d];
       const float r = (zi[d] - m) * expf(-l);
-      dz[(long)il * D + d] = g[d] - alpha * invB * r + gam * invB * zi[d];
+      dz[(long)il * D + d] = g[d] - k.alpha * k.invB * r + k.gam * k.invB * zi[d];
     }
   }
 }
@@ -311,10 +289,8 @@ __global__ __launch_bounds__(256) void k_btcvae_bwd_cols(const float* __restrict
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int j = blockIdx.x * 4 + wv;
   if (j >= Bg) return;
-  const float lN = is_mss ? log_w[0] : 0.f, lS = is_mss ? log_w[1] : 0.f, lM = is_mss ? log_w[2] : 0.f;
-  const float alpha = coef[DVAE_C_ALPHA], beta = coef[DVAE_C_BETA], gam = coef[DVAE_C_GAMMA] * coef[DVAE_C_ANNEAL];
-  const float invB = 1.f / (float)Bg;
-  const float cP = (beta - alpha) * invB, cQ = (gam - beta) * invB;
+  const LogW w = load_log_w(is_mss, log_w);
+  const TcCoef k = load_tc_coef(coef, Bg);
   float mj[DM], lj[DM], ivj[DM], gm[DM], gl[DM];
 #pragma unroll
   for (int d = 0; d < DM; ++d) if (DT != 0 || d < D) {
@@ -324,20 +300,21 @@ __global__ __launch_bounds__(256) void k_btcvae_bwd_cols(const float* __restrict
   for (int il = lane; il < Bl; il += 64) {
     const int i = row0 + il;
     const float* rs = rowstats + (long)il * DVAE_ROWSTATS;
-    const float lw = log_w_ij(i, j, Bg, lN, lS, lM);
+    const float lw = log_w_ij(i, j, Bg, w);
     float ld[DM], r[DM], diff[DM];
     float S = 0.f;
 #pragma unroll
     for (int d = 0; d < DM; ++d) if (DT != 0 || d < D) {
       diff[d] = z[(long)i * D + d] - mj[d];
       r[d] = diff[d] * ivj[d];
-      ld[d] = (-0.5f * (LOG2PI + lj[d]) - 0.5f * (diff[d] * diff[d] * ivj[d])) + lw;
+      const float c = gauss_c(lj[d]);
+      ld[d] = gauss_logdens(diff[d], c, ivj[d]) + lw;
       S += ld[d];
     }
     const float P = __expf(S - rs[1]);
 #pragma unroll
     for (int d = 0; d < DM; ++d) if (DT != 0 || d < D) {
-      const float G = cP * P + cQ * __expf(ld[d] - rs[4 + d]);
+      const float G = k.cP * P + k.cQ * __expf(ld[d] - rs[4 + d]);
       gm[d] += G * r[d];
       gl[d] += G * (-0.5f + 0.5f * r[d] * diff[d]);
     }
@@ -352,8 +329,8 @@ __global__ __launch_bounds__(256) void k_btcvae_bwd_cols(const float* __restrict
       if (local) {  // diagonal term alpha * log q(z_j|x_j) / B
         const float diff = z[(long)j * D + d] - mj[d];
         const float r = diff * ivj[d];
-        a += alpha * invB * r;
-        b += alpha * invB * (-0.5f + 0.5f * r * diff);
+        a += k.alpha * k.invB * r;
+        b += k.alpha * k.invB * (-0.5f + 0.5f * r * diff);
       }
       dmu[(long)j * D + d] = a;
       dlv[(long)j * D + d] = b;
@@ -378,10 +355,8 @@ __device__ __forceinline__ void btcvae_bwd_rows_wg_body(int il, const float* __r
   __shared__ float red[4][DM];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int i = row0 + il;
-  const float lN = is_mss ? log_w[0] : 0.f, lS = is_mss ? log_w[1] : 0.f, lM = is_mss ? log_w[2] : 0.f;
-  const float alpha = coef[DVAE_C_ALPHA], beta = coef[DVAE_C_BETA], gam = coef[DVAE_C_GAMMA] * coef[DVAE_C_ANNEAL];
-  const float invB = 1.f / (float)Bg;
-  const float cP = (beta - alpha) * invB, cQ = (gam - beta) * invB;
+  const LogW w = load_log_w(is_mss, log_w);
+  const TcCoef k = load_tc_coef(coef, Bg);
   const float* muT = tmp; const float* cT = tmp + (long)D * Bg; const float* ivT = tmp + (long)2 * D * Bg;
   const float* rs = rowstats + (long)il * DVAE_ROWSTATS;
   const float lqz = rs[1];
@@ -390,7 +365,7 @@ __device__ __forceinline__ void btcvae_bwd_rows_wg_body(int il, const float* __r
   for (int d = 0; d < DM; ++d) if (DT != 0 || d < D) { zi[d] = z[(long)i * D + d]; lse[d] = rs[4 + d]; g[d] = 0.f; }
 #pragma unroll 2
   for (int j = threadIdx.x; j < Bg; j += 256) {
-    const float lw = log_w_ij(i, j, Bg, lN, lS, lM);
+    const float lw = log_w_ij(i, j, Bg, w);
     float ld[DM], r[DM];
     float S = 0.f;
 #pragma unroll
@@ -398,13 +373,13 @@ __device__ __forceinline__ void btcvae_bwd_rows_wg_body(int il, const float* __r
       const float iv = ivT[(long)d * Bg + j];
       const float diff = zi[d] - muT[(long)d * Bg + j];
       r[d] = diff * iv;
-      ld[d] = (cT[(long)d * Bg + j] - 0.5f * (diff * diff * iv)) + lw;
+      ld[d] = gauss_logdens(diff, cT[(long)d * Bg + j], iv) + lw;
       S += ld[d];
     }
     const float P = __expf(S - lqz);
 #pragma unroll
     for (int d = 0; d < DM; ++d) if (DT != 0 || d < D) {
-      const float G = cP * P + cQ * __expf(ld[d] - lse[d]);
+      const float G = k.cP * P + k.cQ * __expf(ld[d] - lse[d]);
       g[d] -= G * r[d];
     }
   }
@@ -417,11 +392,11 @@ __device__ __forceinline__ void btcvae_bwd_rows_wg_body(int il, const float* __r
   const int d = threadIdx.x;
   if (d < D) {
     // diagonal terms: alpha * log q(z_i|x_i) / B  and  -gamma' * log p(z_i) / B
-    const float gs = (red[0][d] + red[1][d]) + (red[2][d] + red[3][d]);
+    const float gs = block_sum4_read(red, d);
     const float zd = z[(long)i * D + d];
     const float m = mu[(long)i * D + d], l = lv[(long)i * D + d];
     const float r = (zd - m) * expf(-l);
-    dz[(long)il * D + d] = gs - alpha * invB * r + gam * invB * zd;
+    dz[(long)il * D + d] = gs - k.alpha * k.invB * r + k.gam * k.invB * zd;
   }
 }
 
@@ -436,10 +411,8 @@ __device__ __forceinline__ void btcvae_bwd_cols_wg_body(int j, const float* __re
   const int D = DT ? DT : Drt;
   __shared__ float red[4][2 * DM];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const float lN = is_mss ? log_w[0] : 0.f, lS = is_mss ? log_w[1] : 0.f, lM = is_mss ? log_w[2] : 0.f;
-  const float alpha = coef[DVAE_C_ALPHA], beta = coef[DVAE_C_BETA], gam = coef[DVAE_C_GAMMA] * coef[DVAE_C_ANNEAL];
-  const float invB = 1.f / (float)Bg;
-  const float cP = (beta - alpha) * invB, cQ = (gam - beta) * invB;
+  const LogW w = load_log_w(is_mss, log_w);
+  const TcCoef k = load_tc_coef(coef, Bg);
   float mj[DM], lj[DM], ivj[DM], gm[DM], gl[DM];
 #pragma unroll
   for (int d = 0; d < DM; ++d) if (DT != 0 || d < D) {
@@ -449,20 +422,21 @@ __device__ __forceinline__ void btcvae_bwd_cols_wg_body(int j, const float* __re
   for (int il = threadIdx.x; il < Bl; il += 256) {
     const int i = row0 + il;
     const float* rs = rowstats + (long)il * DVAE_ROWSTATS;
-    const float lw = log_w_ij(i, j, Bg, lN, lS, lM);
+    const float lw = log_w_ij(i, j, Bg, w);
     float ld[DM], r[DM], diff[DM];
     float S = 0.f;
 #pragma unroll
     for (int d = 0; d < DM; ++d) if (DT != 0 || d < D) {
       diff[d] = z[(long)i * D + d] - mj[d];
       r[d] = diff[d] * ivj[d];
-      ld[d] = (-0.5f * (LOG2PI + lj[d]) - 0.5f * (diff[d] * diff[d] * ivj[d])) + lw;
+      const float c = gauss_c(lj[d]);
+      ld[d] = gauss_logdens(diff[d], c, ivj[d]) + lw;
       S += ld[d];
     }
     const float P = __expf(S - rs[1]);
 #pragma unroll
     for (int d = 0; d < DM; ++d) if (DT != 0 || d < D) {
-      const float G = cP * P + cQ * __expf(ld[d] - rs[4 + d]);
+      const float G = k.cP * P + k.cQ * __expf(ld[d] - rs[4 + d]);
       gm[d] += G * r[d];
       gl[d] += G * (-0.5f + 0.5f * r[d] * diff[d]);
     }
@@ -475,14 +449,13 @@ __device__ __forceinline__ void btcvae_bwd_cols_wg_body(int j, const float* __re
   __syncthreads();
   const int d = threadIdx.x;
   if (d < D) {
-    float a = (red[0][2 * d] + red[1][2 * d]) + (red[2][2 * d] + red[3][2 * d]);
-    float b = (red[0][2 * d + 1] + red[1][2 * d + 1]) + (red[2][2 * d + 1] + red[3][2 * d + 1]);
+    float a = block_sum4_read(red, 2 * d), b = block_sum4_read(red, 2 * d + 1);
     if (j >= row0 && j < row0 + Bl) {  // diagonal term alpha * log q(z_j|x_j) / B
       const float m = mu[(long)j * D + d], iv = expf(-lv[(long)j * D + d]);
       const float diff = z[(long)j * D + d] - m;
       const float r = diff * iv;
-      a += alpha * invB * r;
-      b += alpha * invB * (-0.5f + 0.5f * r * diff);
+      a += k.alpha * k.invB * r;
+      b += k.alpha * k.invB * (-0.5f + 0.5f * r * diff);
     }
     dmu[(long)j * D + d] = a;
     dlv[(long)j * D + d] = b;
@@ -538,7 +511,7 @@ __global__ __launch_bounds__(256) void k_disc_losses(const float* __restrict__ l
   float v0 = wave_sum(s_tc), v1 = wave_sum(s_ce0), v2 = wave_sum(s_ce1);
   if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = v0; red[1][threadIdx.x >> 6] = v1; red[2][threadIdx.x >> 6] = v2; }
   __syncthreads();
-  if (threadIdx.x < 3) sums[threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+  if (threadIdx.x < 3) sums[threadIdx.x] = block_sum4_read(red[threadIdx.x]);
   if (threadIdx.x == 3) sums[3] = 0.f;
 }
 
@@ -575,7 +548,7 @@ __device__ __forceinline__ void loss_pack_body(const float* __restrict__ rec_par
   }
   __syncthreads();
   if (tid < 5) {
-    const float t = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+    const float t = block_sum4_read(red[tid]);
     packed[tid == 0 ? 0 : 16 + tid] = t;          // [0] rec, [17..20] rowstat sums
   }
   if (tid < 16) {
@@ -675,7 +648,7 @@ __global__ __launch_bounds__(256) void k_reduce_sum(const float* __restrict__ sr
   const float v = wave_sum(a);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
-  if (threadIdx.x == 0) dst[0] = scale * ((red[0] + red[1]) + (red[2] + red[3]));
+  if (threadIdx.x == 0) dst[0] = scale * block_sum4_read(red);
 }
 
 // ToTensor of a uint8 image batch (utils/datasets.py:207-209): dst = float(src) / 255, 16 pixels per thread
@@ -764,18 +737,23 @@ int launch_recon_loss(const float* recon, const float* target, long n, int dist,
   return 0;
 }
 
+// latent_dim 10 (every reference experiment) has fully unrolled kernels <10>; any other D <= DVAE_MAX_D runs the same code
+// <0> with the dimension as a run-time bound (the kernels' last argument)
+#define BTC_LAUNCH_D(kern, grid, ...)                                                         \
+  do {                                                                                        \
+    if (D == 10) hipLaunchKernelGGL(kern<10>, grid, dim3(256), 0, s, __VA_ARGS__, D);         \
+    else hipLaunchKernelGGL(kern<0>, grid, dim3(256), 0, s, __VA_ARGS__, D);                  \
+    DVAE_CHECK_LAUNCH();                                                                      \
+  } while (0)
+
 int launch_btcvae_fwd(const float* z, const float* mu, const float* lv, int Bg, int D, int row0, int Bl, int is_mss,
                       const float* log_w, float* tmp, float* rowstats, hipStream_t s) {
-  // latent_dim 10 (every reference experiment) has fully unrolled kernels; any other D <= 16 runs the same code with the
-  // dimension as a run-time bound; above: latent_wide.hip
   if (D < 1) return 1;
   const long n = (long)Bg * D;
   hipLaunchKernelGGL(k_btcvae_prep, dim3((n + 255) / 256), dim3(256), 0, s, mu, lv, Bg, D, tmp);
   DVAE_CHECK_LAUNCH();
-  if (D > DVAE_MAX_D) return launch_btcvae_fwd_wide(z, mu, lv, Bg, D, row0, Bl, is_mss, log_w, tmp, rowstats, s);
-  if (D == 10) hipLaunchKernelGGL(k_btcvae_fwd<10>, dim3(Bl), dim3(256), 0, s, z, mu, lv, tmp, Bg, row0, Bl, is_mss, log_w, rowstats, D);
-  else hipLaunchKernelGGL(k_btcvae_fwd<0>, dim3(Bl), dim3(256), 0, s, z, mu, lv, tmp, Bg, row0, Bl, is_mss, log_w, rowstats, D);
-  DVAE_CHECK_LAUNCH();
+  if (D > DVAE_MAX_D) return launch_btcvae_fwd_wide(z, mu, lv, Bg, D, row0, Bl, is_mss, log_w, tmp, rowstats, s);   // latent_wide.hip
+  BTC_LAUNCH_D(k_btcvae_fwd, dim3(Bl), z, mu, lv, tmp, Bg, row0, Bl, is_mss, log_w, rowstats);
   return 0;
 }
 
@@ -788,23 +766,11 @@ int launch_btcvae_bwd(const float* z, const float* mu, const float* lv, const fl
   // a workgroup per row / column up to BTC_WG_MAX_ROWS local rows (both passes in one launch), a wave per row / column above:
   // see k_btcvae_bwd_wg
   if (Bl <= BTC_WG_MAX_ROWS) {
-    if (D == 10) hipLaunchKernelGGL(k_btcvae_bwd_wg<10>, dim3(Bl + Bg), dim3(256), 0, s, z, mu, lv, tmp, rowstats, Bg, row0, Bl, is_mss,
-                                    log_w, coef, dz, dmu, dlv, D);
-    else hipLaunchKernelGGL(k_btcvae_bwd_wg<0>, dim3(Bl + Bg), dim3(256), 0, s, z, mu, lv, tmp, rowstats, Bg, row0, Bl, is_mss, log_w,
-                            coef, dz, dmu, dlv, D);
-    DVAE_CHECK_LAUNCH();
+    BTC_LAUNCH_D(k_btcvae_bwd_wg, dim3(Bl + Bg), z, mu, lv, tmp, rowstats, Bg, row0, Bl, is_mss, log_w, coef, dz, dmu, dlv);
     return 0;
   }
-  if (D == 10) hipLaunchKernelGGL(k_btcvae_bwd_rows<10>, dim3((Bl + 3) / 4), dim3(256), 0, s, z, mu, lv, tmp, rowstats, Bg, row0, Bl,
-                                  is_mss, log_w, coef, dz, D);
-  else hipLaunchKernelGGL(k_btcvae_bwd_rows<0>, dim3((Bl + 3) / 4), dim3(256), 0, s, z, mu, lv, tmp, rowstats, Bg, row0, Bl,
-                          is_mss, log_w, coef, dz, D);
-  DVAE_CHECK_LAUNCH();
-  if (D == 10) hipLaunchKernelGGL(k_btcvae_bwd_cols<10>, dim3((Bg + 3) / 4), dim3(256), 0, s, z, mu, lv, rowstats, Bg, row0, Bl,
-                                  is_mss, log_w, coef, dmu, dlv, D);
-  else hipLaunchKernelGGL(k_btcvae_bwd_cols<0>, dim3((Bg + 3) / 4), dim3(256), 0, s, z, mu, lv, rowstats, Bg, row0, Bl,
-                          is_mss, log_w, coef, dmu, dlv, D);
-  DVAE_CHECK_LAUNCH();
+  BTC_LAUNCH_D(k_btcvae_bwd_rows, dim3((Bl + 3) / 4), z, mu, lv, tmp, rowstats, Bg, row0, Bl, is_mss, log_w, coef, dz);
+  BTC_LAUNCH_D(k_btcvae_bwd_cols, dim3((Bg + 3) / 4), z, mu, lv, rowstats, Bg, row0, Bl, is_mss, log_w, coef, dmu, dlv);
   return 0;
 }
 

@@ -13,7 +13,6 @@
 
 namespace dvae {
 
-#define LOG2PI_M 1.8378770664093453f
 #define ENT_CHUNK 16384          // data points per workgroup
 #define ENT_MAX_CHUNKS 64
 
@@ -24,7 +23,7 @@ __global__ void k_entropy_prep(const float* __restrict__ mu, const float* __rest
   const long n = idx / D; const int d = (int)(idx % D);
   const float l = lv[idx];
   tmp[(long)d * N + n] = mu[idx];
-  tmp[(long)(D + d) * N + n] = -0.5f * (LOG2PI_M + l);
+  tmp[(long)(D + d) * N + n] = gauss_c(l);
   tmp[(long)(2 * D + d) * N + n] = expf(-l);
 }
 
@@ -45,12 +44,11 @@ __global__ __launch_bounds__(256) void k_entropy_lse(const float* __restrict__ z
     float mx = m;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      const float diff = z - muT[n + u];
-      v[u] = cT[n + u] - 0.5f * (diff * diff * ivT[n + u]);        // log_density_gaussian, utils/math.py:48-50
+      v[u] = gauss_logdens(z - muT[n + u], cT[n + u], ivT[n + u]);
       mx = fmaxf(mx, v[u]);
     }
-    // every density of the block (and everything before it) can be -inf (exp(-logvar) overflowing): shift by 0 then, so
-    // that exp(-inf - shift) = 0 instead of exp(-inf + inf) = NaN; torch.logsumexp returns -inf for such a column too
+    // lse_fold8 (latent_math.h) and, in the tail, its one-value form, written out: through helpers this kernel's
+    // instructions came out in another order, and it is the one that runs for minutes
     const float sh = mx > -INFINITY ? mx : 0.f;
     float t = 0.f;
 #pragma unroll
@@ -59,8 +57,7 @@ __global__ __launch_bounds__(256) void k_entropy_lse(const float* __restrict__ z
     m = mx;
   }
   for (; n < n1; ++n) {
-    const float diff = z - muT[n];
-    const float v = cT[n] - 0.5f * (diff * diff * ivT[n]);
+    const float v = gauss_logdens(z - muT[n], cT[n], ivT[n]);
     const float mx = fmaxf(m, v);
     const float sh = mx > -INFINITY ? mx : 0.f;
     acc = acc * __expf(m - sh) + __expf(v - sh);
@@ -83,9 +80,7 @@ __global__ __launch_bounds__(256) void k_entropy_finish(const float* __restrict_
     float m = -INFINITY, acc = 0.f;
     for (int c = 0; c < chunks; ++c) {
       const float* p = part + (((long)c * D + d) * S + s) * 2;
-      const float m2 = p[0], a2 = p[1];
-      if (m2 > m) { acc = acc * __expf(m - m2) + a2; m = m2; }
-      else if (m2 > -INFINITY) { acc += a2 * __expf(m2 - m); }
+      m = lse_merge(m, acc, p[0], p[1]);
     }
     const float l = m + logf(acc);
     lse[(long)d * S + s] = l;
@@ -94,7 +89,7 @@ __global__ __launch_bounds__(256) void k_entropy_finish(const float* __restrict_
   float v = wave_sum(hs);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
-  if (threadIdx.x == 0) H[d] = ((red[0] + red[1]) + (red[2] + red[3])) / (float)S;
+  if (threadIdx.x == 0) H[d] = block_sum4_read(red) / (float)S;
 }
 
 static int entropy_chunks(long N) {

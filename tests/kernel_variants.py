@@ -143,12 +143,12 @@ VARIANTS = [
     _v("k_gdma<64, 64, 64, 3, 1, true, 0>", "dvae_linear_dgrad", "ceil(M / 64) * cols64 >= 192, ceil(M / 128) * cols64 < 224", "gemm_dma.hip:509", V + "test_discriminator_linear_at_the_tile_switches[1664]"),
     _v("k_gdma_wg<64, 3>", "dvae_linear_wgrad", "M >= 64, N % 4 == K % 4 == 0, >= 128 output tiles of 64x64", "gemm_dma.hip:527", V + "test_discriminator_linear_at_the_tile_switches[64]"),
     # ---- latent_wide.hip (D > DVAE_MAX_D = 16)
-    _v("k_tcw_joint", "dvae_btcvae_fwd", "D > 16", "latent_wide.hip:240", WL + "test_btcvae_fwd_bwd_wide[4-100-True-17]"),
-    _v("k_kl_cols_wide", "dvae_reparam_kl_fwd", "D > 16, kl_dim != NULL", "latent_wide.hip:231", WL + "test_reparam_kl_wide[2-17]"),
-    _v("k_reparam_wide", "dvae_reparam_kl_fwd", "D > 16", "latent_wide.hip:228", WL + "test_reparam_kl_wide[2-17]"),
-    _v("k_tcw_bwd_cols", "dvae_btcvae_bwd", "D > 16", "latent_wide.hip:256", WL + "test_btcvae_fwd_bwd_wide[4-100-True-17]"),
-    _v("k_tcw_bwd_rows", "dvae_btcvae_bwd", "D > 16", "latent_wide.hip:253", WL + "test_btcvae_fwd_bwd_wide[4-100-True-17]"),
-    _v("k_tcw_rowstats", "dvae_btcvae_fwd", "D > 16", "latent_wide.hip:242", WL + "test_btcvae_fwd_bwd_wide[4-100-True-17]"),
+    _v("k_tcw_joint", "dvae_btcvae_fwd", "D > 16", "latent_wide.hip:211", WL + "test_btcvae_fwd_bwd_wide[4-100-True-17]"),
+    _v("k_kl_cols_wide", "dvae_reparam_kl_fwd", "D > 16, kl_dim != NULL", "latent_wide.hip:202", WL + "test_reparam_kl_wide[2-17]"),
+    _v("k_reparam_wide", "dvae_reparam_kl_fwd", "D > 16", "latent_wide.hip:199", WL + "test_reparam_kl_wide[2-17]"),
+    _v("k_tcw_bwd_cols", "dvae_btcvae_bwd", "D > 16", "latent_wide.hip:227", WL + "test_btcvae_fwd_bwd_wide[4-100-True-17]"),
+    _v("k_tcw_bwd_rows", "dvae_btcvae_bwd", "D > 16", "latent_wide.hip:224", WL + "test_btcvae_fwd_bwd_wide[4-100-True-17]"),
+    _v("k_tcw_rowstats", "dvae_btcvae_fwd", "D > 16", "latent_wide.hip:213", WL + "test_btcvae_fwd_bwd_wide[4-100-True-17]"),
     # ---- linear.hip (try_fc32: contraction <= 512 and < 512 output tiles of 64x64; KP = the contraction rounded up)
     _v("k_fc32<128, false, 0>", "dvae_linear_fwd", "64 < K <= 128, K % 4 == 0", "linear.hip:429", V + "test_linear_at_the_contraction_length_switches[128]"),
     _v("k_fc32<128, true, 0>", "dvae_linear_dgrad", "64 < N <= 128, N % 4 == K % 4 == 0", "linear.hip:429", V + "test_linear_at_the_contraction_length_switches[68]"),
@@ -188,48 +188,48 @@ VARIANTS = [
     _v("k_recon_rows", "dvae_recon_rows", "always", "loglik.hip:158", "tests/test_gpu_loglik.py::test_recon_rows_vs_fp64_oracle[bernoulli-False-img0-1]"),
     _v("k_recon_rows_finish", "dvae_recon_rows", "more than one slice of a row", "loglik.hip:163", "tests/test_gpu_loglik.py::test_recon_rows_vs_fp64_oracle[bernoulli-False-img1-1]"),
     # ---- loss.hip
-    _v("k_add", "dvae_add", "always", "loss.hip:895", FC + "test_event_slots_order_a_late_consumer_after_marked_work"),
-    _v("k_axpby", "dvae_axpby", "always", "loss.hip:902", K + "test_data_parallel_glue_kernels"),
-    _v("k_set_coef", "dvae_set_coef", "always", "loss.hip:888", MC + "[set_coef]"),
-    _v("k_loss_pack", "dvae_loss_pack", "always", "loss.hip:827", K + "test_loss_epilogue_equals_pack_then_finalize[0-8]"),
-    _v("k_u8_to_f32", "dvae_u8_to_f32", "always", "loss.hip:880", U8 + "test_u8_to_f32_is_totensor"),
-    _v("k_btcvae_fwd<0>", "dvae_btcvae_fwd", "D <= 16, D != 10", "loss.hip:777", V + "test_btcvae_bwd_at_the_row_switch[513-6-True]"),
-    _v("k_btcvae_fwd<10>", "dvae_btcvae_fwd", "D == 10", "loss.hip:776", V + "test_btcvae_bwd_at_the_row_switch[513-10-True]"),
-    _v("k_recon_loss", "dvae_recon_loss, dvae_convT4s2_sigmoid_recon_fwd (two-pass shapes)", "always", "loss.hip:761", K + "test_recon_loss[bernoulli]"),
-    _v("k_reduce_sum", "dvae_reduce_sum", "always", "loss.hip:873", MC + "[reduce_sum-n7]"),
-    _v("k_swap_outer", "dvae_swap_outer", "always", "loss.hip:908", K + "test_data_parallel_glue_kernels"),
-    _v("k_btcvae_prep", "dvae_btcvae_fwd", "always", "loss.hip:773", V + "test_btcvae_bwd_at_the_row_switch[512-10-True]"),
-    _v("k_disc_losses", "dvae_disc_losses", "always", "loss.hip:820", K + "test_permute_dims_and_disc_losses"),
-    _v("k_sigmoid_bwd", "dvae_sigmoid_bwd", "always", "loss.hip:860", K + "test_recon_loss[bernoulli]"),
-    _v("k_permute_dims", "dvae_permute_dims", "always", "loss.hip:813", K + "test_permute_dims_and_disc_losses"),
-    _v("k_btcvae_bwd_wg<0>", "dvae_btcvae_bwd", "Bl <= 512, D <= 16, D != 10", "loss.hip:793", V + "test_btcvae_bwd_at_the_row_switch[512-6-True]"),
-    _v("k_btcvae_bwd_wg<10>", "dvae_btcvae_bwd", "Bl <= 512, D == 10", "loss.hip:791", V + "test_btcvae_bwd_at_the_row_switch[512-10-True]"),
-    _v("k_kl_normal_bwd", "dvae_kl_normal_bwd", "always", "loss.hip:867", MC + "[kl_normal_bwd-B7-D1]"),
-    _v("k_loss_epilogue", "dvae_loss_epilogue", "always", "loss.hip:846", K + "test_loss_epilogue_equals_pack_then_finalize[0-8]"),
-    _v("k_loss_finalize", "dvae_loss_finalize", "always", "loss.hip:853", K + "test_loss_epilogue_equals_pack_then_finalize[0-8]"),
-    _v("k_reparam_kl_bwd", "dvae_reparam_kl_bwd", "always", "loss.hip:753", K + "test_reparam_kl[8]"),
-    _v("k_reparam_kl_fwd", "dvae_reparam_kl_fwd", "D <= 16", "loss.hip:739", V + "test_reparam_kl_at_the_partial_block_switches[257]"),
-    _v("k_btcvae_bwd_cols<0>", "dvae_btcvae_bwd", "Bl > 512, D <= 16, D != 10", "loss.hip:805", V + "test_btcvae_bwd_at_the_row_switch[513-6-True]"),
-    _v("k_btcvae_bwd_cols<10>", "dvae_btcvae_bwd", "Bl > 512, D == 10", "loss.hip:803", V + "test_btcvae_bwd_at_the_row_switch[513-10-True]"),
-    _v("k_btcvae_bwd_rows<0>", "dvae_btcvae_bwd", "Bl > 512, D <= 16, D != 10", "loss.hip:800", V + "test_btcvae_bwd_at_the_row_switch[513-6-True]"),
-    _v("k_btcvae_bwd_rows<10>", "dvae_btcvae_bwd", "Bl > 512, D == 10", "loss.hip:798", V + "test_btcvae_bwd_at_the_row_switch[513-10-True]"),
-    _v("k_reparam_kl_finish", "dvae_reparam_kl_fwd, dvae_kl_finish", "kl_dim and coef given", "loss.hip:742", V + "test_reparam_kl_at_the_partial_block_switches[257]"),
+    _v("k_add", "dvae_add", "always", "loss.hip:861", FC + "test_event_slots_order_a_late_consumer_after_marked_work"),
+    _v("k_axpby", "dvae_axpby", "always", "loss.hip:868", K + "test_data_parallel_glue_kernels"),
+    _v("k_set_coef", "dvae_set_coef", "always", "loss.hip:854", MC + "[set_coef]"),
+    _v("k_loss_pack", "dvae_loss_pack", "always", "loss.hip:793", K + "test_loss_epilogue_equals_pack_then_finalize[0-8]"),
+    _v("k_u8_to_f32", "dvae_u8_to_f32", "always", "loss.hip:846", U8 + "test_u8_to_f32_is_totensor"),
+    _v("k_btcvae_fwd<0>", "dvae_btcvae_fwd", "D <= 16, D != 10", "loss.hip:756", V + "test_btcvae_bwd_at_the_row_switch[513-6-True]"),
+    _v("k_btcvae_fwd<10>", "dvae_btcvae_fwd", "D == 10", "loss.hip:756", V + "test_btcvae_bwd_at_the_row_switch[513-10-True]"),
+    _v("k_recon_loss", "dvae_recon_loss, dvae_convT4s2_sigmoid_recon_fwd (two-pass shapes)", "always", "loss.hip:734", K + "test_recon_loss[bernoulli]"),
+    _v("k_reduce_sum", "dvae_reduce_sum", "always", "loss.hip:839", MC + "[reduce_sum-n7]"),
+    _v("k_swap_outer", "dvae_swap_outer", "always", "loss.hip:874", K + "test_data_parallel_glue_kernels"),
+    _v("k_btcvae_prep", "dvae_btcvae_fwd", "always", "loss.hip:753", V + "test_btcvae_bwd_at_the_row_switch[512-10-True]"),
+    _v("k_disc_losses", "dvae_disc_losses", "always", "loss.hip:786", K + "test_permute_dims_and_disc_losses"),
+    _v("k_sigmoid_bwd", "dvae_sigmoid_bwd", "always", "loss.hip:826", K + "test_recon_loss[bernoulli]"),
+    _v("k_permute_dims", "dvae_permute_dims", "always", "loss.hip:779", K + "test_permute_dims_and_disc_losses"),
+    _v("k_btcvae_bwd_wg<0>", "dvae_btcvae_bwd", "Bl <= 512, D <= 16, D != 10", "loss.hip:769", V + "test_btcvae_bwd_at_the_row_switch[512-6-True]"),
+    _v("k_btcvae_bwd_wg<10>", "dvae_btcvae_bwd", "Bl <= 512, D == 10", "loss.hip:769", V + "test_btcvae_bwd_at_the_row_switch[512-10-True]"),
+    _v("k_kl_normal_bwd", "dvae_kl_normal_bwd", "always", "loss.hip:833", MC + "[kl_normal_bwd-B7-D1]"),
+    _v("k_loss_epilogue", "dvae_loss_epilogue", "always", "loss.hip:812", K + "test_loss_epilogue_equals_pack_then_finalize[0-8]"),
+    _v("k_loss_finalize", "dvae_loss_finalize", "always", "loss.hip:819", K + "test_loss_epilogue_equals_pack_then_finalize[0-8]"),
+    _v("k_reparam_kl_bwd", "dvae_reparam_kl_bwd", "always", "loss.hip:726", K + "test_reparam_kl[8]"),
+    _v("k_reparam_kl_fwd", "dvae_reparam_kl_fwd", "D <= 16", "loss.hip:712", V + "test_reparam_kl_at_the_partial_block_switches[257]"),
+    _v("k_btcvae_bwd_cols<0>", "dvae_btcvae_bwd", "Bl > 512, D <= 16, D != 10", "loss.hip:773", V + "test_btcvae_bwd_at_the_row_switch[513-6-True]"),
+    _v("k_btcvae_bwd_cols<10>", "dvae_btcvae_bwd", "Bl > 512, D == 10", "loss.hip:773", V + "test_btcvae_bwd_at_the_row_switch[513-10-True]"),
+    _v("k_btcvae_bwd_rows<0>", "dvae_btcvae_bwd", "Bl > 512, D <= 16, D != 10", "loss.hip:772", V + "test_btcvae_bwd_at_the_row_switch[513-6-True]"),
+    _v("k_btcvae_bwd_rows<10>", "dvae_btcvae_bwd", "Bl > 512, D == 10", "loss.hip:772", V + "test_btcvae_bwd_at_the_row_switch[513-10-True]"),
+    _v("k_reparam_kl_finish", "dvae_reparam_kl_fwd, dvae_kl_finish", "kl_dim and coef given", "loss.hip:715", V + "test_reparam_kl_at_the_partial_block_switches[257]"),
     # ---- metrics.hip
-    _v("k_entropy_lse", "dvae_latent_entropy", "always", "metrics.hip:119", "tests/test_gpu_metrics.py::test_entropy_kernel_vs_oracle[17-3-5]"),
-    _v("k_entropy_prep", "dvae_latent_entropy", "always", "metrics.hip:117", "tests/test_gpu_metrics.py::test_entropy_kernel_vs_oracle[17-3-5]"),
-    _v("k_entropy_finish", "dvae_latent_entropy", "always", "metrics.hip:121", "tests/test_gpu_metrics.py::test_entropy_kernel_vs_oracle[17-3-5]"),
+    _v("k_entropy_lse", "dvae_latent_entropy", "always", "metrics.hip:114", "tests/test_gpu_metrics.py::test_entropy_kernel_vs_oracle[17-3-5]"),
+    _v("k_entropy_prep", "dvae_latent_entropy", "always", "metrics.hip:112", "tests/test_gpu_metrics.py::test_entropy_kernel_vs_oracle[17-3-5]"),
+    _v("k_entropy_finish", "dvae_latent_entropy", "always", "metrics.hip:116", "tests/test_gpu_metrics.py::test_entropy_kernel_vs_oracle[17-3-5]"),
     # ---- stage.hip, viz.hip
     _v("k_stage_weights", "dvae_stage_weights", "at least one image or the coefficients", "stage.hip:137", FC + "test_stage_weights_layouts_and_coefficients"),
     _v("k_image_grid_u8", "dvae_image_grid_u8", "always", "viz.hip:111", "tests/test_gpu_visualize.py::test_grid_kernel_matches_make_grid[3-32]"),
     # ---- fc_chain.hip (<DEPTH = 8, KS = 2, RG, CONV>: RG = 1 up to 1024 rows, 2 above; CONV = the conv ends in the launch)
-    _v("k_fc_chain_bwd<8, 2, 1, false>", "dvae_fc_chain_bwd", "n <= 1024, no conv ends", "fc_chain.hip:788", V + "test_fc_chain_at_the_row_group_switch[1024-10-False]"),
-    _v("k_fc_chain_bwd<8, 2, 1, true>", "dvae_fc_chain_bwd", "n <= 1024, convT_gout given", "fc_chain.hip:783", V + "test_fc_chain_at_the_row_group_switch[1024-10-True]"),
-    _v("k_fc_chain_bwd<8, 2, 2, false>", "dvae_fc_chain_bwd", "n > 1024, no conv ends", "fc_chain.hip:788", V + "test_fc_chain_at_the_row_group_switch[1025-10-False]"),
-    _v("k_fc_chain_bwd<8, 2, 2, true>", "dvae_fc_chain_bwd", "n > 1024, convT_gout given", "fc_chain.hip:783", V + "test_fc_chain_at_the_row_group_switch[1025-10-True]"),
-    _v("k_fc_chain_fwd<8, 2, 1, false>", "dvae_fc_chain_fwd", "n_enc <= 1024, no conv ends", "fc_chain.hip:768", V + "test_fc_chain_at_the_row_group_switch[1024-10-False]"),
-    _v("k_fc_chain_fwd<8, 2, 1, true>", "dvae_fc_chain_fwd", "n_enc <= 1024, conv_in given", "fc_chain.hip:763", V + "test_fc_chain_at_the_row_group_switch[1024-10-True]"),
-    _v("k_fc_chain_fwd<8, 2, 2, false>", "dvae_fc_chain_fwd", "n_enc > 1024, no conv ends", "fc_chain.hip:768", V + "test_fc_chain_at_the_row_group_switch[1025-10-False]"),
-    _v("k_fc_chain_fwd<8, 2, 2, true>", "dvae_fc_chain_fwd", "n_enc > 1024, conv_in given", "fc_chain.hip:763", V + "test_fc_chain_at_the_row_group_switch[1025-10-True]"),
+    _v("k_fc_chain_bwd<8, 2, 1, false>", "dvae_fc_chain_bwd", "n <= 1024, no conv ends", "fc_chain.hip:786", V + "test_fc_chain_at_the_row_group_switch[1024-10-False]"),
+    _v("k_fc_chain_bwd<8, 2, 1, true>", "dvae_fc_chain_bwd", "n <= 1024, convT_gout given", "fc_chain.hip:781", V + "test_fc_chain_at_the_row_group_switch[1024-10-True]"),
+    _v("k_fc_chain_bwd<8, 2, 2, false>", "dvae_fc_chain_bwd", "n > 1024, no conv ends", "fc_chain.hip:786", V + "test_fc_chain_at_the_row_group_switch[1025-10-False]"),
+    _v("k_fc_chain_bwd<8, 2, 2, true>", "dvae_fc_chain_bwd", "n > 1024, convT_gout given", "fc_chain.hip:781", V + "test_fc_chain_at_the_row_group_switch[1025-10-True]"),
+    _v("k_fc_chain_fwd<8, 2, 1, false>", "dvae_fc_chain_fwd", "n_enc <= 1024, no conv ends", "fc_chain.hip:766", V + "test_fc_chain_at_the_row_group_switch[1024-10-False]"),
+    _v("k_fc_chain_fwd<8, 2, 1, true>", "dvae_fc_chain_fwd", "n_enc <= 1024, conv_in given", "fc_chain.hip:761", V + "test_fc_chain_at_the_row_group_switch[1024-10-True]"),
+    _v("k_fc_chain_fwd<8, 2, 2, false>", "dvae_fc_chain_fwd", "n_enc > 1024, no conv ends", "fc_chain.hip:766", V + "test_fc_chain_at_the_row_group_switch[1025-10-False]"),
+    _v("k_fc_chain_fwd<8, 2, 2, true>", "dvae_fc_chain_fwd", "n_enc > 1024, conv_in given", "fc_chain.hip:761", V + "test_fc_chain_at_the_row_group_switch[1025-10-True]"),
 ]
 
 
@@ -253,14 +253,14 @@ _DMAMIN = V + "test_linear_at_the_dma_kernel_minima"
 _ELT = V + "test_elementwise_kernels_at_their_grid_caps"
 
 SWITCHES = [
-    _s("launch_btcvae_bwd", "Bl", "BTC_WG_MAX_ROWS = 512", "loss.hip:790", "Bl = 512, D = 10", _BTC + "[512-10-True]", "Bl = 513, D = 10", _BTC + "[513-10-True]"),
-    _s("launch_btcvae_bwd", "Bl (run-time D)", "BTC_WG_MAX_ROWS = 512", "loss.hip:790", "Bl = 512, D = 6", _BTC + "[512-6-True]", "Bl = 513, D = 6", _BTC + "[513-6-True]"),
-    _s("launch_btcvae_bwd", "Bl of a row shard (Bl < Bg)", "BTC_WG_MAX_ROWS = 512", "loss.hip:790", "Bg = 1100, rows [0, 500)",
+    _s("launch_btcvae_bwd", "Bl", "BTC_WG_MAX_ROWS = 512", "loss.hip:768", "Bl = 512, D = 10", _BTC + "[512-10-True]", "Bl = 513, D = 10", _BTC + "[513-10-True]"),
+    _s("launch_btcvae_bwd", "Bl (run-time D)", "BTC_WG_MAX_ROWS = 512", "loss.hip:768", "Bl = 512, D = 6", _BTC + "[512-6-True]", "Bl = 513, D = 6", _BTC + "[513-6-True]"),
+    _s("launch_btcvae_bwd", "Bl of a row shard (Bl < Bg)", "BTC_WG_MAX_ROWS = 512", "loss.hip:768", "Bg = 1100, rows [0, 500)",
        V + "test_btcvae_bwd_sharded_with_more_than_512_local_rows[0-500]", "Bg = 1100, rows [500, 1100)",
        V + "test_btcvae_bwd_sharded_with_more_than_512_local_rows[500-600]"),
-    _s("reparam_kl_blocks", "ceil(B / 256)", "1 | 2 blocks", "loss.hip:833", "B = 256", V + "test_reparam_kl_at_the_partial_block_switches[256]",
+    _s("reparam_kl_blocks", "ceil(B / 256)", "1 | 2 blocks", "loss.hip:799", "B = 256", V + "test_reparam_kl_at_the_partial_block_switches[256]",
        "B = 257", V + "test_reparam_kl_at_the_partial_block_switches[257]"),
-    _s("reparam_kl_blocks", "ceil(B / 256)", "RK_BLOCKS = 64", "loss.hip:834", "B = 16384", V + "test_reparam_kl_at_the_partial_block_switches[16384]",
+    _s("reparam_kl_blocks", "ceil(B / 256)", "RK_BLOCKS = 64", "loss.hip:800", "B = 16384", V + "test_reparam_kl_at_the_partial_block_switches[16384]",
        "B = 16385", V + "test_reparam_kl_at_the_partial_block_switches[16385]"),
     _s("launch_down_thin_ws", "N", "192", "conv_thin_ws.hip:323", "N = 191, C = 1", _THIN + "[191-1]", "N = 192, C = 1", _THIN + "[192-1]"),
     _s("launch_down_thin_ws", "N (3 channels)", "192", "conv_thin_ws.hip:323", "N = 191, C = 3", _THIN + "[191-3]", "N = 192, C = 3", _THIN + "[192-3]"),
@@ -279,9 +279,9 @@ SWITCHES = [
        "N = 8", V + "test_generic_wgrad_at_the_chunk_switches[8]"),
     _s("launch_wgrad_generic", "chunks", "64", "conv_generic.hip:384", "N = 256 (64 chunks)", V + "test_generic_wgrad_at_the_chunk_switches[256]",
        "N = 260 (65 -> 64)", V + "test_generic_wgrad_at_the_chunk_switches[260]"),
-    _s("fc_chain_rows", "n", "FCC_R4_MAX_ROWS = 1024", "fc_chain.hip:748", "n = 1024", _CHAIN + "[1024-10-False]", "n = 1025", _CHAIN + "[1025-10-False]"),
-    _s("fc_chain_rows", "n (with the conv ends)", "1024", "fc_chain.hip:748", "n = 1024", _CHAIN + "[1024-10-True]", "n = 1025", _CHAIN + "[1025-10-True]"),
-    _s("fc_chain_rows", "n (run-time D)", "1024", "fc_chain.hip:748", "n = 1024, D = 6", _CHAIN + "[1024-6-True]", "n = 1025, D = 6", _CHAIN + "[1025-6-True]"),
+    _s("fc_chain_rows", "n", "FCC_R4_MAX_ROWS = 1024", "fc_chain.hip:746", "n = 1024", _CHAIN + "[1024-10-False]", "n = 1025", _CHAIN + "[1025-10-False]"),
+    _s("fc_chain_rows", "n (with the conv ends)", "1024", "fc_chain.hip:746", "n = 1024", _CHAIN + "[1024-10-True]", "n = 1025", _CHAIN + "[1025-10-True]"),
+    _s("fc_chain_rows", "n (run-time D)", "1024", "fc_chain.hip:746", "n = 1024, D = 6", _CHAIN + "[1024-6-True]", "n = 1025, D = 6", _CHAIN + "[1025-6-True]"),
     _s("try_fc32", "Kc", "32", "linear.hip:427", "K = N = 32", _KC + "[32]", "K = N = 36", _KC + "[36]"),
     _s("try_fc32", "Kc", "64", "linear.hip:428", "K = N = 64", _KC + "[64]", "K = N = 68", _KC + "[68]"),
     _s("try_fc32", "Kc", "128", "linear.hip:429", "K = N = 128", _KC + "[128]", "K = N = 132", _KC + "[132]"),
@@ -320,10 +320,10 @@ SWITCHES = [
     _s("try_narrow_dgrad", "blocks", "4096", "linear_narrow.hip:101", "M = 16384", V + "test_narrow_input_gradient_at_its_grid_cap[16384]",
        "M = 16388", V + "test_narrow_input_gradient_at_its_grid_cap[16388]"),
     # ---- loss.hip, loglik.hip
-    _s("launch_sigmoid_bwd", "workgroups", "4096", "loss.hip:859", "n = 2^20", _ELT + "[0]", "n = 2^20 + 1", _ELT + "[1]"),
-    _s("launch_u8_to_f32", "workgroups", "4096", "loss.hip:879", "n = 2^24", _ELT + "[0]", "n = 2^24 + 16", _ELT + "[1]"),
-    _s("launch_add", "workgroups", "2048", "loss.hip:894", "n = 2^19", _ELT + "[0]", "n = 2^19 + 1", _ELT + "[1]"),
-    _s("launch_axpby", "workgroups", "2048", "loss.hip:901", "n = 2^19", _ELT + "[0]", "n = 2^19 + 1", _ELT + "[1]"),
+    _s("launch_sigmoid_bwd", "workgroups", "4096", "loss.hip:825", "n = 2^20", _ELT + "[0]", "n = 2^20 + 1", _ELT + "[1]"),
+    _s("launch_u8_to_f32", "workgroups", "4096", "loss.hip:845", "n = 2^24", _ELT + "[0]", "n = 2^24 + 16", _ELT + "[1]"),
+    _s("launch_add", "workgroups", "2048", "loss.hip:860", "n = 2^19", _ELT + "[0]", "n = 2^19 + 1", _ELT + "[1]"),
+    _s("launch_axpby", "workgroups", "2048", "loss.hip:867", "n = 2^19", _ELT + "[0]", "n = 2^19 + 1", _ELT + "[1]"),
 ]
 
 # Thresholds read in the launchers that have NO entry above yet: no case sits at the flip, and which existing tests fall on

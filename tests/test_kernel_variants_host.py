@@ -144,3 +144,12 @@ def test_committed_trace_shows_every_kernel_the_table_gives_to_the_new_file():
     assert len(claimed) > 80
     assert not sorted(claimed - seen), "rows that name a test of the file, but the kernel is not in its trace"
     assert not sorted(seen - {v.kernel for v in KV.VARIANTS}), "traced kernels without a row"
+
+
+def test_latent_math_has_one_home():
+    """csrc/latent_math.h is the one definition of log 2 pi and of the stratified-sampling weight: no per-file copy grows back."""
+    csrc = os.path.join(ROOT, "disentangling-vae_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    assert [f for f, t in text.items() if "1.83787" in t] == ["latent_math.h"]
+    defs = [(f, m.group(1)) for f, t in text.items() for m in re.finditer(r"^[ \w]*\bfloat\s+(log_w_ij\w*)\s*\(", t, re.M)]
+    assert defs == [("latent_math.h", "log_w_ij")], defs

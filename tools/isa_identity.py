@@ -4,7 +4,7 @@
     python tools/isa_identity.py PARENT_TREE [--out profiles/NAME.txt] [--work DIR] [--jobs N] [--builds shipped,debug]
 
 PARENT_TREE is a checkout of the commit to compare against (e.g. `git worktree add /tmp/parent HEAD~1`).  Every file of
-build.py's SOURCES is compiled to device-only assembly in both trees with the project's flags, once plain and once with
+build.py's SOURCES, EVAL_SOURCES and SCORE_SOURCES (all three libraries) is compiled to device-only assembly in both trees with the project's flags, once plain and once with
 -DDVAE_DEBUG_SWITCHES.  Comments and assembler directives are stripped; what is left (labels + instructions) is compared per
 function, together with each kernel's .vgpr_count / .sgpr_count / .private_segment_fixed_size / .group_segment_fixed_size
 and the "; Occupancy:" comment.  Prints one line per file and build, and for every kernel that differs the resource lines
@@ -24,6 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, PKG))
 import build as dvae_build  # noqa: E402
 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--offload-device-only", "-S"]
+ALL_SOURCES = dvae_build.SOURCES + dvae_build.EVAL_SOURCES + dvae_build.SCORE_SOURCES
 META = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
@@ -79,7 +80,7 @@ def main():
     for side, tree in trees.items():
         for b, extra in builds.items():
             os.makedirs(os.path.join(work, side, b), exist_ok=True)
-            for s in dvae_build.SOURCES:
+            for s in ALL_SOURCES:
                 out = os.path.join(work, side, b, s + ".s")
                 if side == "tip" or not os.path.exists(out):       # a parent already compiled into --work is kept
                     jobs.append((tree, s, extra, out))
@@ -88,7 +89,7 @@ def main():
 
     lines, differ = [], 0
     for b in builds:
-        for s in dvae_build.SOURCES:
+        for s in ALL_SOURCES:
             pc, pr = parse(os.path.join(work, "parent", b, s + ".s"))
             tc, tr = parse(os.path.join(work, "tip", b, s + ".s"))
             bad = [f for f in sorted(set(pc) | set(tc)) if pc.get(f) != tc.get(f) or pr.get(f) != tr.get(f)]
