@@ -19,6 +19,12 @@
   majority vote as HIP launches on the table where it lies (libdvae_score_hip.so); only the [K, D] vote matrices, the variance
   vector and the beta-VAE classifier's [V, D] features cross to the host.  Definitions and defaults: disentanglement_lib's
   factor_vae.py / beta_vae.py.  Written to factor_scores.log by ``__call__(is_scores=True)``.
+* Discretised MIG (Locatello et al. 2019), modularity (Ridgeway & Mozer 2018) and the continuous-factor SAP score (Kumar et al.
+  2018), new (``compute_information_scores`` / ``information_scores_from_table``): the centred moments and the D x K joint
+  histograms of the table of posterior means against the factors as two HIP passes on the table where it lies
+  (libdvae_info_hip.so; the factor values are digits of the row number and never exist in memory); the moments and the integer
+  counts cross to the host, where the scores are combined in fp64.  Definitions: disentanglement_lib's mig.py,
+  modularity_explicitness.py and sap_score.py.  Written to information_scores.log by ``__call__(is_information=True)``.
 """
 import logging
 import math
@@ -29,7 +35,7 @@ from timeit import default_timer
 import numpy as np
 import torch
 
-from . import _evallib, _lib, _scorelib
+from . import _evallib, _infolib, _lib, _scorelib
 from ._lib import call, ptr
 from .engine import _stream
 from .likelihood import _ScorePasses, check_rec_dist, log_likelihood
@@ -42,6 +48,7 @@ METRIC_HELPERS_FILE = "metric_helpers.pth"
 LOG_LIKELIHOOD_FILE = "log_likelihood.log"
 ELBO_DECOMPOSITION_FILE = "elbo_decomposition.log"
 FACTOR_SCORES_FILE = "factor_scores.log"
+INFORMATION_SCORES_FILE = "information_scores.log"
 
 
 class Evaluator:
@@ -57,10 +64,11 @@ class Evaluator:
         self.logger.info("Testing Device: {}".format(self.device))
 
     def __call__(self, data_loader, is_metrics=False, is_losses=True, is_log_likelihood=False, n_samples=128,
-                 is_decomposition=False, n_samples_decomposition=10000, is_scores=False):
+                 is_decomposition=False, n_samples_decomposition=10000, is_scores=False, is_information=False):
         """evaluate.py:60-95.  is_log_likelihood: also write compute_log_likelihood(data_loader, n_samples) to
         log_likelihood.log; is_decomposition: also write compute_elbo_decomposition(data_loader, n_samples_decomposition) to
-        elbo_decomposition.log; is_scores: also write compute_factor_scores(data_loader) to factor_scores.log (the return value
+        elbo_decomposition.log; is_scores: also write compute_factor_scores(data_loader) to factor_scores.log; is_information: also
+        write compute_information_scores(data_loader), without its [D, K] matrices, to information_scores.log (the return value
         stays the reference's (metric, losses))."""
         start = default_timer()
         is_still_training = self.model.training
@@ -96,6 +104,14 @@ class Evaluator:
             self.logger.info('Disentanglement scores: {}'.format(scores))
             os.makedirs(self.save_dir, exist_ok=True)
             save_metadata(scores, self.save_dir, filename=FACTOR_SCORES_FILE)
+        if is_information:
+            self.logger.info('Computing the discretised MIG, modularity and SAP scores...')
+            info = self.compute_information_scores(data_loader)
+            info = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in info.items()
+                    if not (isinstance(v, np.ndarray) and v.ndim > 1)}
+            self.logger.info('Information scores: {}'.format(info))
+            os.makedirs(self.save_dir, exist_ok=True)
+            save_metadata(info, self.save_dir, filename=INFORMATION_SCORES_FILE)
         if is_still_training:
             self.model.train()
         self.logger.info('Finished evaluating after {:.1f} min.'.format((default_timer() - start) / 60))
@@ -242,6 +258,31 @@ class Evaluator:
             raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (mean.shape[0], lat_sizes))
         return factor_scores_from_table(mean, lat_sizes, n_train=n_train, n_eval=n_eval, batch_size=batch_size,
                                         n_variance=n_variance, active_threshold=active_threshold, seed=seed, draws=draws)
+
+    # ------------------------------------------------------------------ discretised MIG / modularity / SAP
+    def compute_information_scores(self, dataloader, n_samples=None, n_bins=20, seed=0):
+        """Discretised MIG, modularity and continuous-factor SAP of the model (information_scores_from_table below, on the
+        posterior means of the whole data set through the native encoder).  The data-set requirements and errors of
+        compute_factor_scores; every size is checked before any device work; train / eval mode is restored."""
+        ds = getattr(dataloader, "dataset", None)
+        if not (hasattr(ds, "lat_sizes") and hasattr(ds, "lat_names")):
+            raise ValueError("Dataset needs to have known true factors of variations to compute the metric. This does not "
+                             "seem to be the case for {}".format(type(ds).__name__))
+        lat_sizes = [int(k) for k in ds.lat_sizes]
+        n = int(np.prod(lat_sizes)) if lat_sizes else 0
+        _check_information_sizes(n, lat_sizes, n_bins, n_samples)
+        if hasattr(ds, "__len__") and len(ds) != n:
+            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (len(ds), lat_sizes))
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            mean, _logvar = self._encode_dataset(dataloader)
+        finally:
+            if was_training:
+                self.model.train()
+        if mean.shape[0] != n:
+            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (mean.shape[0], lat_sizes))
+        return information_scores_from_table(mean, lat_sizes, n_bins=n_bins, n_samples=n_samples, seed=seed)
 
     # ------------------------------------------------------------------ MIG / AAM (evaluate.py:119-317)
     def compute_metrics(self, dataloader, sample_idx=None, n_samples=10000):
@@ -543,3 +584,140 @@ def factor_scores_from_table(mean, lat_sizes, n_train=10000, n_eval=5000, batch_
     return scores, {"var": var, "active": active, "votes_train": votes_train, "votes_eval": votes_eval, "classifier": classifier,
                     "features_train": feats["train"], "features_eval": feats["eval"], "labels_train": labels["train"],
                     "labels_eval": labels["eval"], "classes": classes, "W": W, "b": b}
+
+
+# ---------------------------------------------------------------------- discretised MIG / modularity / SAP on a table of means
+def _check_information_sizes(n, lat_sizes, n_bins, n_samples):
+    if len(lat_sizes) < 1 or min(lat_sizes) < 1:
+        raise ValueError("lat_sizes must hold positive sizes, got %s" % (lat_sizes,))
+    if len(lat_sizes) > _infolib.MAX_FACTORS:
+        raise ValueError("%d factors of variation: the kernels take at most %d" % (len(lat_sizes), _infolib.MAX_FACTORS))
+    if not 1 <= int(n_bins) <= _infolib.MAX_BINS:
+        raise ValueError("n_bins must lie in [1, %d], got %r" % (_infolib.MAX_BINS, n_bins))
+    if min(lat_sizes) < 2:
+        raise ValueError("a factor of variation with one value has no entropy (the MIG divides by it): lat_sizes=%s" % (lat_sizes,))
+    if n_samples is not None and not 1 <= int(n_samples) <= n:
+        raise ValueError("n_samples must lie in [1, %d] (rows are drawn without replacement) or be None, got %r" % (n, n_samples))
+
+
+def histogram_edges(lo, hi, n_bins):
+    """The n_bins lower bin edges numpy.histogram(x, n_bins) uses for an fp32 column with minimum lo and maximum hi, bit for bit:
+    numpy's own linspace between the two np.float32 scalars (a constant column: lo - 0.5 and hi + 0.5, as numpy does).  The same
+    edges formed from Python floats differ in the last bit for most columns.  Where numpy refuses (a range of fewer than n_bins
+    ulps) neighbouring edges coincide; the bin of x stays defined as the number of edges <= x, minus one."""
+    lo, hi = np.float32(lo), np.float32(hi)
+    if lo == hi:
+        lo, hi = np.float32(lo - np.float32(0.5)), np.float32(hi + np.float32(0.5))
+    return np.linspace(lo, hi, int(n_bins) + 1, dtype=np.float32)[:-1]
+
+
+def information_scores_from_statistics(counts, lat_sizes, n_bins, col_var, factor_var, cov_zv):
+    """The host half of information_scores_from_table, fp64: ``counts`` int [D, n_bins * sum(lat_sizes)] in the layout of
+    dvae_info_joint_hist, col_var [D], factor_var [K], cov_zv [D, K] of dvae_info_moments.
+
+    mutual_information[d, k] = sum over the nonzero cells of P log(P / (P_row P_col)), P = counts / S (nats; sklearn's
+    mutual_info_score); factor_entropy[k] = entropy of factor k's values among the selected rows;
+    mig_discrete = mean_k (largest - second largest MI over d) / factor_entropy[k] (one latent: the second is 0; a factor without
+    entropy raises ValueError);  modularity = mean_d [1 - (sum m - t) / (t (K - 1))], m = MI[d, :]^2, t = max m (0 where t = 0;
+    K = 1: 1 where t > 0);  sap_matrix[d, k] = cov_zv^2 / (col_var factor_var) where col_var > 1e-12, else 0;
+    sap_continuous = mean_k (largest - second largest over d)."""
+    lat_sizes = [int(k) for k in lat_sizes]
+    K, n_bins = len(lat_sizes), int(n_bins)
+    counts = np.asarray(counts).astype(np.int64)
+    D = counts.shape[0]
+    assert counts.shape == (D, n_bins * sum(lat_sizes)), counts.shape
+    mi, H = np.zeros((D, K)), np.zeros(K)
+    start = 0
+    for k, size in enumerate(lat_sizes):
+        block = counts[:, start:start + n_bins * size].reshape(D, n_bins, size).astype(np.float64)
+        start += n_bins * size
+        S = block[0].sum()
+        row, col = block.sum(axis=2, keepdims=True), block.sum(axis=1, keepdims=True)
+        # P / (P_row P_col) = c S / (row col) from the integer counts: both products are exact in fp64, so a cell of an independent
+        # table (a constant latent: row = S) contributes log(1) = 0 exactly and modularity's "t = 0" sees the number 0
+        nz = block > 0
+        term = np.zeros_like(block)
+        term[nz] = block[nz] / S * np.log((block * S)[nz] / (row * col)[nz])
+        mi[:, k] = term.sum(axis=(1, 2))
+        pv = col[0, 0] / S
+        H[k] = -(pv[pv > 0] * np.log(pv[pv > 0])).sum()
+    if not (H > 0).all():
+        raise ValueError("factor(s) %s take one value among the selected rows: no entropy to divide the MIG by"
+                         % [k for k in range(K) if not H[k] > 0])
+
+    def gap(m):                                                          # [D, K] -> largest minus second largest over d, [K]
+        ranked = np.sort(m, axis=0)[::-1]
+        return ranked[0] - (ranked[1] if D > 1 else 0.0)
+    m = mi ** 2
+    t = m.max(axis=1)
+    modularity_d = np.zeros(D)
+    if K > 1:
+        modularity_d[t > 0] = 1.0 - (m.sum(axis=1) - t)[t > 0] / (t[t > 0] * (K - 1))
+    else:
+        modularity_d[t > 0] = 1.0
+    col_var, factor_var, cov_zv = (np.asarray(a, dtype=np.float64) for a in (col_var, factor_var, cov_zv))
+    sap = np.zeros((D, K))
+    live = col_var > 1e-12
+    sap[live] = cov_zv[live] ** 2 / (col_var[live, None] * factor_var[None, :])
+    return {"mig_discrete": float(np.mean(gap(mi) / H)), "modularity": float(modularity_d.mean()),
+            "sap_continuous": float(np.mean(gap(sap))), "sap_matrix": sap, "mutual_information": mi, "factor_entropy": H}
+
+
+def information_scores_from_table(mean, lat_sizes, n_bins=20, n_samples=None, seed=0, rows=None):
+    """Discretised MIG, modularity and continuous-factor SAP of a representation given as the fp32 [N, D] table ``mean`` (on the
+    GPU) of a data set that enumerates ``lat_sizes`` in row-major order (formulas: information_scores_from_statistics).
+
+    n_samples=None: every row; else rows = randperm(N)[:n_samples] from a private generator seeded with ``seed`` (the same seed
+    gives the same bits, the global random states are untouched); ``rows`` ([S] row numbers in [0, N), repeats allowed) injects
+    the selection.  Every size and argument is checked before any device work, and a table with a NaN or an infinity raises
+    ValueError.  dvae_info_moments, ONE device-to-host copy of its outputs, the bin edges of numpy.histogram on the host
+    (histogram_edges), dvae_info_joint_hist, ONE copy of the counts, the scores in fp64 on the host.  Returns {"mig_discrete",
+    "modularity", "sap_continuous", "sap_matrix" [D, K], "mutual_information" [D, K], "factor_entropy" [K], "n_samples",
+    "n_bins"}: Python and numpy values."""
+    lat_sizes = [int(k) for k in lat_sizes]
+    K, n_bins = len(lat_sizes), int(n_bins)
+    if mean.dim() != 2:
+        raise ValueError("mean must be an [N, D] table, got shape %s" % (tuple(mean.shape),))
+    n, dim = int(mean.shape[0]), int(mean.shape[1])
+    _check_information_sizes(n, lat_sizes, n_bins, None if rows is not None else n_samples)
+    if n != int(np.prod(lat_sizes)):
+        raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (n, lat_sizes))
+    if dim < 1:
+        raise ValueError("mean must have one latent dimension or more")
+    if rows is not None:
+        rows = torch.as_tensor(rows).to(torch.int64).reshape(-1)
+        if rows.numel() < 1 or not (0 <= int(rows.min()) and int(rows.max()) < n):
+            raise ValueError("rows must hold one row number or more, each in [0, %d)" % n)     # (the kernels do not check them)
+    if not bool(torch.isfinite(mean).all()):
+        raise ValueError("the table of means holds a NaN or an infinity")
+    if not mean.is_cuda:
+        raise _lib.DvaeHipError("information_scores_from_table needs the table on the GPU (there is no CPU / PyTorch fallback "
+                                "for the information-score kernels)")
+    dev = mean.device
+    table = mean.detach().to(torch.float32).contiguous()
+    if rows is not None:
+        rows = rows.to(dev).contiguous()
+    elif n_samples is not None:
+        gen = torch.Generator(device=dev).manual_seed(int(seed))
+        rows = torch.randperm(n, generator=gen, device=dev)[:int(n_samples)].contiguous()
+    S = n if rows is None else int(rows.numel())
+    I = _infolib.lib()
+    st = _stream()
+    sizes_dev = torch.tensor(lat_sizes, dtype=torch.int32, device=dev)
+    sum_sizes = sum(lat_sizes)
+    ws = torch.empty(max(I.dvae_info_moments_ws_floats(n, dim, K, S), I.dvae_info_hist_ws_floats(n, dim, K, S, n_bins, sum_sizes), 1),
+                     dtype=torch.float32, device=dev)
+    out = torch.empty(4 * dim + dim * K + 2 * K, dtype=torch.float32, device=dev)
+    parts = torch.split(out, [dim, dim, dim, dim, dim * K, K, K])
+    _infolib.call("dvae_info_moments", ptr(table), ptr(rows), ptr(sizes_dev), n, dim, K, S, ptr(ws), *[ptr(p) for p in parts], st)
+    col_min, col_max, _col_mean, col_var, cov_zv, _factor_mean, factor_var = (p.numpy() for p in torch.split(
+        out.cpu(), [dim, dim, dim, dim, dim * K, K, K]))                               # ONE device->host copy
+    edges = np.stack([histogram_edges(col_min[d], col_max[d], n_bins) for d in range(dim)])
+    edges_dev = torch.from_numpy(edges).to(dev)
+    counts = torch.empty(dim, n_bins * sum_sizes, dtype=torch.int32, device=dev)
+    _infolib.call("dvae_info_joint_hist", ptr(table), ptr(rows), ptr(sizes_dev), ptr(edges_dev), n, dim, K, S, n_bins, sum_sizes,
+                  ptr(ws), ptr(counts), st)
+    scores = information_scores_from_statistics(counts.cpu().numpy(), lat_sizes, n_bins, col_var, factor_var,
+                                                cov_zv.reshape(dim, K))               # ONE copy of the counts
+    scores.update(n_samples=S, n_bins=n_bins)
+    return scores
