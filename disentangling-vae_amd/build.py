@@ -1,4 +1,4 @@
-"""Build libdvae_hip.so, libdvae_eval_hip.so, libdvae_score_hip.so and libdvae_info_hip.so (gfx950) in-tree: hipcc cross-compiles without a GPU.
+"""Build libdvae_hip.so, libdvae_eval_hip.so, libdvae_score_hip.so, libdvae_info_hip.so and libdvae_irs_hip.so (gfx950) in-tree: hipcc cross-compiles without a GPU.
 
     python disentangling-vae_amd/build.py [--force] [--debug]
 
@@ -10,7 +10,9 @@ library has none of them.  libdvae_eval_hip.so (include/dvae_eval_hip.h: the eva
 csrc/elbo_decomp.hip) is a second target with the same flags and the same up-to-date logic under its own stamp;
 libdvae_score_hip.so (include/dvae_score_hip.h: the FactorVAE / beta-VAE score kernels, csrc/factor_scores.hip) a third;
 libdvae_info_hip.so (include/dvae_info_hip.h: the moments / joint-histogram kernels of the MIG, modularity and SAP scores,
-csrc/factor_info.hip) a fourth.
+csrc/factor_info.hip) a fourth;
+libdvae_irs_hip.so (include/dvae_irs_hip.h: the group-mean / segmented-selection kernels of the interventional robustness score,
+csrc/factor_irs.hip) a fifth.
 """
 import glob
 import os
@@ -38,6 +40,10 @@ SCORE_HEADERS = HEADERS + [os.path.join(HERE, "..", "include", "dvae_score_hip.h
 INFO_LIB = os.path.join(HERE, "lib", "libdvae_info_hip.so")
 INFO_SOURCES = ["factor_info"]
 INFO_HEADERS = HEADERS + [os.path.join(HERE, "..", "include", "dvae_info_hip.h")]
+# the interventional-robustness-score library: a fifth
+IRS_LIB = os.path.join(HERE, "lib", "libdvae_irs_hip.so")
+IRS_SOURCES = ["factor_irs"]
+IRS_HEADERS = HEADERS + [os.path.join(HERE, "..", "include", "dvae_irs_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 
@@ -75,7 +81,7 @@ def _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose):
 
 
 def build(force=False, verbose=True, debug=None):
-    """Build the four libraries; returns the path of libdvae_hip.so."""
+    """Build the five libraries; returns the path of libdvae_hip.so."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if debug is None:
         debug = os.environ.get("DVAE_BUILD_DEBUG", "0") == "1"
@@ -87,6 +93,7 @@ def build(force=False, verbose=True, debug=None):
     _build_target(hipcc, EVAL_LIB, EVAL_SOURCES, EVAL_HEADERS, flags, os.path.join(OBJ, "flags_eval.txt"), force, verbose)
     _build_target(hipcc, SCORE_LIB, SCORE_SOURCES, SCORE_HEADERS, flags, os.path.join(OBJ, "flags_score.txt"), force, verbose)
     _build_target(hipcc, INFO_LIB, INFO_SOURCES, INFO_HEADERS, flags, os.path.join(OBJ, "flags_info.txt"), force, verbose)
+    _build_target(hipcc, IRS_LIB, IRS_SOURCES, IRS_HEADERS, flags, os.path.join(OBJ, "flags_irs.txt"), force, verbose)
     return LIB
 
 

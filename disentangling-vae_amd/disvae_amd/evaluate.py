@@ -25,6 +25,11 @@
   (libdvae_info_hip.so; the factor values are digits of the row number and never exist in memory); the moments and the integer
   counts cross to the host, where the scores are combined in fp64.  Definitions: disentanglement_lib's mig.py,
   modularity_explicitness.py and sap_score.py.  Written to information_scores.log by ``__call__(is_information=True)``.
+* Interventional robustness score (Suter et al. 2019), new (``compute_irs`` / ``irs_from_table``): per (binned) factor value the
+  mean of every latent and a quantile of the absolute deviations from it -- group means and an exact segmented radix select as HIP
+  launches on the table where it lies (libdvae_irs_hip.so); the counts and two order statistics per (group, latent) cross to
+  the host, where the quantiles are interpolated and the score is combined in fp64.  Definition: disentanglement_lib's irs.py.
+  Written to irs.log by ``__call__(is_irs=True)``.
 """
 import logging
 import math
@@ -35,7 +40,7 @@ from timeit import default_timer
 import numpy as np
 import torch
 
-from . import _evallib, _infolib, _lib, _scorelib
+from . import _evallib, _infolib, _irslib, _lib, _scorelib
 from ._lib import call, ptr
 from .engine import _stream
 from .likelihood import _ScorePasses, check_rec_dist, log_likelihood
@@ -49,6 +54,7 @@ LOG_LIKELIHOOD_FILE = "log_likelihood.log"
 ELBO_DECOMPOSITION_FILE = "elbo_decomposition.log"
 FACTOR_SCORES_FILE = "factor_scores.log"
 INFORMATION_SCORES_FILE = "information_scores.log"
+IRS_FILE = "irs.log"
 
 
 class Evaluator:
@@ -64,12 +70,13 @@ class Evaluator:
         self.logger.info("Testing Device: {}".format(self.device))
 
     def __call__(self, data_loader, is_metrics=False, is_losses=True, is_log_likelihood=False, n_samples=128,
-                 is_decomposition=False, n_samples_decomposition=10000, is_scores=False, is_information=False):
+                 is_decomposition=False, n_samples_decomposition=10000, is_scores=False, is_information=False,
+                 is_irs=False):
         """evaluate.py:60-95.  is_log_likelihood: also write compute_log_likelihood(data_loader, n_samples) to
         log_likelihood.log; is_decomposition: also write compute_elbo_decomposition(data_loader, n_samples_decomposition) to
         elbo_decomposition.log; is_scores: also write compute_factor_scores(data_loader) to factor_scores.log; is_information: also
-        write compute_information_scores(data_loader), without its [D, K] matrices, to information_scores.log (the return value
-        stays the reference's (metric, losses))."""
+        write compute_information_scores(data_loader), without its [D, K] matrices, to information_scores.log; is_irs: also write compute_irs(data_loader),
+        its arrays as lists, to irs.log (the return value stays the reference's (metric, losses))."""
         start = default_timer()
         is_still_training = self.model.training
         self.model.eval()
@@ -112,6 +119,12 @@ class Evaluator:
             self.logger.info('Information scores: {}'.format(info))
             os.makedirs(self.save_dir, exist_ok=True)
             save_metadata(info, self.save_dir, filename=INFORMATION_SCORES_FILE)
+        if is_irs:
+            self.logger.info('Computing the interventional robustness score...')
+            irs = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in self.compute_irs(data_loader).items()}
+            self.logger.info('IRS: {}'.format(irs))
+            os.makedirs(self.save_dir, exist_ok=True)
+            save_metadata(irs, self.save_dir, filename=IRS_FILE)
         if is_still_training:
             self.model.train()
         self.logger.info('Finished evaluating after {:.1f} min.'.format((default_timer() - start) / 60))
@@ -283,6 +296,31 @@ class Evaluator:
         if mean.shape[0] != n:
             raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (mean.shape[0], lat_sizes))
         return information_scores_from_table(mean, lat_sizes, n_bins=n_bins, n_samples=n_samples, seed=seed)
+
+    # ------------------------------------------------------------------ interventional robustness score
+    def compute_irs(self, dataloader, diff_quantile=0.99, factor_bins=20, n_samples=None, seed=0):
+        """Interventional robustness score of the model (irs_from_table below, on the posterior means of the whole data set
+        through the native encoder).  The data-set requirements and errors of compute_factor_scores; every size and argument is
+        checked before any device work; train / eval mode is restored."""
+        ds = getattr(dataloader, "dataset", None)
+        if not (hasattr(ds, "lat_sizes") and hasattr(ds, "lat_names")):
+            raise ValueError("Dataset needs to have known true factors of variations to compute the metric. This does not "
+                             "seem to be the case for {}".format(type(ds).__name__))
+        lat_sizes = [int(k) for k in ds.lat_sizes]
+        n = int(np.prod(lat_sizes)) if lat_sizes else 0
+        _check_irs_arguments(n, lat_sizes, diff_quantile, factor_bins, n_samples)
+        if hasattr(ds, "__len__") and len(ds) != n:
+            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (len(ds), lat_sizes))
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            mean, _logvar = self._encode_dataset(dataloader)
+        finally:
+            if was_training:
+                self.model.train()
+        if mean.shape[0] != n:
+            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (mean.shape[0], lat_sizes))
+        return irs_from_table(mean, lat_sizes, diff_quantile=diff_quantile, factor_bins=factor_bins, n_samples=n_samples, seed=seed)
 
     # ------------------------------------------------------------------ MIG / AAM (evaluate.py:119-317)
     def compute_metrics(self, dataloader, sample_idx=None, n_samples=10000):
@@ -720,4 +758,160 @@ def information_scores_from_table(mean, lat_sizes, n_bins=20, n_samples=None, se
     scores = information_scores_from_statistics(counts.cpu().numpy(), lat_sizes, n_bins, col_var, factor_var,
                                                 cov_zv.reshape(dim, K))               # ONE copy of the counts
     scores.update(n_samples=S, n_bins=n_bins)
+    return scores
+
+
+# ---------------------------------------------------------------------- interventional robustness score on a table of means
+def irs_group_map(lat_sizes, factor_bins=20):
+    """The groups of step 1 of the IRS: -> (group_of_value int32 [sum(lat_sizes)], n_groups [K]).  factor_bins=None: every value of
+    a factor is its own group; else value v of a factor with `size` values goes to bin numpy.digitize(v,
+    numpy.histogram(numpy.arange(size), factor_bins)[1][:-1]) (disentanglement_lib's histogram discretiser; the edges come from the
+    factor's full range 0 .. size - 1, not from a selection of rows), the distinct bins relabelled 0 .. G - 1 in order."""
+    parts, n_groups = [], []
+    for size in lat_sizes:
+        values = np.arange(int(size))
+        if factor_bins is not None:
+            bins = np.digitize(values, np.histogram(values, int(factor_bins))[1][:-1])
+            values = np.unique(bins, return_inverse=True)[1].reshape(-1)
+        parts.append(values.astype(np.int32))
+        n_groups.append(int(values.max()) + 1)
+    return np.concatenate(parts), n_groups
+
+
+def _check_irs_arguments(n, lat_sizes, diff_quantile, factor_bins, n_samples):
+    if len(lat_sizes) < 1 or min(lat_sizes) < 1:
+        raise ValueError("lat_sizes must hold positive sizes, got %s" % (lat_sizes,))
+    if len(lat_sizes) > _irslib.MAX_FACTORS:
+        raise ValueError("%d factors of variation: the kernels take at most %d" % (len(lat_sizes), _irslib.MAX_FACTORS))
+    if not 0.0 <= float(diff_quantile) <= 1.0:
+        raise ValueError("diff_quantile must lie in [0, 1], got %r" % (diff_quantile,))
+    if factor_bins is not None and int(factor_bins) < 1:
+        raise ValueError("factor_bins must be >= 1 or None (every value its own group), got %r" % (factor_bins,))
+    most = max(lat_sizes) if factor_bins is None else min(max(lat_sizes), int(factor_bins))
+    if most > _irslib.MAX_GROUPS:
+        raise ValueError("%d groups of one factor: the kernels take at most %d (use factor_bins)" % (most, _irslib.MAX_GROUPS))
+    if n_samples is not None and not 1 <= int(n_samples) <= n:
+        raise ValueError("n_samples must lie in [1, %d] (rows are drawn without replacement) or be None, got %r" % (n, n_samples))
+
+
+def irs_quantile_ranks(counts, diff_quantile):
+    """numpy.percentile(x, 100 q) with the default linear method on n sorted values is a_lo + (a_hi - a_lo) t with
+    h = (n - 1) (100 q / 100), lo = floor(h), hi = min(lo + 1, n - 1), t = h - lo.  -> (lo int64 [..] with -1 where n = 0, t)."""
+    n = np.asarray(counts).astype(np.int64)
+    h = (n - 1).clip(min=0) * (100.0 * float(diff_quantile) / 100.0)
+    lo = np.floor(h)
+    return np.where(n > 0, lo, -1).astype(np.int64), h - lo
+
+
+def irs_from_statistics(counts, n_groups, stat_lo, stat_hi, dev_max, diff_quantile=0.99):
+    """The host half of irs_from_table, fp64 (steps 4 to 6 of the score): counts int [total_groups], n_groups [K], and stat_lo,
+    stat_hi, dev_max [total_groups, D] of dvae_irs_group_order_stats in its group index space (slot 0 = all selected rows, whose
+    dev_max is the normaliser; the groups of factor k from 1 + sum(n_groups[:k])), stat_lo / stat_hi taken at the ranks of
+    irs_quantile_ranks.
+
+    max_diffs[g, d] = numpy.percentile's linear interpolation between the two order statistics; max_deviations[d] = dev_max[0, d];
+    latent d is active iff max_deviations[d] > 0 and only active latents are scored (none: IRS = 0.0);
+    IRS_matrix[a, k] = 1 - mean over the non-empty groups g of factor k of max_diffs[g, a] / max_deviations[a];
+    disentanglement_scores[a] = max_k IRS_matrix[a, k], parents[a] the arg-max (the lowest k on ties); IRS = their average weighted
+    by max_deviations.  Returns {"IRS", "disentanglement_scores" [A], "parents" [A], "IRS_matrix" [A, K] (the A active latents in
+    order), "max_deviations" [D], "active" bool [D]}."""
+    counts = np.asarray(counts).astype(np.int64).reshape(-1)
+    n_groups = [int(g) for g in n_groups]
+    lo, hi, mx = (np.asarray(a, dtype=np.float64) for a in (stat_lo, stat_hi, dev_max))
+    total = 1 + sum(n_groups)
+    assert counts.shape == (total,) and lo.shape == hi.shape == mx.shape and lo.shape[0] == total and lo.ndim == 2, (counts.shape, lo.shape)
+    _rank, t = irs_quantile_ranks(counts, diff_quantile)
+    t = t[:, None]
+    diff = hi - lo
+    max_diffs = np.where(t >= 0.5, hi - diff * (1.0 - t), lo + diff * t)                     # numpy's _lerp
+    max_deviations = mx[0]
+    active = max_deviations > 0
+    K, A = len(n_groups), int(active.sum())
+    matrix = np.zeros((A, K))
+    start = 1
+    for k, G in enumerate(n_groups):
+        present = counts[start:start + G] > 0
+        if A and present.any():
+            matrix[:, k] = 1.0 - max_diffs[start:start + G][present][:, active].mean(axis=0) / max_deviations[active]
+        start += G
+    if A:
+        scores, parents = matrix.max(axis=1), matrix.argmax(axis=1)
+        irs = float(np.average(scores, weights=max_deviations[active]))
+    else:
+        scores, parents, irs = np.zeros(0), np.zeros(0, dtype=np.int64), 0.0
+    return {"IRS": irs, "disentanglement_scores": scores, "parents": parents, "IRS_matrix": matrix,
+            "max_deviations": max_deviations, "active": active}
+
+
+def irs_from_table(mean, lat_sizes, diff_quantile=0.99, factor_bins=20, n_samples=None, seed=0, rows=None):
+    """Interventional robustness score (Suter et al. 2019; disentanglement_lib's irs.py) of a representation given as the fp32
+    [N, D] table ``mean`` (on the GPU) of a data set that enumerates ``lat_sizes`` in row-major order.
+
+    For every group of selected rows that share a (binned, irs_group_map) factor value: the centre c = the mean of every latent
+    (fp64 sums, rounded to fp32 once), the deviations |x - c| in fp32, and their diff_quantile-quantile as numpy.percentile
+    interpolates it; the same over all selected rows gives the largest deviation per latent, the normaliser.  The rest is
+    irs_from_statistics.  The groups' edges come from the full range of every factor: they are those of the selected rows'
+    own values whenever the selection holds every factor's smallest and largest value; a group without a selected row does not
+    exist for the score.
+
+    n_samples=None: every row; else rows = randperm(N)[:n_samples] from a private generator seeded with ``seed`` (the same seed
+    gives the same bits, the global random states are untouched); ``rows`` ([S] row numbers in [0, N), repeats allowed) injects
+    the selection.  Every size and argument is checked before any device work, and a table with a NaN or an infinity raises
+    ValueError.  dvae_irs_group_means, ONE device-to-host copy of the counts, the ranks on the host, dvae_irs_group_order_stats
+    with the device-resident means as centres, ONE copy of the statistics, the score in fp64 on the host.  Returns the dict of
+    irs_from_statistics plus {"n_groups", "n_samples", "diff_quantile", "factor_bins"}: Python and numpy values."""
+    lat_sizes = [int(k) for k in lat_sizes]
+    K = len(lat_sizes)
+    if mean.dim() != 2:
+        raise ValueError("mean must be an [N, D] table, got shape %s" % (tuple(mean.shape),))
+    n, dim = int(mean.shape[0]), int(mean.shape[1])
+    _check_irs_arguments(n, lat_sizes, diff_quantile, factor_bins, None if rows is not None else n_samples)
+    if n != int(np.prod(lat_sizes)):
+        raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (n, lat_sizes))
+    if dim < 1:
+        raise ValueError("mean must have one latent dimension or more")
+    group_of_value, n_groups = irs_group_map(lat_sizes, factor_bins)
+    total = 1 + sum(n_groups)
+    if total * dim > _irslib.MAX_PAIRS:
+        raise ValueError("%d groups x %d latents: the kernels take at most %d pairs" % (total, dim, _irslib.MAX_PAIRS))
+    if rows is not None:
+        rows = torch.as_tensor(rows).to(torch.int64).reshape(-1)
+        if rows.numel() < 1 or not (0 <= int(rows.min()) and int(rows.max()) < n):
+            raise ValueError("rows must hold one row number or more, each in [0, %d)" % n)     # (the kernels do not check them)
+    if not bool(torch.isfinite(mean).all()):
+        raise ValueError("the table of means holds a NaN or an infinity")
+    if not mean.is_cuda:
+        raise _lib.DvaeHipError("irs_from_table needs the table on the GPU (there is no CPU / PyTorch fallback for the "
+                                "interventional-robustness kernels)")
+    dev = mean.device
+    table = mean.detach().to(torch.float32).contiguous()
+    if rows is not None:
+        rows = rows.to(dev).contiguous()
+    elif n_samples is not None:
+        gen = torch.Generator(device=dev).manual_seed(int(seed))
+        rows = torch.randperm(n, generator=gen, device=dev)[:int(n_samples)].contiguous()
+    S = n if rows is None else int(rows.numel())
+    R = _irslib.lib()
+    st = _stream()
+    sizes_dev = torch.tensor(lat_sizes, dtype=torch.int32, device=dev)
+    map_dev = torch.from_numpy(group_of_value).to(dev)
+    groups_dev = torch.tensor(n_groups, dtype=torch.int32, device=dev)
+    layout = (n, dim, K, S, sum(lat_sizes), total, max(n_groups))
+    ws = torch.empty(max(R.dvae_irs_group_means_ws_floats(n, dim, K, S, total),
+                         R.dvae_irs_group_order_stats_ws_floats(n, dim, K, S, total), 1), dtype=torch.float32, device=dev)
+    counts_dev = torch.empty(total, dtype=torch.int32, device=dev)
+    means_dev = torch.empty(total, dim, dtype=torch.float32, device=dev)
+    _irslib.call("dvae_irs_group_means", ptr(table), ptr(rows), ptr(sizes_dev), ptr(map_dev), ptr(groups_dev), *layout, ptr(ws),
+                 ptr(counts_dev), ptr(means_dev), st)
+    counts = counts_dev.cpu().numpy()                                                  # ONE device->host copy
+    rank, _t = irs_quantile_ranks(counts, diff_quantile)
+    rank[0] = S - 1                                                                    # all rows: only the largest deviation is used
+    rank_dev = torch.from_numpy(rank.astype(np.int32)).to(dev)
+    stats = torch.empty(3, total, dim, dtype=torch.float32, device=dev)
+    _irslib.call("dvae_irs_group_order_stats", ptr(table), ptr(rows), ptr(sizes_dev), ptr(map_dev), ptr(groups_dev), ptr(means_dev),
+                 ptr(rank_dev), *layout, ptr(ws), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), st)
+    stat_lo, stat_hi, dev_max = stats.cpu().numpy()                                    # ONE copy of the statistics
+    scores = irs_from_statistics(counts, n_groups, stat_lo, stat_hi, dev_max, diff_quantile)
+    scores.update(n_groups=n_groups, n_samples=S, diff_quantile=float(diff_quantile),
+                  factor_bins=None if factor_bins is None else int(factor_bins))
     return scores
