@@ -84,7 +84,8 @@ int launch_adam(const dvae_adam_tensor* ts, int nt, float step_new, double lr, d
     for (int i = 0; i < T.nt; ++i) {
       T.t[i] = ts[t0 + i];
       T.blk0[i] = blk;
-      blk += (int)((ts[t0 + i].n + ADAM_CHUNK - 1) / ADAM_CHUNK);
+      // (an empty tensor keeps one workgroup: it updates nothing and writes the tensor's step count, as torch's Adam does)
+      blk += ts[t0 + i].n > 0 ? (int)((ts[t0 + i].n + ADAM_CHUNK - 1) / ADAM_CHUNK) : 1;
     }
     T.blk0[T.nt] = blk;
     if (blk == 0) continue;

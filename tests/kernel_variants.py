@@ -10,14 +10,26 @@ VARIANTS   one row per __global__ kernel instantiation of the SHIPPED library (b
              where    the launch site, file:line under disentangling-vae_amd/csrc/;
              test     node id of one GPU test that makes such a call, or None;
              reason   test is None: why no call of the shipped library can reach the kernel.
-SWITCHES   numeric thresholds in the launchers: (launcher, variable, threshold, where, last shape of one side, its test id,
-           first shape of the other side, its test id -- a different id).
-OPEN_SWITCHES  thresholds read in the launchers that have no such pair yet.
+SWITCHES   every numeric threshold read in the launchers: (launcher, variable, threshold, where, last shape of one side, its
+           test id, first shape of the other side, its test id -- a different id), or, where no call through the C-ABI can
+           reach the flip, no shapes and no ids but a `reason`.
+OPEN_SWITCHES  thresholds read in the launchers without such a pair: empty, and held empty by the host test -- a newly found
+           threshold goes into SWITCHES with its pair.
+TRIP_CLASSES  per persistent (grid-capped) kernel family: grid size and trips of workgroup b as Python expressions of the image
+           count N copied from the launcher and the kernel's loop, the depth of its software pipeline (units in flight per
+           workgroup; 1 = the loop holds one unit at a time), the smallest N that reaches the kernel, and the tests that sit
+           at each required trip-count class:
+             uniform t  (every workgroup makes t trips) for each t from the kernel's minimum to depth + 1,
+             one uniform odd and one uniform even count above the depth,
+             one mixed launch (workgroups of t + 1 and of t trips side by side);
+           `unreachable` names the uniform counts that no image count gives.  The host test evaluates the expressions at the N
+           of each named id and asserts that the class claimed is the class obtained.
 """
 from collections import namedtuple
 
 Variant = namedtuple("Variant", "kernel entry when where test reason")
-Switch = namedtuple("Switch", "launcher variable threshold where below below_test above above_test")
+Switch = namedtuple("Switch", "launcher variable threshold where below below_test above above_test reason")
+TripFamily = namedtuple("TripFamily", "family where grid trips depth n_from cases unreachable")
 
 K = "tests/test_gpu_kernels.py::"
 V = "tests/test_gpu_kernel_variants.py::"
@@ -27,6 +39,7 @@ MB = "tests/test_gpu_mask_bits.py::"
 U8 = "tests/test_gpu_uint8_input.py::"
 MC = "tests/test_gpu_memory_contract.py::test_memory_contract"
 WL = "tests/test_gpu_wide_latent.py::"
+T = "tests/test_gpu_trip_counts.py::"
 
 _DEBUG_ONLY = ("the wave-specialised kernel takes every shape this one covers; the launcher falls through to it only with %s=0, "
                "an environment switch that exists in --debug builds only (common.h: env_off() is constant false)")
@@ -233,8 +246,8 @@ VARIANTS = [
 ]
 
 
-def _s(launcher, variable, threshold, where, below, below_test, above, above_test):
-    return Switch(launcher, variable, threshold, where, below, below_test, above, above_test)
+def _s(launcher, variable, threshold, where, below=None, below_test=None, above=None, above_test=None, reason=None):
+    return Switch(launcher, variable, threshold, where, below, below_test, above, above_test, reason)
 
 
 _BTC = V + "test_btcvae_bwd_at_the_row_switch"
@@ -251,6 +264,14 @@ _SPLIT = V + "test_linear_at_the_contraction_slice_switches"
 _RGRID = V + "test_linear_split_contraction_at_the_reduction_grid_cap"
 _DMAMIN = V + "test_linear_at_the_dma_kernel_minima"
 _ELT = V + "test_elementwise_kernels_at_their_grid_caps"
+_PAST = V + "test_thin_ends_past_the_wave_specialised_switch"
+_U8F = T + "test_u8_thin_kernels_vs_fp64"
+_FUSED = T + "test_fused_convT3_likelihood_at_the_grid_cap"
+_STG = T + "test_staged_convT3_at_the_grid_caps"
+_WG4 = T + "test_wgrad32_4x4_at_the_grid_cap"
+_GEN = T + "test_generic_conv_at_the_grid_cap"
+_RR = T + "test_recon_rows_at_the_slice_switches"
+_ADAMC = T + "test_adam_at_the_chunk_switch"
 
 SWITCHES = [
     _s("launch_btcvae_bwd", "Bl", "BTC_WG_MAX_ROWS = 512", "loss.hip:768", "Bl = 512, D = 10", _BTC + "[512-10-True]", "Bl = 513, D = 10", _BTC + "[513-10-True]"),
@@ -324,19 +345,112 @@ SWITCHES = [
     _s("launch_u8_to_f32", "workgroups", "4096", "loss.hip:845", "n = 2^24", _ELT + "[0]", "n = 2^24 + 16", _ELT + "[1]"),
     _s("launch_add", "workgroups", "2048", "loss.hip:860", "n = 2^19", _ELT + "[0]", "n = 2^19 + 1", _ELT + "[1]"),
     _s("launch_axpby", "workgroups", "2048", "loss.hip:867", "n = 2^19", _ELT + "[0]", "n = 2^19 + 1", _ELT + "[1]"),
+    _s("launch_recon_rows", "nslice = ceil(row_elems / 4 / 256)", "1 | 2 (k_recon_rows_finish)", "loglik.hip:147", "1024 elements, K = 1",
+       _RR + "[bernoulli-False-1024-1]", "1028 elements, K = 1", _RR + "[bernoulli-False-1028-1]"),
+    _s("launch_recon_rows", "nslice (two row chunks, uint8 target)", "2 | 3", "loglik.hip:147", "2048 elements, K = 9", _RR + "[laplace-True-2048-9]",
+       "2052 elements, K = 9", _RR + "[laplace-True-2052-9]"),
+    # ---- persistent-grid caps: the image count from which a workgroup takes a second trip (more trip counts: TRIP_CLASSES)
+    _s("launch_down_thin", "n_units = 8 N", "1536", "conv_thin.hip:679", "N = 192, C = 1 (k_down_thin<1, 1>)", _THIN + "[192-1]",
+       "N = 193, C = 1", _PAST + "[193-1]"),
+    _s("launch_down_thin", "n_units = 8 N (3 channels)", "1536", "conv_thin.hip:679", "N = 192, C = 3 (k_down_thin<3, 1>)", _THIN + "[192-3]",
+       "N = 193, C = 3 (and modes 0, 2, 3 on unaligned buffers)", V + "test_thin_ends_past_the_cap_on_buffers_the_wave_specialised_kernels_decline"),
+    _s("launch_down_thin_u8", "n_units = 8 N", "1536", "conv_thin.hip:719", "N = 192", _U8F + "[192-1-0]", "N = 193", _U8F + "[193-1-1]"),
+    _s("launch_up_thin_recon", "n_units = 8 N", "1536", "conv_thin.hip:708", "N = 192, C = 1", _FUSED + "[192-1-0-False]", "N = 193, C = 1", _FUSED + "[193-1-1-False]"),
+    _s("launch_up_thin_recon", "n_units = 8 N (3 channels)", "1536", "conv_thin.hip:708", "N = 192, C = 3", _FUSED + "[192-3-2-False]", "N = 193, C = 3", _FUSED + "[193-3-0-False]"),
+    _s("launch_up_thin_recon_u8", "n_units = 8 N", "1536", "conv_thin.hip:733", "N = 192, C = 1", _FUSED + "[192-1-1-True]", "N = 193, C = 1", _FUSED + "[193-1-2-True]"),
+    _s("launch_up_thin_recon_u8", "n_units = 8 N (3 channels)", "1536", "conv_thin.hip:733", "N = 192, C = 3", _FUSED + "[192-3-0-True]", "N = 193, C = 3", _FUSED + "[193-3-1-True]"),
+    _s("k_up_thin / k_up_thin_pk", "XCD-aware unit map: grid % 64", "0", "conv_thin.hip:214", "N = 8 (64 workgroups: on)", _FUSED + "[8-3-2-False]",
+       "N = 9 (72: off)", _FUSED + "[9-3-2-False]"),
+    _s("launch_up_thin_staged", "n_units = 8 N (k_up_thin_pk<1, *>)", "1536", "conv_thin.hip:545", "N = 192", _STG + "[192-1]", "N = 193", _STG + "[193-1]"),
+    _s("launch_up_thin_staged", "n_units = 8 N (k_up_thin_pk<3, *>: buffers k_up_thin_mm declines)", "1536", "conv_thin.hip:545", "N = 3 (24 units)",
+       V + "test_convT3_staged_falls_back_to_the_packed_fma_kernel", "N = 193", V + "test_convT3_staged_fallback_past_its_grid_cap"),
+    _s("launch_up_thin_mm", "n_units = 3 N", "512", "conv_up_thin_mm.hip:278", "N = 170 (510 units)", _STG + "[170-3]", "N = 171 (513)", _STG + "[171-3]"),
+    _s("launch_wgrad_thin_u8", "n_units = 8 N", "WT_MAX_BLOCKS = 512", "conv_thin.hip:757", "N = 64, C = 3", _U8F + "[64-3-0]", "N = 65, C = 1", _U8F + "[65-1-1]"),
+    _s("launch_wgrad_thin_u8", "n_units = 8 N (uint8 == fp32 kernel, bit for bit)", "512", "conv_thin.hip:757", "N = 64, C = 3",
+       U8 + "test_u8_kernels_equal_fp32_kernels_bitwise[64-3]", "N = 65, C = 3", U8 + "test_u8_kernels_equal_fp32_kernels_bitwise[65-3]"),
+    _s("launch_wgrad_thin", "n_units = 8 N (fp32; aligned buffers leave for conv_thin_ws.hip at 192 images)", "512", "conv_thin.hip:772",
+       "N = 64, C = 3", U8 + "test_u8_kernels_equal_fp32_kernels_bitwise[64-3]", "N = 65, C = 1", U8 + "test_u8_kernels_equal_fp32_kernels_bitwise[65-1]"),
+    _s("launch_wgrad_t<4> (k_wgrad32<4>)", "units = ceil(N / 4)", "WG_MAX_BLOCKS = 256", "conv_mfma.hip:425", "N = 1024", _WG4 + "[1024-False-False]",
+       "N = 1025", _WG4 + "[1025-False-False]"),
+    _s("launch_wgrad_t<4> (k_wgrad32<4>)", "units (convT, NCHW small side)", "256", "conv_mfma.hip:425", "N = 1024", _WG4 + "[1024-True-True]",
+       "N = 1025", _WG4 + "[1025-True-True]"),
+    _s("grid_for (k_down_thin_px<1>)", "ceil(N * Hs * Ws * 8 / 256)", "8192", "conv_generic.hip:344", "N = 16384 (8x8 images)", _GEN + "[down_thin_px1-0]",
+       "N = 16385 (8193 wanted)", _GEN + "[down_thin_px1-1]"),
+    _s("grid_for (k_down_thin_px<3>)", "ceil(N * Hs * Ws * 8 / 256)", "8192", "conv_generic.hip:344", "N = 16384 (8x8 images)", _GEN + "[down_thin_px3-0]",
+       "N = 16385", _GEN + "[down_thin_px3-1]"),
+    _s("grid_for (k_down_generic)", "ceil(N * Cs * Hs * Ws / 256)", "8192", "conv_generic.hip:351", "N = 8192 (2 -> 16 channels, 8x8 -> 4x4)",
+       _GEN + "[down_generic-0]", "N = 8193", _GEN + "[down_generic-1]"),
+    _s("grid_for (k_up_thin_px<1>)", "ceil(N * Cb * 4 Hs Ws / 256)", "8192", "conv_generic.hip:363", "N = 8192 (8x8 -> 16x16)", _GEN + "[up_thin_px1-0]",
+       "N = 8193", _GEN + "[up_thin_px1-1]"),
+    _s("grid_for (k_up_thin_px<3>)", "ceil(N * Cb * 4 Hs Ws / 256)", "8192", "conv_generic.hip:363", "N = 10922 (4x4 -> 8x8: 8191.5)", _GEN + "[up_thin_px3-0]",
+       "N = 10923 (8192.25)", _GEN + "[up_thin_px3-1]"),
+    _s("grid_for (k_up_generic)", "ceil(N * Cb * 4 Hs Ws / 256)", "8192", "conv_generic.hip:370", "N = 8192 (2 -> 4 channels, 4x4 -> 8x8)",
+       _GEN + "[up_generic-0]", "N = 8193", _GEN + "[up_generic-1]"),
+    _s("launch_wgrad_generic", "chunks * Cs * Cb * 17 floats against the workspace", "dvae_conv_wgrad_ws_floats() = 4 276 224", "conv_generic.hip:385",
+       "N = 61 (64 -> 64 channels, 32x32 small side)", T + "test_generic_wgrad_at_the_workspace_switch[61]", "N = 62",
+       T + "test_generic_wgrad_at_the_workspace_switch[62]"),
+    _s("k_adam", "tensor elements", "ADAM_CHUNK = 4096 (and 8192: 2 | 3 workgroups)", "adam.hip:88", "4096 and 8192 elements", _ADAMC + "[0]",
+       "4097 and 8193 elements", _ADAMC + "[1]"),
+    # ---- read in a launcher, out of reach of the C-ABI
+    _s("pick_split / launch_linear_wgrad", "S * (output + 4096) floats against the workspace", "dvae_conv_wgrad_ws_floats()", "linear.hip:616",
+       reason="the loop in front of the clamp doubles S only while tiles * S < 256 and S < 16, so tiles * S < 512 and S <= 16 behind it, and "
+              "the output has at most 4096 tiles elements (tiles = ceil(rows / 64) * ceil(columns / 64), linear.hip:640 / 679): S * (output + "
+              "4096) <= 4096 (tiles * S + S) < 4096 * 528 = PICK_SPLIT_WS_BOUND floats; launch_linear_wgrad's own form (linear.hip:718) needs "
+              "S * (N * K + N) <= 4096 tiles * S + 64 tiles * S < 4160 * 512, which is less.  capi.hip passes dvae_conv_wgrad_ws_floats() = "
+              "4 276 224 floats on every call, so neither clamp ever halves S; test_kernel_variants_host.py::"
+              "test_the_workspace_keeps_the_split_contraction_clamps_out_of_reach fails if the workspace shrinks below the bound"),
 ]
 
-# Thresholds read in the launchers that have NO entry above yet: no case sits at the flip, and which existing tests fall on
-# which side has not been established.  (launcher, variable, threshold, where)
-OPEN_SWITCHES = [
-    ("pick_split / launch_linear_wgrad", "S * (output + 4096) floats against the workspace", "dvae_conv_wgrad_ws_floats()", "linear.hip:616"),
-    ("launch_down_thin / launch_down_thin_u8", "n_units = 8 N", "1536 (N = 192 | 193)", "conv_thin.hip:679"),
-    ("launch_up_thin_recon / launch_up_thin_recon_u8", "n_units = 8 N", "1536 (N = 192 | 193)", "conv_thin.hip:708"),
-    ("launch_up_thin_staged", "n_units = 8 N (k_up_thin_pk)", "1536 (N = 192 | 193)", "conv_thin.hip:545"),
-    ("launch_wgrad_thin_u8 / launch_wgrad_thin", "n_units = 8 N", "WT_MAX_BLOCKS", "conv_thin.hip:757"),
-    ("launch_wgrad32 (k_wgrad32<4>)", "units", "WG_MAX_BLOCKS", "conv_mfma.hip:425"),
-    ("launch_up_thin_mm", "n_units = 3 N", "512 (N = 170 | 171)", "conv_up_thin_mm.hip:278"),
-    ("grid_for", "workgroups of the shape-generic conv kernels", "8192", "conv_generic.hip:330"),
-    ("launch_recon_rows", "nslice", "1 | 2 (k_recon_rows_finish)", "loglik.hip:147"),
-    ("k_adam", "tensor elements", "ADAM_CHUNK = 4096 (4096 | 4097 elements sit in both cases of test_adam_at_the_table_split)", "adam.hip:87"),
+# above every S * (out_elems + 4096) that pick_split's clamp (linear.hip:616) can meet: tiles * S < 512 and S <= 16 behind its first loop
+PICK_SPLIT_WS_BOUND = 4096 * 512 + 4096 * 16
+
+# Thresholds read in the launchers that have no entry above: none.  A newly found one goes into SWITCHES with its pair.
+OPEN_SWITCHES = []
+
+
+def _t(family, where, grid, trips, depth, n_from, cases, unreachable=None):
+    return TripFamily(family, where, grid, trips, depth, n_from, cases, unreachable or {})
+
+
+_STRIDE = "cdiv(units - b, grid)"                                    # for (unit = b; unit < units; unit += grid)
+_XMAP = "cdiv(8 * N - (8 * ((b & 7) + 8 * (b >> 6)) + ((b >> 3) & 7) if grid % 64 == 0 else b), grid)"     # conv_thin.hip:214-217
+_LANE = "cdiv(N - ((b & 7) + 8 * (b >> 6)), grid >> 3)"              # conv_thin_ws.hip:65-68, 113: n0 .. N step grid / 8 images
+_W4T = T + "test_wgrad32_4x4_trip_counts"
+_WWS = T + "test_wgrad32ws_trip_counts"
+
+# cases: (class, N, test id): "u<t>" = t trips in every workgroup, "m<t>" = workgroups of t + 1 and of t trips.  In the expressions
+# N is the image count, b the workgroup, grid the grid size, units the `units` expression, cdiv(a, b) = max(0, ceil(a / b)).
+TRIP_CLASSES = [
+    _t("k_down_thin_ws", "conv_thin_ws.hip:324", "512", _LANE, depth=4, n_from=192, cases=[       # ring of four tile stages
+        ("u3", 192, _THIN + "[192-3]"), ("u4", 256, _PAST + "[256-1]"), ("u5", 320, _PAST + "[320-3]"),
+        ("u16", 1024, B + "test_conv_persistent_loops[1024-3-64]"), ("m3", 193, _PAST + "[193-1]"), ("m3", 224, _PAST + "[224-3]"),
+        ("m4", 257, _PAST + "[257-3]")]),
+    _t("k_wgrad_thin_ws", "conv_thin_ws.hip:631", "256", _LANE, depth=3, n_from=192, cases=[      # ring of three
+        ("u6", 192, _THIN + "[192-1]"), ("u7", 224, _PAST + "[224-3]"), ("u8", 256, _PAST + "[256-1]"), ("u10", 320, _PAST + "[320-3]"),
+        ("m6", 193, _PAST + "[193-3]"), ("m8", 257, _PAST + "[257-1]")]),
+    _t("k_down_thin", "conv_thin.hip:679", "min(8 * N, 1536)", _STRIDE.replace("units", "8 * N"), depth=2, n_from=1, cases=[   # two tiles in registers
+        ("u1", 191, _THIN + "[191-1]"), ("u2", 384, _U8F + "[384-3-1]"), ("u3", 576, _U8F + "[576-1-0]"), ("u4", 768, _U8F + "[768-1-1]"),
+        ("m1", 193, _PAST + "[193-1]")]),
+    _t("k_up_thin fused", "conv_thin.hip:708", "min(8 * N, 1536)", _XMAP, depth=1, n_from=1, cases=[
+        ("u1", 192, _FUSED + "[192-1-0-False]"), ("u2", 384, _U8F + "[384-3-1]"), ("u3", 576, _U8F + "[576-1-0]"),
+        ("m1", 193, _FUSED + "[193-3-0-False]")]),
+    _t("k_up_thin_pk", "conv_thin.hip:545", "min(8 * N, 1536)", _XMAP, depth=1, n_from=1, cases=[
+        ("u1", 192, _STG + "[192-1]"), ("u2", 384, _STG + "[384-1]"), ("u3", 576, _STG + "[576-1]"), ("m1", 193, _STG + "[193-1]")]),
+    _t("k_up_thin_mm", "conv_up_thin_mm.hip:278", "min(3 * N, 512)", _STRIDE.replace("units", "3 * N"), depth=2, n_from=1, cases=[   # next tile in registers
+        ("u1", 170, _STG + "[170-3]"), ("u3", 512, _STG + "[512-3]"), ("u6", 1024, _STG + "[1024-3]"), ("m1", 171, _STG + "[171-3]")],
+       unreachable={2: "3 N is a multiple of the 512 workgroups only for N = 512 k, which gives 3 k trips"}),
+    _t("k_wgrad_thin", "conv_thin.hip:757", "min(8 * N, 512)", _STRIDE.replace("units", "8 * N"), depth=2, n_from=1, cases=[   # next unit in registers
+        ("u1", 64, _U8F + "[64-3-0]"), ("u2", 128, _U8F + "[128-3-2]"), ("u3", 192, _U8F + "[192-1-0]"), ("u4", 256, _U8F + "[256-3-0]"),
+        ("m1", 65, _U8F + "[65-1-1]")]),
+    _t("k_wgrad32<4>", "conv_mfma.hip:425", "min(cdiv(N, 4), 256)", _STRIDE.replace("units", "cdiv(N, 4)"), depth=2, n_from=1, cases=[
+        ("u1", 1024, _WG4 + "[1024-False-False]"), ("u2", 2048, _W4T + "[2048]"), ("u3", 3072, _W4T + "[3072]"), ("u4", 4096, _W4T + "[4096]"),
+        ("m1", 1025, _WG4 + "[1025-False-False]")]),
+    _t("k_down32dma / k_up32ws (HS 16)", "conv_down_dma.hip:222", "min(4 * N, 256)", _STRIDE.replace("units", "4 * N"), depth=3, n_from=1, cases=[
+        ("u1", 64, _GRID + "[64-16]"), ("u2", 128, _GRID + "[128-16]"), ("u3", 192, _GRID + "[192-16]"), ("u4", 256, _GRID + "[256-16]"),
+        ("u5", 320, _GRID + "[320-16]"), ("m1", 65, _GRID + "[65-16]"), ("m2", 129, _GRID + "[129-16]"), ("m3", 193, _GRID + "[193-16]")]),
+    _t("k_wgrad32ws (HS 16)", "conv_wgrad_ws.hip:307", "min(4 * N, 192 if 128 < N <= 320 else 256)", _STRIDE.replace("units", "4 * N"), depth=4,
+       n_from=1, cases=[                                             # two LDS buffers and two register sets
+        ("u1", 64, _WWS + "[64]"), ("u2", 128, _CAP + "[128-16]"), ("u3", 144, _WWS + "[144]"), ("u4", 192, _WWS + "[192]"),
+        ("u5", 240, _WWS + "[240]"), ("u6", 288, _WWS + "[288]"), ("m2", 129, _CAP + "[129-16]")]),
 ]
+

@@ -124,6 +124,95 @@ def test_reparam_kl_at_the_partial_block_switches(B):
 
 
 # ---- thin ends (C = 1 / 3 <-> 32 channels at 64x64): conv_thin_ws.hip takes over at N >= 192 -------------------------------
+@functools.lru_cache(maxsize=1)
+def _thin_problem(N, C):
+    """seeded inputs of the thin-end bundle and its fp64 references (computed once per (N, C); the aligned and the misaligned
+    run of one shape share them)."""
+    x = torch.rand(N, C, 64, 64, generator=torch.Generator().manual_seed(1))
+    w = _rand(32, C, 4, 4, seed=2, scale=0.2)
+    b = _rand(32, seed=3, scale=0.1)
+    dy = _rand(N, 32, 32, 32, seed=4)                         # NCHW values
+    wr, br = w.double().requires_grad_(True), b.double().requires_grad_(True)
+    pre = F.conv2d(x.double(), wr, br, stride=2, padding=1)
+    ref = torch.relu(pre).detach()
+    pre.backward(dy.double())
+    a = torch.relu(_rand(N, 32, 32, 32, seed=5))              # NCHW values
+    wt = _rand(32, C, 4, 4, seed=6, scale=0.2)
+    g = _rand(N, C, 64, 64, seed=7)
+    ar, wtr, btr = a.double().requires_grad_(True), wt.double().requires_grad_(True), torch.zeros(C, dtype=torch.float64, requires_grad=True)
+    F.conv_transpose2d(ar, wtr, btr, stride=2, padding=1).backward(g.double())
+    return dict(x=x, w=w, b=b, dy=dy, ref=ref, dw=wr.grad, db=br.grad, a=a, wt=wt, g=g, dx=(ar.grad * (a > 0)).detach(),
+                dwt=wtr.grad, dbt=btr.grad)
+
+
+def _off4(t=None, numel=None, dtype=torch.float32, fill=7.0):
+    """(arena, view): the view starts 4 bytes into a 16-byte aligned arena (filled with `fill`) and holds `t` if given."""
+    n = t.numel() if t is not None else numel
+    arena = torch.full((n + 4,), fill, dtype=dtype, device=DEV)
+    v = arena[1:1 + n]
+    if t is not None:
+        v.copy_(t.reshape(-1).to(DEV))
+    assert ptr(arena) % 16 == 0 and ptr(v) % 16 == 4
+    return keep(arena), v
+
+
+def _thin_ends(N, C, misaligned=False):
+    """conv1 forward (plain and with the bit plane), convT3's input gradient (fp32 mask, bit-plane mask) and both weight
+    gradients with a thin side, each against fp64 at KTOL, outputs pre-filled with 7.0.  misaligned: the images (x, g), the
+    outputs and the bit planes are views 4 bytes into their buffers, which launch_down_thin_ws / launch_wgrad_thin_ws decline
+    (conv_thin_ws.hip: 16-byte LDS-DMA and stores), so k_down_thin<C, MODE> / k_wgrad_thin<C> run at any N.  Returns the
+    forward outputs, the bit plane and the weight gradients."""
+    P = _thin_problem(N, C)
+    tag = "thin N=%d C=%d%s " % (N, C, " (4 bytes in)" if misaligned else "")
+    ws = _ws()
+    guards = []
+
+    def inp(t):
+        if not misaligned:
+            return dev(t)
+        return _off4(t)[1]
+
+    def outp(*shape, dtype=torch.float32, fill=7.0):
+        if not misaligned:
+            return torch.full(shape, fill, dtype=dtype, device=DEV)
+        arena, v = _off4(numel=math.prod(shape), dtype=dtype, fill=fill)
+        guards.append((arena, fill))
+        return v.view(*shape)
+
+    # conv1: x[N,C,64,64] NCHW -> y[N,32,32,32] NHWC
+    xd, wd, bd = inp(P["x"]), dev(P["w"]), dev(P["b"])
+    y = outp(N, 32, 32, 32)
+    call("dvae_conv4s2_fwd", ptr(xd), _lib.NCHW, ptr(wd), ptr(bd), ptr(y), _lib.NHWC, N, C, 64, 64, 32, _lib.ACT_RELU, stream())
+    check(from_nhwc(y, N, 32, 32, 32), P["ref"], what=tag + "conv1 fwd", **KTOL)
+    yb = outp(N, 32, 32, 32)
+    bits = outp(N * 1024, dtype=torch.int32, fill=0x55555555)
+    call("dvae_conv1_fwd_bits", ptr(xd), 0, ptr(wd), ptr(bd), ptr(yb), ptr(bits), N, C, stream())
+    check(from_nhwc(yb, N, 32, 32, 32), P["ref"], what=tag + "conv1 fwd (bits)", **KTOL)
+    assert torch.equal(bits, _pack_bits(yb))
+    dw, db = full(32, C, 4, 4), full(32)
+    call("dvae_conv4s2_wgrad", ptr(xd), _lib.NCHW, ptr(nhwc(P["dy"])), _lib.NHWC, ptr(dw), ptr(db), N, C, 64, 64, 32, ptr(ws), stream())
+    check(dw, P["dw"], what=tag + "conv1 wgrad", **KTOL)
+    check(db, P["db"], what=tag + "conv1 bias grad", **KTOL)
+    # convT3: a[N,32,32,32] NHWC -> C x 64 x 64 NCHW; input gradient masked by a, weight gradient (bias from the big side)
+    ad, gd, wtd = nhwc(P["a"]), inp(P["g"]), dev(P["wt"])
+    dx = outp(N, 32, 32, 32)
+    call("dvae_convT4s2_dgrad", ptr(gd), _lib.NCHW, ptr(wtd), ptr(ad), ptr(dx), _lib.NHWC, N, 32, 32, 32, C, stream())
+    check(from_nhwc(dx, N, 32, 32, 32), P["dx"], what=tag + "convT3 dgrad", **KTOL)
+    dxb = outp(N, 32, 32, 32)
+    mbits = _pack_bits(ad)
+    if misaligned:
+        mbits = _off4(mbits, dtype=torch.int32, fill=0)[1]
+    call("dvae_convT3_dgrad_bits", ptr(gd), ptr(wtd), ptr(mbits), ptr(dxb), N, C, stream())
+    check(from_nhwc(dxb, N, 32, 32, 32), P["dx"], what=tag + "convT3 dgrad (bits)", **KTOL)
+    dwt, dbt = full(32, C, 4, 4), full(C)
+    call("dvae_convT4s2_wgrad", ptr(ad), _lib.NHWC, ptr(gd), _lib.NCHW, ptr(dwt), ptr(dbt), N, 32, 32, 32, C, ptr(ws), stream())
+    check(dwt, P["dwt"], what=tag + "convT3 wgrad", **KTOL)
+    check(dbt, P["dbt"], what=tag + "convT3 bias grad", **KTOL)
+    for arena, fill in guards:
+        assert arena[0].item() == fill and torch.all(arena[-3:] == fill), tag + "the elements around a 4-byte-in output are untouched"
+    return dict(y=y, yb=yb, bits=bits, dx=dx, dxb=dxb, dw=dw, dwt=dwt)
+
+
 @pytest.mark.parametrize("C", [1, 3])
 @pytest.mark.parametrize("N", [191, 192])
 def test_thin_ends_at_the_wave_specialised_switch(N, C):
@@ -131,48 +220,35 @@ def test_thin_ends_at_the_wave_specialised_switch(N, C):
     gradients with a thin side: k_down_thin<C, MODE> / k_wgrad_thin<C> at 191 images, k_down_thin_ws<C, MODE> /
     k_wgrad_thin_ws<C, BIAS_BIG> at 192 (launch_down_thin_ws / launch_wgrad_thin_ws: N >= 192; a fp32 mask stays on
     k_down_thin<C, 1> on both sides)."""
-    tag = "thin N=%d C=%d " % (N, C)
-    ws = _ws()
-    # conv1: x[N,C,64,64] NCHW -> y[N,32,32,32] NHWC
-    x = torch.rand(N, C, 64, 64, generator=torch.Generator().manual_seed(1))
-    w = _rand(32, C, 4, 4, seed=2, scale=0.2)
-    b = _rand(32, seed=3, scale=0.1)
-    xd, wd, bd = dev(x), dev(w), dev(b)
-    wr, br = w.double().requires_grad_(True), b.double().requires_grad_(True)
-    pre = F.conv2d(x.double(), wr, br, stride=2, padding=1)
-    ref = torch.relu(pre).detach()
-    y = full(N, 32, 32, 32)
-    call("dvae_conv4s2_fwd", ptr(xd), _lib.NCHW, ptr(wd), ptr(bd), ptr(y), _lib.NHWC, N, C, 64, 64, 32, _lib.ACT_RELU, stream())
-    check(from_nhwc(y, N, 32, 32, 32), ref, what=tag + "conv1 fwd", **KTOL)
-    yb = full(N, 32, 32, 32)
-    bits = torch.full((N * 1024,), 0x55555555, dtype=torch.int32, device=DEV)
-    call("dvae_conv1_fwd_bits", ptr(xd), 0, ptr(wd), ptr(bd), ptr(yb), ptr(bits), N, C, stream())
-    check(from_nhwc(yb, N, 32, 32, 32), ref, what=tag + "conv1 fwd (bits)", **KTOL)
-    assert torch.equal(bits, _pack_bits(yb))
-    dy = _rand(N, 32, 32, 32, seed=4)                         # NCHW values
-    pre.backward(dy.double())
-    dw, db = full(32, C, 4, 4), full(32)
-    call("dvae_conv4s2_wgrad", ptr(xd), _lib.NCHW, ptr(nhwc(dy)), _lib.NHWC, ptr(dw), ptr(db), N, C, 64, 64, 32, ptr(ws), stream())
-    check(dw, wr.grad, what=tag + "conv1 wgrad", **KTOL)
-    check(db, br.grad, what=tag + "conv1 bias grad", **KTOL)
-    # convT3: a[N,32,32,32] NHWC -> C x 64 x 64 NCHW; input gradient masked by a, weight gradient (bias from the big side)
-    a = torch.relu(_rand(N, 32, 32, 32, seed=5))              # NCHW values
-    wt = _rand(32, C, 4, 4, seed=6, scale=0.2)
-    g = _rand(N, C, 64, 64, seed=7)
-    ar, wtr, btr = a.double().requires_grad_(True), wt.double().requires_grad_(True), torch.zeros(C, dtype=torch.float64, requires_grad=True)
-    F.conv_transpose2d(ar, wtr, btr, stride=2, padding=1).backward(g.double())
-    ad, gd, wtd = nhwc(a), dev(g), dev(wt)
-    ref_dx = ar.grad * (a > 0)
-    dx = full(N, 32, 32, 32)
-    call("dvae_convT4s2_dgrad", ptr(gd), _lib.NCHW, ptr(wtd), ptr(ad), ptr(dx), _lib.NHWC, N, 32, 32, 32, C, stream())
-    check(from_nhwc(dx, N, 32, 32, 32), ref_dx, what=tag + "convT3 dgrad", **KTOL)
-    dxb = full(N, 32, 32, 32)
-    call("dvae_convT3_dgrad_bits", ptr(gd), ptr(wtd), ptr(_pack_bits(ad)), ptr(dxb), N, C, stream())
-    check(from_nhwc(dxb, N, 32, 32, 32), ref_dx, what=tag + "convT3 dgrad (bits)", **KTOL)
-    dwt, dbt = full(32, C, 4, 4), full(C)
-    call("dvae_convT4s2_wgrad", ptr(ad), _lib.NHWC, ptr(gd), _lib.NCHW, ptr(dwt), ptr(dbt), N, 32, 32, 32, C, ptr(ws), stream())
-    check(dwt, wtr.grad, what=tag + "convT3 wgrad", **KTOL)
-    check(dbt, btr.grad, what=tag + "convT3 bias grad", **KTOL)
+    _thin_ends(N, C)
+
+
+@pytest.mark.parametrize("N,C", [(193, 1), (193, 3), (224, 3), (256, 1), (257, 1), (257, 3), (320, 3)])
+def test_thin_ends_past_the_wave_specialised_switch(N, C):
+    """The same bundle at the trip counts of the two wave-specialised kernels that 192 images (3 / 6 trips in every workgroup)
+    leave out.  k_down_thin_ws: 512 workgroups, image lane n0 = (b & 7) + 8 (b >> 6) in 0..63, ceil((N - n0) / 64) trips
+    through a ring of four tile stages and two output stages picked by the parity of the trip; k_wgrad_thin_ws: 256 workgroups,
+    n0 in 0..31, ceil((N - n0) / 32) trips through a ring of three.
+      N = 193: 4 | 3 and 7 | 6 trips (workgroups of image lane 0 against the rest);  224: 4 | 3 and 7 everywhere;
+      256: 4 everywhere (the ring depth) and 8;  257: 5 | 4 and 9 | 8;  320: 5 everywhere (odd, above the ring depth) and 10.
+    The fp32-mask input gradient stays on k_down_thin<C, 1>: min(8 N, 1536) workgroups, so 193 images are also its first
+    case past the cap (workgroups 0..7 take a second unit), as they are of k_wgrad_thin_reduce behind a full partial buffer."""
+    _thin_ends(N, C)
+
+
+def test_thin_ends_past_the_cap_on_buffers_the_wave_specialised_kernels_decline():
+    """N = 193, C = 3 with the images, the outputs and the bit planes 4 bytes into their buffers: modes 0, 2 and 3 of the fp32
+    k_down_thin and k_wgrad_thin<3, float>, which aligned buffers reach only below 192 images, past their grid caps (1544
+    units on 1536 workgroups; 1544 on WT_MAX_BLOCKS = 512: 4 | 3 trips).  conv_thin_ws.hip's header states that
+    k_down_thin_ws accumulates in k_down_thin's order and gives the same bits: the forward outputs, the emitted bit plane and
+    the bit-masked input gradient of the two runs are compared with torch.equal.  The weight gradients are not: k_wgrad_thin_ws
+    sums 16x16x4 tiles, k_wgrad_thin 32x32x2 tiles, in another order (its header promises k_wgrad_thin's partial-buffer LAYOUT
+    only), so they are held to fp64 alone."""
+    al = _thin_ends(193, 3)
+    mis = _thin_ends(193, 3, misaligned=True)
+    for k in ("y", "yb", "bits", "dxb"):
+        assert torch.equal(al[k], mis[k]), "k_down_thin_ws and k_down_thin differ in " + k
+    assert torch.equal(al["dx"], mis["dx"])                 # k_down_thin<3, 1> both times: alignment changes nothing
 
 
 # ---- 32-channel weight gradients: grid cap of conv_wgrad_ws.hip, reduction form of wgrad_reduce.h ---------------------------
@@ -410,11 +486,18 @@ def test_linear_outside_the_lds_resident_kernels(M, K, N):
     _linear(M, K, N, act=_lib.ACT_LEAKY02)
 
 
-@pytest.mark.parametrize("N,Hs", [(64, 16), (65, 16), (256, 8), (257, 8), (1024, 4), (1025, 4)])
+@pytest.mark.parametrize("N,Hs", [(64, 16), (65, 16), (256, 8), (257, 8), (1024, 4), (1025, 4),
+                                  (128, 16), (129, 16), (192, 16), (193, 16), (256, 16), (320, 16), (513, 8), (2049, 4)])
 def test_conv32_at_the_persistent_grid_switch(N, Hs):
     """The 32 <-> 32 channel forward / input-gradient kernels run min(units, 256) persistent workgroups (launch_down_dma_t,
     launch_up_ws_t, launch_down_t<4>, launch_up_t<4>): one unit per workgroup up to N * Hs * Hs / 64 = 256, the first
-    workgroup takes a second unit at the next image count."""
+    workgroup takes a second unit at the next image count.
+    Further trip counts of the software-pipelined loops (k_down32dma: a ring of three tile buffers; k_up32ws: two input and
+    two output stages, the tile after next in registers), HS 16 = 4 N units: 128 / 192 / 256 / 320 images are 2 / 3 / 4 / 5
+    trips in every workgroup, 129 and 193 are 3 | 2 and 4 | 3 (workgroups 0..3 against the rest); HS 8: 513 images are 3 | 2;
+    HS 4: 2049 images = 513 units are 3 | 2.  None of these was held to fp64 before: test_gpu_bench_sizes.py runs 261 and 1024
+    images at HS 16 (5 | 4, 16), 1027 / 1100 at HS 8 (5 | 4), 4099 / 4200 at HS 4 (5 | 4), and
+    test_conv32_on_staged_images_is_bit_identical_to_the_raw_weight_path compares two runs of one kernel."""
     Hb = 2 * Hs
     tag = "conv32 N=%d HS=%d " % (N, Hs)
     w, b = _rand(32, 32, 4, 4, seed=2, scale=0.2), _rand(32, seed=3, scale=0.1)
@@ -546,13 +629,14 @@ def test_elementwise_kernels_at_their_grid_caps(over):
 
 
 # ---- convT3 on the staged records, 3 channels, buffers that the matrix-core kernel declines -----------------------------------
-def test_convT3_staged_falls_back_to_the_packed_fma_kernel():
-    """dvae_convT3_fwd_staged at C = 3 runs k_up_thin_mm only on 16-byte aligned recon / g / fp32 target and a 4-byte aligned
-    uint8 target; here recon, g and the fp32 target are views 8 bytes into their arenas and the uint8 target 2 bytes into its
-    (the float2 / uchar2 accesses of k_up_thin_pk<3, *> stay naturally aligned), so all three instantiations of the fallback
-    run: reconstruction, dL/dlogit and the likelihood sum against fp64 at the tolerances of
-    test_convT3_forward_on_staged_pair_records."""
-    N, C = 3, 3
+_ALL_FALLBACK_COMBOS = tuple((dist, is_u8) for dist in (0, 1, 2) for is_u8 in (0, 1))
+
+
+def _convT3_staged_fallback(N, combos=_ALL_FALLBACK_COMBOS):
+    """dvae_convT3_fwd_staged at C = 3 on buffers k_up_thin_mm declines: the plain forward, then one fused launch per
+    (distribution, uint8 target) of `combos`; every unused partial slot (index >= the grid of min(8 N, 1536) workgroups) must
+    read 0.0 after a 7.0 pre-fill."""
+    C = 3
     w, b = _rand(32, C, 4, 4, seed=2, scale=0.2), _rand(C, seed=3, scale=0.1)
     wd, bd = dev(w), dev(b)
     pairs = torch.full((32 * _lib.thin_pair_floats(C),), 7.0, device=DEV)
@@ -584,6 +668,7 @@ def test_convT3_staged_falls_back_to_the_packed_fma_kernel():
     call("dvae_convT3_fwd_staged", ptr(x), ptr(pairs), ptr(bd), None, 0, ptr(r), None, 0, None, None, N, C, stream())
     check(r, pr.reshape(-1), what="fallback convT3 fwd", **tol)
     assert torch.all(ra[:2] == 7.0)
+    grid = min(8 * N, 1536)                                   # launch_up_thin_staged (conv_thin.hip)
     for dist in (0, 1, 2):
         if dist == 0:
             tot = F.binary_cross_entropy(pr, t64, reduction="sum"); gref = (pr - t64) / N
@@ -592,16 +677,35 @@ def test_convT3_staged_falls_back_to_the_packed_fma_kernel():
         else:
             tot = 3 * (pr - t64).abs().sum(); gref = 3 * torch.sign(pr - t64) * pr * (1 - pr) / N
         for tp, is_u8, nm in ((t32, 0, "fp32"), (t8, 1, "uint8")):
+            if (dist, is_u8) not in combos:
+                continue
             ra, r = off8()
             ga, gg = off8()
             part = torch.full((_lib.REC_NPART,), 7.0, device=DEV)
             call("dvae_convT3_fwd_staged", ptr(x), ptr(pairs), ptr(bd), ptr(tp), is_u8, ptr(r), ptr(gg), dist, ptr(coefd),
                  ptr(part), N, C, stream())
-            tag = "fallback convT3 %s target dist %d " % (nm, dist)
+            tag = "fallback convT3 N=%d %s target dist %d " % (N, nm, dist)
             check(r, pr.reshape(-1), what=tag + "recon", **tol)
             check(part.sum(), tot, rtol=1e-5, what=tag + "loss sum")
             check(gg, gref.reshape(-1), rtol=1e-4, atol_rel=4e-6, what=tag + "dL/dlogit")
             assert torch.all(ra[:2] == 7.0) and torch.all(ga[:2] == 7.0), tag + "the floats in front are untouched"
+            assert torch.all(part[grid:] == 0.0), tag + "unused partial slots read as zero"
+
+
+def test_convT3_staged_falls_back_to_the_packed_fma_kernel():
+    """dvae_convT3_fwd_staged at C = 3 runs k_up_thin_mm only on 16-byte aligned recon / g / fp32 target and a 4-byte aligned
+    uint8 target; here recon, g and the fp32 target are views 8 bytes into their arenas and the uint8 target 2 bytes into its
+    (the float2 / uchar2 accesses of k_up_thin_pk<3, *> stay naturally aligned), so all three instantiations of the fallback
+    run: reconstruction, dL/dlogit and the likelihood sum against fp64 at the tolerances of
+    test_convT3_forward_on_staged_pair_records."""
+    _convT3_staged_fallback(3)
+
+
+def test_convT3_staged_fallback_past_its_grid_cap():
+    """The same fall-back at 193 images: 1544 units on the 1536 workgroups of k_up_thin_pk<3, *> (launch_up_thin_staged), so
+    workgroups 0, 8, .. 56 (the XCD-aware unit map is on: the grid is a multiple of 64) take a second unit.  One launch without
+    a target and one per distribution, fp32 and uint8 targets in turn."""
+    _convT3_staged_fallback(193, combos=((0, 0), (1, 1), (2, 0)))
 
 
 # ---- Adam: the by-value table holds ADAM_MAX_T = 64 tensors per launch --------------------------------------------------------

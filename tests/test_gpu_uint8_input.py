@@ -38,10 +38,13 @@ def test_u8_to_f32_is_totensor():
         assert torch.equal(out.cpu(), to_tensor(u8))            # all 256 values, bit for bit
 
 
-@pytest.mark.parametrize("N,C", [(5, 3), (3, 1), (300, 3), (1024, 3)])
+@pytest.mark.parametrize("N,C", [(5, 3), (3, 1), (300, 3), (1024, 3), (193, 1), (64, 3), (65, 3), (65, 1)])
 def test_u8_kernels_equal_fp32_kernels_bitwise(N, C):
     """conv1 forward, conv1 weight gradient and the fused likelihood with a uint8 image == the same kernels on
-    ToTensor(image), bit for bit (the conversion is the only difference and it is exact)."""
+    ToTensor(image), bit for bit (the conversion is the only difference and it is exact).
+    193 single-channel images: the first count past the 1536-workgroup cap of k_down_thin / k_up_thin<C, true> (8 N units);
+    64 | 65 images: k_wgrad_thin<C, unsigned char> at WT_MAX_BLOCKS = 512 workgroups (8 N units).  What holds the uint8
+    kernels to fp64 at these counts is tests/test_gpu_trip_counts.py::test_u8_thin_kernels_vs_fp64."""
     g = torch.Generator().manual_seed(N)
     u8 = torch.randint(0, 256, (N, C, 64, 64), dtype=torch.uint8, generator=g)
     if C == 1:

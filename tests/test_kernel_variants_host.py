@@ -3,7 +3,10 @@
 * every __global__ kernel instantiation of the built library (the dvae::__device_stub__ symbols `nm -C` lists: one host stub
   per instantiation; only NAMES are read) matches exactly one row of VARIANTS, and every row matches an instantiation -- a
   kernel added to csrc/ without a row, or a row left behind by a removed kernel, fails here;
-* every row names a GPU test or a reason, every numeric switch two tests, and pytest collects every id named;
+* every row names a GPU test or a reason, every numeric switch two tests (or the reason no call reaches it, guarded by a host
+  test), OPEN_SWITCHES is empty, and pytest collects every id named;
+* TRIP_CLASSES: the launch arithmetic, evaluated at the image count of each named test, gives the trip-count class the table
+  claims for it, and every required class of every persistent kernel family has a test;
 * tools/kernel_trace_names.py reduces a kernel trace to the same spelling of the names."""
 import os
 import re
@@ -83,15 +86,88 @@ def test_every_row_names_a_test_or_a_reason_and_cites_its_launch_site():
                 lines[f] = fh.read().split("\n")
         return 0 < int(ln) <= len(lines[f]) and bool(lines[f][int(ln) - 1].strip())
     for s in KV.SWITCHES:
-        assert s.below_test and s.above_test and s.below and s.above, s
-        assert s.below_test != s.above_test, s                      # one test id PER SIDE
+        assert s.launcher and s.variable and s.threshold, s
         assert cited(s.where), s
-    for o in KV.OPEN_SWITCHES:
-        assert len(o) == 4 and all(o) and cited(o[3]), o
+        if s.reason is None:
+            assert s.below_test and s.above_test and s.below and s.above, s
+            assert s.below_test != s.above_test, s                  # one test id PER SIDE
+        else:                                                       # out of reach of the C-ABI: the argument, no half-filled pair
+            assert s.below is s.above is s.below_test is s.above_test is None, s
+            assert len(s.reason) > 80 and "test_kernel_variants_host.py::" in s.reason, s      # ... and the host test that guards it
+            guard = s.reason.split("test_kernel_variants_host.py::")[1].split()[0]
+            assert callable(globals().get(guard)), guard
+    assert len({(s.launcher, s.variable, s.where) for s in KV.SWITCHES}) == len(KV.SWITCHES), "a switch is listed twice"
+    assert KV.OPEN_SWITCHES == [], ("a threshold newly found in a launcher goes into SWITCHES with a test on either side of it (or "
+                                    "the reason no call can reach it), not into OPEN_SWITCHES: %s" % (KV.OPEN_SWITCHES,))
+
+
+def test_the_workspace_keeps_the_split_contraction_clamps_out_of_reach():
+    """pick_split and launch_linear_wgrad (linear.hip:616, 718) halve the number of contraction slices while they do not fit the
+    workspace.  capi.hip hands them dvae_conv_wgrad_ws_floats() floats, more than any slice count their first loops can ask for
+    (KV.PICK_SPLIT_WS_BOUND: the SWITCHES row gives the argument), so no test sits at that flip -- if the workspace ever shrinks
+    below the bound, this fails instead of the clamp being reached untested.  (Needs the library, not a GPU.)"""
+    assert KV.PICK_SPLIT_WS_BOUND == 2162688
+    def slices(tiles):                                              # pick_split's first loop on a contraction long enough never to end it
+        S = 1
+        while S < 16 and tiles * S < 256:
+            S *= 2
+        return S
+    # (the clamp runs only while S > 1; an output of `tiles` 64x64 tiles has at most 4096 tiles elements)
+    worst = max(slices(t) * (4096 * t + 4096) for t in range(1, 256))
+    assert slices(256) == 1 and worst < KV.PICK_SPLIT_WS_BOUND, worst
+    assert _lib.lib().dvae_conv_wgrad_ws_floats() >= KV.PICK_SPLIT_WS_BOUND
+
+
+def _trip_counts(fam, N):
+    """the trip count of every workgroup of `fam` at N images, by its expressions."""
+    cdiv = lambda a, b: max(0, -(-a // b))
+    grid = eval(fam.grid, {"N": N, "cdiv": cdiv, "min": min})
+    return grid, [eval(fam.trips, {"N": N, "b": b, "grid": grid, "cdiv": cdiv}) for b in range(grid)]
+
+
+def _trip_class(fam, N):
+    grid, trips = _trip_counts(fam, N)
+    lo, hi = min(trips), max(trips)
+    assert lo >= 1 and sum(trips) > 0, (fam.family, N, "an idle workgroup")
+    return "u%d" % lo if lo == hi else ("m%d" % lo if hi == lo + 1 else "spread %d..%d" % (lo, hi))
+
+
+def test_trip_class_table_claims_what_the_launch_arithmetic_gives():
+    csrc = os.path.join(ROOT, "disentangling-vae_amd", "csrc")
+    assert len(KV.TRIP_CLASSES) == 10
+    for fam in KV.TRIP_CLASSES:
+        f, _, ln = fam.where.partition(":")
+        with open(os.path.join(csrc, f)) as fh:
+            line = fh.read().split("\n")[int(ln) - 1]
+        assert "grid" in line, (fam.family, fam.where, line)        # the line that sizes the grid
+        have = {}
+        for cls, N, test in fam.cases:
+            assert N >= fam.n_from, (fam.family, test)
+            assert test.split("[")[1].split("-")[0].rstrip("]") == str(N), (fam.family, test, N)     # the id runs that image count
+            assert _trip_class(fam, N) == cls, (fam.family, test, N, cls, _trip_class(fam, N))
+            have.setdefault(cls, test)
+        tmin = int(_trip_class(fam, fam.n_from)[1:])
+        for t in range(tmin, fam.depth + 2):                        # every uniform count up to one past the pipeline depth
+            if t in fam.unreachable:
+                assert all(_trip_class(fam, N) != "u%d" % t for N in range(fam.n_from, 4097)), (fam.family, t)
+            else:
+                assert "u%d" % t in have, "%s: no test at %d trips in every workgroup" % (fam.family, t)
+        above = [int(c[1:]) for c in have if c[0] == "u" and int(c[1:]) > fam.depth]
+        assert any(t % 2 for t in above) and any(t % 2 == 0 for t in above), "%s: an odd and an even uniform count above depth %d" % (fam.family, fam.depth)
+        assert any(c[0] == "m" for c in have), "%s: no mixed launch" % fam.family
+    # the expressions themselves, at launches worked out by hand from the kernels
+    by = {f.family: f for f in KV.TRIP_CLASSES}
+    assert _trip_counts(by["k_down_thin_ws"], 193)[1].count(4) == 8 and _trip_counts(by["k_down_thin_ws"], 193)[1].count(3) == 504
+    assert _trip_counts(by["k_wgrad_thin_ws"], 193)[1].count(7) == 8
+    g, tr = _trip_counts(by["k_up_thin fused"], 193)                 # image 192 = lane 0 of the unit map: workgroups 0, 8, .. 56
+    assert g == 1536 and [b for b in range(g) if tr[b] == 2] == list(range(0, 64, 8))
+    assert _trip_counts(by["k_up_thin_mm"], 171) == (512, [2] + [1] * 511)
+    assert _trip_counts(by["k_wgrad32ws (HS 16)"], 129)[0] == 192 and _trip_counts(by["k_wgrad32ws (HS 16)"], 321)[0] == 256
 
 
 def test_every_named_test_is_collected():
-    ids = {v.test for v in KV.VARIANTS if v.test} | {t for s in KV.SWITCHES for t in (s.below_test, s.above_test)}
+    ids = ({v.test for v in KV.VARIANTS if v.test} | {t for s in KV.SWITCHES for t in (s.below_test, s.above_test) if t}
+           | {c[2] for f in KV.TRIP_CLASSES for c in f.cases})
     assert all(i.startswith("tests/test_gpu_") for i in ids)
     files = sorted({i.split("::")[0] for i in ids})
     r = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + files, cwd=ROOT,
