@@ -1,4 +1,4 @@
-"""Build libdvae_hip.so, libdvae_eval_hip.so, libdvae_score_hip.so, libdvae_info_hip.so and libdvae_irs_hip.so (gfx950) in-tree: hipcc cross-compiles without a GPU.
+"""Build libdvae_hip.so, libdvae_eval_hip.so, libdvae_score_hip.so, libdvae_info_hip.so, libdvae_irs_hip.so and libdvae_unsup_hip.so (gfx950) in-tree: hipcc cross-compiles without a GPU.
 
     python disentangling-vae_amd/build.py [--force] [--debug]
 
@@ -12,7 +12,9 @@ libdvae_score_hip.so (include/dvae_score_hip.h: the FactorVAE / beta-VAE score k
 libdvae_info_hip.so (include/dvae_info_hip.h: the moments / joint-histogram kernels of the MIG, modularity and SAP scores,
 csrc/factor_info.hip) a fourth;
 libdvae_irs_hip.so (include/dvae_irs_hip.h: the group-mean / segmented-selection kernels of the interventional robustness score,
-csrc/factor_irs.hip) a fifth.
+csrc/factor_irs.hip) a fifth;
+libdvae_unsup_hip.so (include/dvae_unsup_hip.h: the covariance / pair-histogram kernels of the label-free scores,
+csrc/latent_pairs.hip) a sixth.
 """
 import glob
 import os
@@ -44,6 +46,10 @@ INFO_HEADERS = HEADERS + [os.path.join(HERE, "..", "include", "dvae_info_hip.h")
 IRS_LIB = os.path.join(HERE, "lib", "libdvae_irs_hip.so")
 IRS_SOURCES = ["factor_irs"]
 IRS_HEADERS = HEADERS + [os.path.join(HERE, "..", "include", "dvae_irs_hip.h")]
+# the label-free score library (Gaussian total correlation, Wasserstein correlation, latent-latent mutual information): a sixth
+UNSUP_LIB = os.path.join(HERE, "lib", "libdvae_unsup_hip.so")
+UNSUP_SOURCES = ["latent_pairs"]
+UNSUP_HEADERS = HEADERS + [os.path.join(HERE, "..", "include", "dvae_unsup_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 
@@ -81,7 +87,7 @@ def _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose):
 
 
 def build(force=False, verbose=True, debug=None):
-    """Build the five libraries; returns the path of libdvae_hip.so."""
+    """Build the six libraries; returns the path of libdvae_hip.so."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if debug is None:
         debug = os.environ.get("DVAE_BUILD_DEBUG", "0") == "1"
@@ -94,6 +100,7 @@ def build(force=False, verbose=True, debug=None):
     _build_target(hipcc, SCORE_LIB, SCORE_SOURCES, SCORE_HEADERS, flags, os.path.join(OBJ, "flags_score.txt"), force, verbose)
     _build_target(hipcc, INFO_LIB, INFO_SOURCES, INFO_HEADERS, flags, os.path.join(OBJ, "flags_info.txt"), force, verbose)
     _build_target(hipcc, IRS_LIB, IRS_SOURCES, IRS_HEADERS, flags, os.path.join(OBJ, "flags_irs.txt"), force, verbose)
+    _build_target(hipcc, UNSUP_LIB, UNSUP_SOURCES, UNSUP_HEADERS, flags, os.path.join(OBJ, "flags_unsup.txt"), force, verbose)
     return LIB
 
 

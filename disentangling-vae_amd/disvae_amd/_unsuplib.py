@@ -1,0 +1,69 @@
+"""ctypes binding of libdvae_unsup_hip.so (the C-ABI declared in include/dvae_unsup_hip.h): the kernels behind the label-free
+scores (Gaussian total correlation, Gaussian Wasserstein correlation, mean pairwise mutual information of the discretised
+latents) -- the D x D covariance of the table of posterior means and the joint histograms of every pair of its columns.
+
+A sixth library next to libdvae_hip.so (_lib.py), libdvae_eval_hip.so (_evallib.py), libdvae_score_hip.so (_scorelib.py),
+libdvae_info_hip.so (_infolib.py) and libdvae_irs_hip.so (_irslib.py), loaded lazily on first use.  As there, the library is the
+product: no CPU or PyTorch fallback, a missing shared object or symbol fails loudly.  Calls go straight to the library -- they
+are never recorded into a launch plan (graph.py replays the training step only).
+"""
+import ctypes
+import os
+
+from ._lib import DvaeHipError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("DVAE_UNSUP_HIP_LIB", os.path.join(_HERE, "..", "lib", "libdvae_unsup_hip.so"))
+
+VERSION = 1                  # DVAE_UNSUP_VERSION
+MAX_D = 64                   # DVAE_UNSUP_MAX_D: D above it is refused
+MAX_BINS = 64                # DVAE_UNSUP_MAX_BINS: n_bins above it is refused
+MOMENTS_BLOCK_ROWS = 1024    # DVAE_UNSUP_MOMENTS_BLOCK_ROWS: rows of one workgroup of the moments pass ...
+HIST_BLOCK_ROWS = 4096       # DVAE_UNSUP_HIST_BLOCK_ROWS: ... and of the histogram pass,
+MAX_BLOCKS = 1024            # DVAE_UNSUP_MAX_BLOCKS: until that many workgroups (per tile of pairs) are reached; then the chunks grow
+MOMENTS_THREAD_SUMS = 9      # DVAE_UNSUP_MOMENTS_THREAD_SUMS: sums one thread of the moments pass keeps at most (256 threads)
+HIST_LDS_INTS = 4096         # DVAE_UNSUP_HIST_LDS_INTS: the counters of one tile of pairs, n_bins^2 per pair, one pair at least
+
+_p = ctypes.c_void_p
+_i = ctypes.c_int
+_l = ctypes.c_long
+
+# name -> argtypes (all return int unless listed in _RESTYPE)
+SIGNATURES = {
+    "dvae_unsup_version": [],
+    "dvae_unsup_last_error": [],
+    "dvae_unsup_moments_ws_floats": [_l, _i, _l],
+    "dvae_unsup_pair_hist_ws_floats": [_l, _i, _l, _i],
+    "dvae_unsup_moments": [_p, _p, _l, _i, _l, _p, _p, _p, _p, _p, _p],
+    "dvae_unsup_pair_hist": [_p, _p, _p, _l, _i, _l, _i, _p, _p, _p],
+}
+_RESTYPE = {"dvae_unsup_last_error": ctypes.c_char_p, "dvae_unsup_moments_ws_floats": ctypes.c_size_t,
+            "dvae_unsup_pair_hist_ws_floats": ctypes.c_size_t}
+
+_lib = None
+
+
+def lib():
+    """Load (once) and return the ctypes handle; raises if the library is absent."""
+    global _lib
+    if _lib is None:
+        path = os.path.abspath(LIB_PATH)
+        if not os.path.exists(path):
+            raise DvaeHipError(
+                "libdvae_unsup_hip.so not found at %s -- build it with `python disentangling-vae_amd/build.py` "
+                "(there is no CPU / PyTorch fallback for the label-free score kernels)" % path)
+        h = ctypes.CDLL(path)
+        for name, argtypes in SIGNATURES.items():
+            fn = getattr(h, name)  # AttributeError if the symbol is missing: fail loudly
+            fn.argtypes = argtypes
+            fn.restype = _RESTYPE.get(name, ctypes.c_int)
+        _lib = h
+    return _lib
+
+
+def call(name, *args):
+    """Call an int-returning entry point, raise on a non-zero status."""
+    h = lib()
+    rc = getattr(h, name)(*args)
+    if rc != 0:
+        raise DvaeHipError("%s failed (%d): %s" % (name, rc, h.dvae_unsup_last_error().decode()))

@@ -30,6 +30,12 @@
   launches on the table where it lies (libdvae_irs_hip.so); the counts and two order statistics per (group, latent) cross to
   the host, where the quantiles are interpolated and the score is combined in fp64.  Definition: disentanglement_lib's irs.py.
   Written to irs.log by ``__call__(is_irs=True)``.
+* Label-free scores (disentanglement_lib's unsupervised_metrics.py), new (``compute_unsupervised_scores`` /
+  ``unsupervised_scores_from_table``): Gaussian total correlation, Gaussian Wasserstein correlation and the mean pairwise
+  mutual information of the discretised latents, for data sets WITHOUT known factors (CelebA, Chairs, MNIST).  The D x D
+  covariance in fp64 and the D (D - 1) / 2 pair histograms as two HIP passes on the table where it lies
+  (libdvae_unsup_hip.so); the statistics cross to the host, where the scores are combined in fp64.
+  Written to unsupervised_scores.log by ``__call__(is_unsupervised=True)``.
 """
 import logging
 import math
@@ -40,7 +46,7 @@ from timeit import default_timer
 import numpy as np
 import torch
 
-from . import _evallib, _infolib, _irslib, _lib, _scorelib
+from . import _evallib, _infolib, _irslib, _lib, _scorelib, _unsuplib
 from ._lib import call, ptr
 from .engine import _stream
 from .likelihood import _ScorePasses, check_rec_dist, log_likelihood
@@ -55,6 +61,7 @@ ELBO_DECOMPOSITION_FILE = "elbo_decomposition.log"
 FACTOR_SCORES_FILE = "factor_scores.log"
 INFORMATION_SCORES_FILE = "information_scores.log"
 IRS_FILE = "irs.log"
+UNSUPERVISED_SCORES_FILE = "unsupervised_scores.log"
 
 
 class Evaluator:
@@ -71,12 +78,13 @@ class Evaluator:
 
     def __call__(self, data_loader, is_metrics=False, is_losses=True, is_log_likelihood=False, n_samples=128,
                  is_decomposition=False, n_samples_decomposition=10000, is_scores=False, is_information=False,
-                 is_irs=False):
+                 is_irs=False, is_unsupervised=False):
         """evaluate.py:60-95.  is_log_likelihood: also write compute_log_likelihood(data_loader, n_samples) to
         log_likelihood.log; is_decomposition: also write compute_elbo_decomposition(data_loader, n_samples_decomposition) to
         elbo_decomposition.log; is_scores: also write compute_factor_scores(data_loader) to factor_scores.log; is_information: also
         write compute_information_scores(data_loader), without its [D, K] matrices, to information_scores.log; is_irs: also write compute_irs(data_loader),
-        its arrays as lists, to irs.log (the return value stays the reference's (metric, losses))."""
+        its arrays as lists, to irs.log; is_unsupervised: also write compute_unsupervised_scores(data_loader), its arrays as lists and
+        without its [D, D] matrix, to unsupervised_scores.log (the return value stays the reference's (metric, losses))."""
         start = default_timer()
         is_still_training = self.model.training
         self.model.eval()
@@ -125,6 +133,14 @@ class Evaluator:
             self.logger.info('IRS: {}'.format(irs))
             os.makedirs(self.save_dir, exist_ok=True)
             save_metadata(irs, self.save_dir, filename=IRS_FILE)
+        if is_unsupervised:
+            self.logger.info('Computing the label-free scores...')
+            unsup = self.compute_unsupervised_scores(data_loader)
+            unsup = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in unsup.items()
+                     if not (isinstance(v, np.ndarray) and v.ndim > 1)}
+            self.logger.info('Unsupervised scores: {}'.format(unsup))
+            os.makedirs(self.save_dir, exist_ok=True)
+            save_metadata(unsup, self.save_dir, filename=UNSUPERVISED_SCORES_FILE)
         if is_still_training:
             self.model.train()
         self.logger.info('Finished evaluating after {:.1f} min.'.format((default_timer() - start) / 60))
@@ -321,6 +337,23 @@ class Evaluator:
         if mean.shape[0] != n:
             raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (mean.shape[0], lat_sizes))
         return irs_from_table(mean, lat_sizes, diff_quantile=diff_quantile, factor_bins=factor_bins, n_samples=n_samples, seed=seed)
+
+    # ------------------------------------------------------------------ label-free scores
+    def compute_unsupervised_scores(self, dataloader, n_samples=None, n_bins=20, seed=0):
+        """Gaussian total correlation, Gaussian Wasserstein correlation and mean pairwise mutual information of the model's
+        representation (unsupervised_scores_from_table below, on the posterior means of the whole data set through the native
+        encoder).  The data set needs NO known factors of variation; every argument that can be is checked before any device
+        work; train / eval mode is restored."""
+        ds = getattr(dataloader, "dataset", None)
+        _check_unsupervised_arguments(len(ds) if hasattr(ds, "__len__") else None, None, n_bins, n_samples)
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            mean, _logvar = self._encode_dataset(dataloader)
+        finally:
+            if was_training:
+                self.model.train()
+        return unsupervised_scores_from_table(mean, n_bins=n_bins, n_samples=n_samples, seed=seed)
 
     # ------------------------------------------------------------------ MIG / AAM (evaluate.py:119-317)
     def compute_metrics(self, dataloader, sample_idx=None, n_samples=10000):
@@ -914,4 +947,132 @@ def irs_from_table(mean, lat_sizes, diff_quantile=0.99, factor_bins=20, n_sample
     scores = irs_from_statistics(counts, n_groups, stat_lo, stat_hi, dev_max, diff_quantile)
     scores.update(n_groups=n_groups, n_samples=S, diff_quantile=float(diff_quantile),
                   factor_bins=None if factor_bins is None else int(factor_bins))
+    return scores
+
+
+# ---------------------------------------------------------------------- label-free scores on a table of means
+def _check_unsupervised_arguments(n, dim, n_bins, n_samples):
+    """n / dim: None where not known yet (a data set without __len__; before the encoder ran)."""
+    if not 1 <= int(n_bins) <= _unsuplib.MAX_BINS:
+        raise ValueError("n_bins must lie in [1, %d], got %r" % (_unsuplib.MAX_BINS, n_bins))
+    if n_samples is not None and int(n_samples) < 1:
+        raise ValueError("n_samples must be at least 1 or None, got %r" % (n_samples,))
+    if n is not None:
+        if n < 1:
+            raise ValueError("the table of means must hold one row or more")
+        if n_samples is not None and int(n_samples) > n:
+            raise ValueError("n_samples must lie in [1, %d] (rows are drawn without replacement) or be None, got %r" % (n, n_samples))
+    if dim is not None and not 1 <= dim <= _unsuplib.MAX_D:
+        raise ValueError("mean must have between 1 and %d latent dimensions, got %d" % (_unsuplib.MAX_D, dim))
+
+
+def unsupervised_scores_from_statistics(col_min, col_max, cov, counts, n_bins, active_threshold=0.01):
+    """The host half of unsupervised_scores_from_table, fp64: col_min / col_max [D] and cov [D, D] of dvae_unsup_moments, ``counts``
+    int [D (D - 1) / 2, n_bins, n_bins] of dvae_unsup_pair_hist (None or empty for D = 1).  disentanglement_lib's
+    unsupervised_metrics.py on the posterior means:
+
+    live [D] bool = col_max > col_min: an exactly constant column has variance 0, its logarithm would make every Gaussian score
+    infinite, so it is dropped from them (as the IRS drops it);  C = cov on the live block, v = diag C;
+    gaussian_total_correlation = KL(N(m, C) || N(m, diag v)) = 0.5 (sum log v - logdet C), inf when C is not positive definite to
+    working precision (numpy.linalg.slogdet's sign), 0.0 with fewer than two live columns;
+    gaussian_wasserstein_correlation = W2^2(N(m, C), N(m, diag v)) = 2 tr C - 2 tr sqrtm(diag(v) C) = 2 sum v - 2 sum sqrt(max(
+    eigvalsh(V^1/2 C V^1/2), 0)) (the two matrices are similar; the symmetric form needs no scipy), and
+    gaussian_wasserstein_correlation_norm = that / sum v; both 0.0 without a live column (eigvalsh leaves an ABSOLUTE error of about
+    2^-53 max(v)^2 in every eigenvalue, so a live column whose variance is below 1e-4 of the largest costs the score up to
+    1e-8 sum v: harmless for reading it, and the reason the tests keep their near-collapsed columns above that);
+    mutual_information [D, D]: nats between the discretised columns d and e from the integer counts, as
+    information_scores_from_statistics forms it (c S / (row col), zero cells skipped), symmetric, zero diagonal;
+    mutual_info_score = sum of it / (D^2 - D), over ALL D columns as disentanglement_lib does (0.0 for D = 1);
+    active_units = #{d : cov[d, d] > active_threshold} (Burda et al. 2016);  variances = diag cov."""
+    col_min, col_max = np.asarray(col_min), np.asarray(col_max)
+    cov = np.asarray(cov, dtype=np.float64)
+    D, n_bins = cov.shape[0], int(n_bins)
+    assert cov.shape == (D, D) and col_min.shape == col_max.shape == (D,), (cov.shape, col_min.shape, col_max.shape)
+    live = col_max > col_min
+    C = cov[np.ix_(live, live)]
+    v = np.diag(C).copy()
+    tc = wass = wass_norm = 0.0
+    if live.sum() >= 2:
+        sign, logdet = np.linalg.slogdet(C)
+        tc = float(0.5 * (np.log(v).sum() - logdet)) if sign > 0 else float("inf")
+    if live.any():
+        root = np.sqrt(v)
+        eig = np.linalg.eigvalsh(root[:, None] * C * root[None, :])
+        wass = float(2 * v.sum() - 2 * np.sqrt(np.maximum(eig, 0.0)).sum())
+        wass_norm = float(wass / v.sum())
+    mi = np.zeros((D, D))
+    P = D * (D - 1) // 2
+    if P:
+        block = np.asarray(counts).astype(np.int64).reshape(P, n_bins, n_bins).astype(np.float64)
+        S = block[0].sum()
+        row, col = block.sum(axis=2, keepdims=True), block.sum(axis=1, keepdims=True)
+        # P / (P_row P_col) = c S / (row col) from the integer counts: both products are exact in fp64, so a pair with a collapsed
+        # latent (row = S) gives log(1) = 0 exactly
+        nz = block > 0
+        term = np.zeros_like(block)
+        term[nz] = block[nz] / S * np.log((block * S)[nz] / (row * col)[nz])
+        upper = np.triu_indices(D, 1)                                    # (d, e), d < e, in lexicographic order: the pairs' own
+        mi[upper] = term.sum(axis=(1, 2))
+        mi = mi + mi.T
+    return {"gaussian_total_correlation": tc, "gaussian_wasserstein_correlation": wass,
+            "gaussian_wasserstein_correlation_norm": wass_norm, "mutual_info_score": float(mi.sum() / (D * D - D)) if D > 1 else 0.0,
+            "mutual_information": mi, "active_units": int((np.diag(cov) > active_threshold).sum()), "variances": np.diag(cov).copy(),
+            "live": live}
+
+
+def unsupervised_scores_from_table(mean, n_bins=20, n_samples=None, seed=0, rows=None, active_threshold=0.01):
+    """Gaussian total correlation, Gaussian Wasserstein correlation and mean pairwise mutual information of a representation given as
+    the fp32 [N, D] table ``mean`` (on the GPU), D <= 64 (formulas: unsupervised_scores_from_statistics).  No factor of variation is
+    needed: this is what a data set without lat_sizes can be given.
+
+    n_samples=None: every row; else rows = randperm(N)[:n_samples] from a private generator seeded with ``seed`` (the same seed
+    gives the same bits, the global random states are untouched); ``rows`` ([S] row numbers in [0, N), repeats allowed) injects
+    the selection.  Every size and argument is checked before any device work, and a table with a NaN or an infinity raises
+    ValueError.  dvae_unsup_moments, ONE device-to-host copy of its outputs (the covariance stays fp64 throughout), the bin edges
+    of numpy.histogram on the host (histogram_edges: disentanglement_lib's histogram discretiser bit for bit),
+    dvae_unsup_pair_hist (not for D = 1), ONE copy of the counts, the scores in fp64 on the host.  Returns the dict of
+    unsupervised_scores_from_statistics plus {"n_samples", "n_bins"}: Python and numpy values."""
+    n_bins = int(n_bins)
+    if mean.dim() != 2:
+        raise ValueError("mean must be an [N, D] table, got shape %s" % (tuple(mean.shape),))
+    n, dim = int(mean.shape[0]), int(mean.shape[1])
+    _check_unsupervised_arguments(n, dim, n_bins, None if rows is not None else n_samples)
+    if rows is not None:
+        rows = torch.as_tensor(rows).to(torch.int64).reshape(-1)
+        if rows.numel() < 1 or not (0 <= int(rows.min()) and int(rows.max()) < n):
+            raise ValueError("rows must hold one row number or more, each in [0, %d)" % n)     # (the kernels do not check them)
+    if not bool(torch.isfinite(mean).all()):
+        raise ValueError("the table of means holds a NaN or an infinity")
+    if not mean.is_cuda:
+        raise _lib.DvaeHipError("unsupervised_scores_from_table needs the table on the GPU (there is no CPU / PyTorch fallback "
+                                "for the label-free score kernels)")
+    dev = mean.device
+    table = mean.detach().to(torch.float32).contiguous()
+    if rows is not None:
+        rows = rows.to(dev).contiguous()
+    elif n_samples is not None:
+        gen = torch.Generator(device=dev).manual_seed(int(seed))
+        rows = torch.randperm(n, generator=gen, device=dev)[:int(n_samples)].contiguous()
+    S = n if rows is None else int(rows.numel())
+    U = _unsuplib.lib()
+    st = _stream()
+    ws = torch.empty(max(U.dvae_unsup_moments_ws_floats(n, dim, S), U.dvae_unsup_pair_hist_ws_floats(n, dim, S, n_bins), 1),
+                     dtype=torch.float32, device=dev)
+    out = torch.empty(dim * dim + 2 * dim, dtype=torch.float64, device=dev)      # cov, mean, then min and max: 2 D floats in D doubles
+    cov_dev, mean_dev, minmax_dev = out[:dim * dim], out[dim * dim:dim * dim + dim], out[dim * dim + dim:].view(torch.float32)
+    _unsuplib.call("dvae_unsup_moments", ptr(table), ptr(rows), n, dim, S, ptr(ws), ptr(minmax_dev[:dim]), ptr(minmax_dev[dim:]),
+                   ptr(mean_dev), ptr(cov_dev), st)
+    host = out.cpu()                                                               # ONE device->host copy
+    cov = host[:dim * dim].numpy().reshape(dim, dim)
+    minmax = host[dim * dim + dim:].view(torch.float32).numpy()
+    col_min, col_max = minmax[:dim], minmax[dim:]
+    counts = None
+    if dim > 1:
+        edges = np.stack([histogram_edges(col_min[d], col_max[d], n_bins) for d in range(dim)])
+        edges_dev = torch.from_numpy(edges).to(dev)
+        counts_dev = torch.empty(dim * (dim - 1) // 2, n_bins, n_bins, dtype=torch.int32, device=dev)
+        _unsuplib.call("dvae_unsup_pair_hist", ptr(table), ptr(rows), ptr(edges_dev), n, dim, S, n_bins, ptr(ws), ptr(counts_dev), st)
+        counts = counts_dev.cpu().numpy()                                          # ONE copy of the counts
+    scores = unsupervised_scores_from_statistics(col_min, col_max, cov, counts, n_bins, active_threshold)
+    scores.update(n_samples=S, n_bins=n_bins)
     return scores
