@@ -1,20 +1,11 @@
 // extern "C" surface of libdvae_hip.so (see include/dvae_hip.h): argument checking and
 // dispatch between the tuned gfx950 kernels and the shape-generic HIP kernels.
 #include <mutex>
-#include <stdarg.h>
 #include <stdlib.h>
 #include "common.h"
+#include "last_error.h"
 
 namespace dvae {
-
-static thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
 
 bool use_generic_only() {
   const char* e = getenv("DVAE_FORCE_GENERIC");
@@ -71,7 +62,7 @@ using namespace dvae;
 extern "C" {
 
 int dvae_version(void) { return DVAE_VERSION; }
-const char* dvae_last_error(void) { return g_err; }
+const char* dvae_last_error(void) { return last_error(); }
 
 int dvae_conv4s2_fwd(const float* x, int x_layout, const float* w, const float* b, float* y, int y_layout, int N,
                      int Cin, int H, int W, int Cout, int act, void* stream) {

@@ -20,22 +20,11 @@
 // times larger than their sum and cancel catastrophically in fp32: the dominant densities -- z a fraction of a standard deviation
 // from mu -- would come out with absolute errors of order 1e-3 .. 1 in the exponent.  The difference is formed first.
 #include <float.h>
-#include <stdarg.h>
-
 #include "../../include/dvae_eval_hip.h"
 #include "common.h"
+#include "last_error.h"
 
 namespace dvae {
-
-static thread_local char g_eval_err[512] = "";
-
-// the check macros of common.h report through dvae::set_error: this library keeps its own (capi.hip's is in libdvae_hip.so)
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_eval_err, sizeof(g_eval_err), fmt, ap);
-  va_end(ap);
-}
 
 namespace {
 
@@ -207,7 +196,7 @@ using namespace dvae;
 extern "C" {
 
 int dvae_eval_version(void) { return DVAE_EVAL_VERSION; }
-const char* dvae_eval_last_error(void) { return g_eval_err; }
+const char* dvae_eval_last_error(void) { return last_error(); }
 
 size_t dvae_eval_joint_logq_ws_floats(long N, int D, long S) {
   if (N <= 0 || D <= 0 || S <= 0) return 0;

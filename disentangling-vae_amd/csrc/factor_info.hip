@@ -18,31 +18,19 @@
 // most n_bins adds on distinct counters; the other factors take one add per lane.  Counters live in LDS when one latent's
 // n_bins * sum(lat_sizes) fit (DVAE_INFO_HIST_LDS_INTS) and are added to `counts` at the workgroup's end, else the same adds go
 // to global memory.  Integer adds: any order gives the same counts.  k_info_zero clears `counts` first.
-#include <stdarg.h>
-
 #include "../../include/dvae_info_hip.h"
 #include "common.h"
+#include "last_error.h"
+#include "table_stats.h"
 
 namespace dvae {
-
-static thread_local char g_info_err[512] = "";
-
-// the check macros of common.h report through dvae::set_error: this library keeps its own (capi.hip's is in libdvae_hip.so)
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_info_err, sizeof(g_info_err), fmt, ap);
-  va_end(ap);
-}
 
 namespace {
 
 #define INFO_T 256
 #define INFO_KMAX DVAE_INFO_MAX_FACTORS
 
-template <class T>
-__host__ __device__ __forceinline__ T lesser(T a, T b) { return a < b ? a : b; }
-
+// (kept here: built on a helper shared with factor_irs.hip's load_factor, k_info_joint_hist compiled to other machine code)
 // sizes (>= 1) and strides of the K factors, the same in every thread.  A stride that does not fit 32 bits saturates: row numbers
 // are below 2^31, the digit is then 0.  Returns sum(lat_sizes), or -1 when a size is not positive.
 struct Factors {
@@ -66,13 +54,6 @@ __device__ __forceinline__ long load_factors(const int32_t* __restrict__ lat_siz
   }
   return ok ? sum : -1;
 }
-
-// doubles cross the fp32 workspace as two words: ws is aligned to 4 bytes and no more
-__device__ __forceinline__ void put_f64(float* p, double v) {
-  p[0] = __int_as_float(__double2loint(v));
-  p[1] = __int_as_float(__double2hiint(v));
-}
-__device__ __forceinline__ double get_f64(const float* p) { return __hiloint2double(__float_as_int(p[1]), __float_as_int(p[0])); }
 
 // combination of v over the 256 / DP threads that share a dimension (same t % DP); every thread gets the same bits.  Fixed
 // order: the xor butterfly inside a wave, then the waves in wave order.  EVERY thread of the workgroup calls.
@@ -227,7 +208,7 @@ __global__ __launch_bounds__(INFO_T) void k_info_moments_finish(const float* __r
 }
 
 __global__ __launch_bounds__(INFO_T) void k_info_zero(int32_t* __restrict__ p, long n) {
-  for (long i = blockIdx.x * (long)INFO_T + threadIdx.x; i < n; i += (long)gridDim.x * INFO_T) p[i] = 0;
+  zero_i32<INFO_T>(p, n);
 }
 
 template <bool LDS>
@@ -259,6 +240,7 @@ __global__ __launch_bounds__(INFO_T) void k_info_joint_hist(const float* __restr
     const bool valid = l < c1;                               // (lane 0 always is)
     const unsigned r = valid ? (rows ? (unsigned)rows[l] : (unsigned)l) : 0u;
     const float x = table[(long)r * D + d];
+    // (the count of edges stays in the kernel: as a helper shared with k_unsup_pair_hist it changed both kernels' machine code)
     int below = 0;
     for (int j = 0; j < n_bins; ++j) below += edge[j] <= x ? 1 : 0;
     const int b = min(max(below - 1, 0), n_bins - 1);
@@ -305,15 +287,7 @@ __global__ __launch_bounds__(INFO_T) void k_info_joint_hist(const float* __restr
   }
 }
 
-int padded_dim(int D) { return D <= DVAE_INFO_ROW_LANES_NARROW ? DVAE_INFO_ROW_LANES_NARROW : D <= DVAE_INFO_ROW_LANES_MID ? DVAE_INFO_ROW_LANES_MID : DVAE_INFO_ROW_LANES_WAVE; }
-
-// chunks of the S rows: ceil(S / block_rows) workgroups, at most DVAE_INFO_MAX_BLOCKS, none of them empty
-int chunks_of(long S, long block_rows, long* chunk) {
-  long nb = (S + block_rows - 1) / block_rows;
-  if (nb > DVAE_INFO_MAX_BLOCKS) nb = DVAE_INFO_MAX_BLOCKS;
-  *chunk = (S + nb - 1) / nb;
-  return (int)((S + *chunk - 1) / *chunk);
-}
+static_assert(DVAE_INFO_ROW_LANES_NARROW == 4 && DVAE_INFO_ROW_LANES_MID == 16 && DVAE_INFO_ROW_LANES_WAVE == 64, "padded_width gives the row lanes");
 
 bool sizes_ok(long N, int D, int K, long S) {
   return N > 0 && N <= 2000000000L && D > 0 && D <= 16384 && K > 0 && K <= DVAE_INFO_MAX_FACTORS && S > 0 && S <= 2000000000L;
@@ -327,13 +301,13 @@ using namespace dvae;
 extern "C" {
 
 int dvae_info_version(void) { return DVAE_INFO_VERSION; }
-const char* dvae_info_last_error(void) { return g_info_err; }
+const char* dvae_info_last_error(void) { return last_error(); }
 
 size_t dvae_info_moments_ws_floats(long N, int D, int K, long S) {
   if (S <= 0) S = N;
   if (!sizes_ok(N, D, K, S)) return 0;
   long chunk;
-  const int nb = chunks_of(S, DVAE_INFO_MOMENTS_BLOCK_ROWS, &chunk);
+  const int nb = chunks_of(S, DVAE_INFO_MOMENTS_BLOCK_ROWS, DVAE_INFO_MAX_BLOCKS, &chunk);
   return (size_t)(2 * (nb + 1) * moments_record(D, K));     // one record of doubles per chunk, and their total
 }
 
@@ -351,8 +325,8 @@ int dvae_info_moments(const float* table, const int64_t* rows, const int32_t* la
   DVAE_CHECK_ARG(sizes_ok(N, D, K, S));
   hipStream_t st = (hipStream_t)stream;
   long chunk;
-  const int nb = chunks_of(S, DVAE_INFO_MOMENTS_BLOCK_ROWS, &chunk);
-  switch (padded_dim(D)) {
+  const int nb = chunks_of(S, DVAE_INFO_MOMENTS_BLOCK_ROWS, DVAE_INFO_MAX_BLOCKS, &chunk);
+  switch (padded_width(D)) {
     case DVAE_INFO_ROW_LANES_NARROW: hipLaunchKernelGGL((k_info_moments_part<DVAE_INFO_ROW_LANES_NARROW>), dim3(nb), dim3(INFO_T), 0, st, table, rows, lat_sizes, D, K, S, chunk, ws); break;
     case DVAE_INFO_ROW_LANES_MID: hipLaunchKernelGGL((k_info_moments_part<DVAE_INFO_ROW_LANES_MID>), dim3(nb), dim3(INFO_T), 0, st, table, rows, lat_sizes, D, K, S, chunk, ws); break;
     default: hipLaunchKernelGGL((k_info_moments_part<DVAE_INFO_ROW_LANES_WAVE>), dim3(nb), dim3(INFO_T), 0, st, table, rows, lat_sizes, D, K, S, chunk, ws);
@@ -378,7 +352,7 @@ int dvae_info_joint_hist(const float* table, const int64_t* rows, const int32_t*
   hipLaunchKernelGGL(k_info_zero, dim3((unsigned)lesser((all + INFO_T - 1) / INFO_T, 1024L)), dim3(INFO_T), 0, st, counts, all);
   DVAE_CHECK_LAUNCH();
   long chunk;
-  const int nb = chunks_of(S, DVAE_INFO_HIST_BLOCK_ROWS, &chunk);
+  const int nb = chunks_of(S, DVAE_INFO_HIST_BLOCK_ROWS, DVAE_INFO_MAX_BLOCKS, &chunk);
   if (tot <= DVAE_INFO_HIST_LDS_INTS)
     hipLaunchKernelGGL((k_info_joint_hist<true>), dim3(nb, D), dim3(INFO_T), 0, st, table, rows, lat_sizes, edges, D, K, S, n_bins,
                        sum_sizes, chunk, counts);

@@ -18,22 +18,12 @@
 // reduces the rank and clears the counters.  After the fourth pass the prefix IS the rank-th smallest deviation, and the walk knows
 // how many deviations are <= it.  One more pass takes the largest deviation (integer max) and the smallest one above the prefix
 // (integer min) per group; k_irs_select_finish picks stat_hi between the two.  Integer atomics only: any order gives the same bits.
-#include <stdarg.h>
-
 #include "../../include/dvae_irs_hip.h"
 #include "common.h"
+#include "last_error.h"
+#include "table_stats.h"
 
 namespace dvae {
-
-static thread_local char g_irs_err[512] = "";
-
-// the check macros of common.h report through dvae::set_error: this library keeps its own (capi.hip's is in libdvae_hip.so)
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_irs_err, sizeof(g_irs_err), fmt, ap);
-  va_end(ap);
-}
 
 namespace {
 
@@ -45,11 +35,9 @@ namespace {
 #define IRS_AGG 4                                            // distinct keys of a wave that are added by ballot
 #define IRS_NONE 0xFFFFFFFFu
 
-template <class T>
-__host__ __device__ __forceinline__ T lesser(T a, T b) { return a < b ? a : b; }
-
 // What one workgroup needs of the layout for ITS factor number j (0: "all selected rows", j >= 1: factor j - 1); the same in every
-// thread.  ok: lat_sizes / n_groups agree with what the caller said of them (sum_sizes, total_groups, max_groups).
+// thread.  ok: lat_sizes / n_groups agree with what the caller said of them (sum_sizes, total_groups, max_groups).  (The sizes and
+// strides are formed here as in factor_info.hip's load_factors: built on one shared helper, five kernels compiled to other machine code.)
 struct Factor {
   unsigned size, stride;  // value of a row: (r / stride) % size
   int voff;               // where the factor's values start in group_of_value
@@ -98,13 +86,6 @@ __device__ __forceinline__ int group_of_row(const Factor& f, const int32_t* __re
   const int g = group_of_value[f.voff + (int)((r / f.stride) % f.size)];
   return (unsigned)g < (unsigned)f.G ? g : -1;
 }
-
-// doubles cross the fp32 workspace as two words: ws is aligned to 4 bytes and no more
-__device__ __forceinline__ void put_f64(float* p, double v) {
-  p[0] = __int_as_float(__double2loint(v));
-  p[1] = __int_as_float(__double2hiint(v));
-}
-__device__ __forceinline__ double get_f64(const float* p) { return __hiloint2double(__float_as_int(p[1]), __float_as_int(p[0])); }
 
 // ---- means -------------------------------------------------------------------------------------------------------------------------
 // record of one chunk: [total_groups * D] doubles (two words each), then [total_groups] int32 counts
@@ -406,14 +387,6 @@ __global__ __launch_bounds__(IRS_T) void k_irs_select_finish(const int32_t* __re
   dev_max[pair] = __uint_as_float(mx);
 }
 
-// chunks of the S rows: ceil(S / block_rows) workgroups, at most DVAE_IRS_MAX_BLOCKS, none of them empty
-int chunks_of(long S, long block_rows, long* chunk) {
-  long nb = (S + block_rows - 1) / block_rows;
-  if (nb > DVAE_IRS_MAX_BLOCKS) nb = DVAE_IRS_MAX_BLOCKS;
-  *chunk = (S + nb - 1) / nb;
-  return (int)((S + *chunk - 1) / *chunk);
-}
-
 bool sizes_ok(long N, int D, int K, long S, int total_groups) {
   return N > 0 && N <= 2147483647L && D > 0 && D <= 65535 && K > 0 && K <= DVAE_IRS_MAX_FACTORS && S > 0 && S <= 2147483647L &&
          total_groups >= 1 + K && total_groups <= 1 + K * DVAE_IRS_MAX_GROUPS && (long)total_groups * D <= DVAE_IRS_MAX_PAIRS;
@@ -427,13 +400,13 @@ using namespace dvae;
 extern "C" {
 
 int dvae_irs_version(void) { return DVAE_IRS_VERSION; }
-const char* dvae_irs_last_error(void) { return g_irs_err; }
+const char* dvae_irs_last_error(void) { return last_error(); }
 
 size_t dvae_irs_group_means_ws_floats(long N, int D, int K, long S, int total_groups) {
   if (S <= 0) S = N;
   if (!sizes_ok(N, D, K, S, total_groups)) return 0;
   long chunk;
-  const int nb = chunks_of(S, DVAE_IRS_MEANS_BLOCK_ROWS, &chunk);
+  const int nb = chunks_of(S, DVAE_IRS_MEANS_BLOCK_ROWS, DVAE_IRS_MAX_BLOCKS, &chunk);
   return (size_t)(nb * means_record(D, total_groups));
 }
 
@@ -454,7 +427,7 @@ int dvae_irs_group_means(const float* table, const int64_t* rows, const int32_t*
   DVAE_CHECK_ARG(max_groups >= 1 && sum_sizes >= K && sum_sizes <= 2147483647L && total_groups <= 1 + (long)K * max_groups);
   hipStream_t st = (hipStream_t)stream;
   long chunk;
-  const int nb = chunks_of(S, DVAE_IRS_MEANS_BLOCK_ROWS, &chunk);
+  const int nb = chunks_of(S, DVAE_IRS_MEANS_BLOCK_ROWS, DVAE_IRS_MAX_BLOCKS, &chunk);
   hipLaunchKernelGGL(k_irs_means_part, dim3(nb, K + 1), dim3(IRS_T), 0, st, table, rows, lat_sizes, group_of_value, n_groups, D, K, S,
                      sum_sizes, total_groups, max_groups, chunk, ws);
   DVAE_CHECK_LAUNCH();
@@ -478,7 +451,7 @@ int dvae_irs_group_order_stats(const float* table, const int64_t* rows, const in
   hipStream_t st = (hipStream_t)stream;
   const long P = (long)total_groups * D;
   long chunk;
-  const int nb = chunks_of(S, DVAE_IRS_SELECT_BLOCK_ROWS, &chunk);
+  const int nb = chunks_of(S, DVAE_IRS_SELECT_BLOCK_ROWS, DVAE_IRS_MAX_BLOCKS, &chunk);
   const int slices = (max_groups + IRS_LG - 1) / IRS_LG;
   const dim3 grid(nb, D, (K + 1) * slices);
   hipLaunchKernelGGL(k_irs_select_init, dim3((unsigned)lesser((P * 256 + IRS_T - 1) / IRS_T, 4096L)), dim3(IRS_T), 0, st, rank, D, P, ws);

@@ -14,22 +14,12 @@
 //
 // The variance is taken around the group's mean -- mean first, squared deviations second, the rows re-read from cache --
 // and both passes work on x - x_0 (the group's first row): the sums then carry the spread of the group, not its offset.
-#include <stdarg.h>
-
 #include "../../include/dvae_score_hip.h"
 #include "common.h"
+#include "last_error.h"
+#include "table_stats.h"
 
 namespace dvae {
-
-static thread_local char g_score_err[512] = "";
-
-// the check macros of common.h report through dvae::set_error: this library keeps its own (capi.hip's is in libdvae_hip.so)
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_score_err, sizeof(g_score_err), fmt, ap);
-  va_end(ap);
-}
 
 namespace {
 
@@ -163,8 +153,6 @@ __global__ __launch_bounds__(256) void k_vote_count_wide(const int32_t* __restri
   votes[i] = c;
 }
 
-int padded_dim(int D) { return D <= 4 ? 4 : D <= 16 ? 16 : 64; }
-
 #define SCORE_LAUNCH(kern, DP, ...)                                                                                       \
   do {                                                                                                                    \
     if (L <= DVAE_SCORE_WAVE_MAX_L)                                                                                       \
@@ -175,7 +163,7 @@ int padded_dim(int D) { return D <= 4 ? 4 : D <= 16 ? 16 : 64; }
   } while (0)
 
 #define SCORE_DISPATCH(kern, ...)                                \
-  switch (padded_dim(D)) {                                       \
+  switch (padded_width(D)) {                                       \
     case 4: SCORE_LAUNCH(kern, 4, __VA_ARGS__); break;           \
     case 16: SCORE_LAUNCH(kern, 16, __VA_ARGS__); break;         \
     default: SCORE_LAUNCH(kern, 64, __VA_ARGS__);                \
@@ -189,7 +177,7 @@ using namespace dvae;
 extern "C" {
 
 int dvae_score_version(void) { return DVAE_SCORE_VERSION; }
-const char* dvae_score_last_error(void) { return g_score_err; }
+const char* dvae_score_last_error(void) { return last_error(); }
 
 size_t dvae_score_group_var_ws_floats(long N, int D, long V, long L) {
   (void)N; (void)D; (void)V; (void)L;

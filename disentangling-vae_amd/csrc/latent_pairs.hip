@@ -21,22 +21,12 @@
 // number once instead; every other pair takes plain LDS integer atomics, which a live latent spreads over its bins.  The
 // workgroup adds its non-zero counters to `counts` at its end (integer adds: any order gives the same counts);
 // k_unsup_zero clears `counts` first.
-#include <stdarg.h>
-
 #include "../../include/dvae_unsup_hip.h"
 #include "common.h"
+#include "last_error.h"
+#include "table_stats.h"
 
 namespace dvae {
-
-static thread_local char g_unsup_err[512] = "";
-
-// the check macros of common.h report through dvae::set_error: this library keeps its own (capi.hip's is in libdvae_hip.so)
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_unsup_err, sizeof(g_unsup_err), fmt, ap);
-  va_end(ap);
-}
 
 namespace {
 
@@ -50,16 +40,6 @@ namespace {
 static_assert(UNSUP_SUMS * UNSUP_T >= UNSUP_DMAX * (UNSUP_DMAX + 3) / 2, "every sum needs an owner");
 static_assert(DVAE_UNSUP_MAX_BINS <= 256, "a bin is staged as one byte");
 static_assert(DVAE_UNSUP_HIST_LDS_INTS >= DVAE_UNSUP_MAX_BINS * DVAE_UNSUP_MAX_BINS, "one pair of the most bins fits a tile");
-
-template <class T>
-__host__ __device__ __forceinline__ T lesser(T a, T b) { return a < b ? a : b; }
-
-// doubles cross the fp32 workspace as two words: ws is aligned to 4 bytes and no more
-__device__ __forceinline__ void put_f64(float* p, double v) {
-  p[0] = __int_as_float(__double2loint(v));
-  p[1] = __int_as_float(__double2hiint(v));
-}
-__device__ __forceinline__ double get_f64(const float* p) { return __hiloint2double(__float_as_int(p[1]), __float_as_int(p[0])); }
 
 // ---- moments --------------------------------------------------------------------------------------------------------------------
 // sum i <-> (a, b), a <= b <= D, in lexicographic order: line a holds D + 1 - a of them
@@ -188,7 +168,7 @@ __global__ __launch_bounds__(UNSUP_T) void k_unsup_moments_finish(const float* _
 
 // ---- histograms -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(UNSUP_T) void k_unsup_zero(int32_t* __restrict__ p, long n) {
-  for (long i = blockIdx.x * (long)UNSUP_T + threadIdx.x; i < n; i += (long)gridDim.x * UNSUP_T) p[i] = 0;
+  zero_i32<UNSUP_T>(p, n);
 }
 
 // pair p <-> (d, e), d < e < D, in lexicographic order: line d holds D - 1 - d of them
@@ -249,6 +229,7 @@ __global__ __launch_bounds__(UNSUP_T) void k_unsup_pair_hist(const float* __rest
       const long row = rows ? (long)rows[base + r] : base + r;
       const float x = table[row * D + lat_of[s]];
       const float* ed = edge + s * n_bins;
+      // (the count of edges stays in the kernel: as a helper shared with k_info_joint_hist it changed both kernels' machine code)
       int below = 0;
       for (int j = 0; j < n_bins; ++j) below += ed[j] <= x ? 1 : 0;
       binb[r * Ls + s] = (unsigned char)min(max(below - 1, 0), n_bins - 1);
@@ -283,14 +264,6 @@ __global__ __launch_bounds__(UNSUP_T) void k_unsup_pair_hist(const float* __rest
   }
 }
 
-// chunks of the S rows: ceil(S / block_rows) workgroups, at most DVAE_UNSUP_MAX_BLOCKS, none of them empty
-int chunks_of(long S, long block_rows, long* chunk) {
-  long nb = (S + block_rows - 1) / block_rows;
-  if (nb > DVAE_UNSUP_MAX_BLOCKS) nb = DVAE_UNSUP_MAX_BLOCKS;
-  *chunk = (S + nb - 1) / nb;
-  return (int)((S + *chunk - 1) / *chunk);
-}
-
 bool sizes_ok(long N, int D, long S) {
   return N > 0 && N <= 2147483647L && D > 0 && D <= DVAE_UNSUP_MAX_D && S > 0 && S <= 2147483647L;
 }
@@ -303,13 +276,13 @@ using namespace dvae;
 extern "C" {
 
 int dvae_unsup_version(void) { return DVAE_UNSUP_VERSION; }
-const char* dvae_unsup_last_error(void) { return g_unsup_err; }
+const char* dvae_unsup_last_error(void) { return last_error(); }
 
 size_t dvae_unsup_moments_ws_floats(long N, int D, long S) {
   if (S <= 0) S = N;
   if (!sizes_ok(N, D, S)) return 0;
   long chunk;
-  const int nb = chunks_of(S, DVAE_UNSUP_MOMENTS_BLOCK_ROWS, &chunk);
+  const int nb = chunks_of(S, DVAE_UNSUP_MOMENTS_BLOCK_ROWS, DVAE_UNSUP_MAX_BLOCKS, &chunk);
   return (size_t)(nb * moments_record(D));                   // one record per chunk
 }
 
@@ -326,7 +299,7 @@ int dvae_unsup_moments(const float* table, const int64_t* rows, long N, int D, l
   DVAE_CHECK_ARG(sizes_ok(N, D, S));
   hipStream_t st = (hipStream_t)stream;
   long chunk;
-  const int nb = chunks_of(S, DVAE_UNSUP_MOMENTS_BLOCK_ROWS, &chunk);
+  const int nb = chunks_of(S, DVAE_UNSUP_MOMENTS_BLOCK_ROWS, DVAE_UNSUP_MAX_BLOCKS, &chunk);
   hipLaunchKernelGGL(k_unsup_moments_part, dim3(nb), dim3(UNSUP_T), 0, st, table, rows, D, S, chunk, ws);
   DVAE_CHECK_LAUNCH();
   const int waves = UNSUP_T / 64;
@@ -354,7 +327,7 @@ int dvae_unsup_pair_hist(const float* table, const int64_t* rows, const float* e
   hipLaunchKernelGGL(k_unsup_zero, dim3((unsigned)lesser((all + UNSUP_T - 1) / UNSUP_T, 1024L)), dim3(UNSUP_T), 0, st, counts, all);
   DVAE_CHECK_LAUNCH();
   long chunk;
-  const int nb = chunks_of(S, DVAE_UNSUP_HIST_BLOCK_ROWS, &chunk);
+  const int nb = chunks_of(S, DVAE_UNSUP_HIST_BLOCK_ROWS, DVAE_UNSUP_MAX_BLOCKS, &chunk);
   hipLaunchKernelGGL(k_unsup_pair_hist, dim3(nb, (P + tile_pairs - 1) / tile_pairs), dim3(UNSUP_T), 0, st, table, rows, edges, D, S,
                      n_bins, chunk, P, tile_pairs, counts);
   DVAE_CHECK_LAUNCH();

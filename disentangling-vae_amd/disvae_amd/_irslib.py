@@ -10,7 +10,7 @@ a missing shared object or symbol fails loudly.  Calls go straight to the librar
 import ctypes
 import os
 
-from ._lib import DvaeHipError
+from ._cabi import Binding
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DVAE_IRS_HIP_LIB", os.path.join(_HERE, "..", "lib", "libdvae_irs_hip.so"))
@@ -42,30 +42,14 @@ SIGNATURES = {
 _RESTYPE = {"dvae_irs_last_error": ctypes.c_char_p, "dvae_irs_group_means_ws_floats": ctypes.c_size_t,
             "dvae_irs_group_order_stats_ws_floats": ctypes.c_size_t}
 
-_lib = None
+_binding = Binding(LIB_PATH, SIGNATURES, _RESTYPE, "dvae_irs_last_error", "interventional-robustness")
 
 
 def lib():
     """Load (once) and return the ctypes handle; raises if the library is absent."""
-    global _lib
-    if _lib is None:
-        path = os.path.abspath(LIB_PATH)
-        if not os.path.exists(path):
-            raise DvaeHipError(
-                "libdvae_irs_hip.so not found at %s -- build it with `python disentangling-vae_amd/build.py` "
-                "(there is no CPU / PyTorch fallback for the interventional-robustness kernels)" % path)
-        h = ctypes.CDLL(path)
-        for name, argtypes in SIGNATURES.items():
-            fn = getattr(h, name)  # AttributeError if the symbol is missing: fail loudly
-            fn.argtypes = argtypes
-            fn.restype = _RESTYPE.get(name, ctypes.c_int)
-        _lib = h
-    return _lib
+    return _binding.lib()
 
 
 def call(name, *args):
     """Call an int-returning entry point, raise on a non-zero status."""
-    h = lib()
-    rc = getattr(h, name)(*args)
-    if rc != 0:
-        raise DvaeHipError("%s failed (%d): %s" % (name, rc, h.dvae_irs_last_error().decode()))
+    _binding.call(lib(), name, *args)      # lib through the module: a test that replaces it intercepts this load too

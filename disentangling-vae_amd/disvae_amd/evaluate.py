@@ -657,6 +657,55 @@ def factor_scores_from_table(mean, lat_sizes, n_train=10000, n_eval=5000, batch_
                     "labels_eval": labels["eval"], "classes": classes, "W": W, "b": b}
 
 
+# ---------------------------------------------------------------------- shared by the scores on a table of means
+def _table_shape(mean):
+    if mean.dim() != 2:
+        raise ValueError("mean must be an [N, D] table, got shape %s" % (tuple(mean.shape),))
+    return int(mean.shape[0]), int(mean.shape[1])
+
+
+def _checked_rows(rows, n):
+    """An injected selection -> int64 [S], S >= 1, every row number in [0, n): the kernels do not check them."""
+    rows = torch.as_tensor(rows).to(torch.int64).reshape(-1)
+    if rows.numel() < 1 or not (0 <= int(rows.min()) and int(rows.max()) < n):
+        raise ValueError("rows must hold one row number or more, each in [0, %d)" % n)
+    return rows
+
+
+def _select_rows(mean, rows, n_samples, seed, caller, kernels):
+    """What the *_from_table functions do once their own arguments are checked, in this order: ``rows`` is validated, the table
+    must be finite, then on the GPU.  -> (table fp32 contiguous, rows int64 on the device or None for every row, S, device);
+    rows=None and n_samples given: randperm(N)[:n_samples] from a private generator seeded with ``seed``."""
+    n = int(mean.shape[0])
+    if rows is not None:
+        rows = _checked_rows(rows, n)
+    if not bool(torch.isfinite(mean).all()):
+        raise ValueError("the table of means holds a NaN or an infinity")
+    if not mean.is_cuda:
+        raise _lib.DvaeHipError("%s needs the table on the GPU (there is no CPU / PyTorch fallback for the %s kernels)" % (caller, kernels))
+    dev = mean.device
+    table = mean.detach().to(torch.float32).contiguous()
+    if rows is not None:
+        rows = rows.to(dev).contiguous()
+    elif n_samples is not None:
+        gen = torch.Generator(device=dev).manual_seed(int(seed))
+        rows = torch.randperm(n, generator=gen, device=dev)[:int(n_samples)].contiguous()
+    return table, rows, n if rows is None else int(rows.numel()), dev
+
+
+def mutual_information_from_counts(block):
+    """fp64 [B, R, C] integer-valued joint counts of B tables over the same S rows -> mutual information [B] in nats:
+    sum over the nonzero cells of P log(P / (P_row P_col)), P = counts / S (sklearn's mutual_info_score)."""
+    S = block[0].sum()
+    row, col = block.sum(axis=2, keepdims=True), block.sum(axis=1, keepdims=True)
+    # P / (P_row P_col) = c S / (row col) from the integer counts: both products are exact in fp64, so a cell of an independent
+    # table (a constant or collapsed latent: row = S) contributes log(1) = 0 exactly and modularity's "t = 0" sees the number 0
+    nz = block > 0
+    term = np.zeros_like(block)
+    term[nz] = block[nz] / S * np.log((block * S)[nz] / (row * col)[nz])
+    return term.sum(axis=(1, 2))
+
+
 # ---------------------------------------------------------------------- discretised MIG / modularity / SAP on a table of means
 def _check_information_sizes(n, lat_sizes, n_bins, n_samples):
     if len(lat_sizes) < 1 or min(lat_sizes) < 1:
@@ -702,15 +751,8 @@ def information_scores_from_statistics(counts, lat_sizes, n_bins, col_var, facto
     for k, size in enumerate(lat_sizes):
         block = counts[:, start:start + n_bins * size].reshape(D, n_bins, size).astype(np.float64)
         start += n_bins * size
-        S = block[0].sum()
-        row, col = block.sum(axis=2, keepdims=True), block.sum(axis=1, keepdims=True)
-        # P / (P_row P_col) = c S / (row col) from the integer counts: both products are exact in fp64, so a cell of an independent
-        # table (a constant latent: row = S) contributes log(1) = 0 exactly and modularity's "t = 0" sees the number 0
-        nz = block > 0
-        term = np.zeros_like(block)
-        term[nz] = block[nz] / S * np.log((block * S)[nz] / (row * col)[nz])
-        mi[:, k] = term.sum(axis=(1, 2))
-        pv = col[0, 0] / S
+        mi[:, k] = mutual_information_from_counts(block)
+        pv = block[0].sum(axis=0) / block[0].sum()                       # the factor's values among the selected rows: any d
         H[k] = -(pv[pv > 0] * np.log(pv[pv > 0])).sum()
     if not (H > 0).all():
         raise ValueError("factor(s) %s take one value among the selected rows: no entropy to divide the MIG by"
@@ -747,31 +789,13 @@ def information_scores_from_table(mean, lat_sizes, n_bins=20, n_samples=None, se
     "n_bins"}: Python and numpy values."""
     lat_sizes = [int(k) for k in lat_sizes]
     K, n_bins = len(lat_sizes), int(n_bins)
-    if mean.dim() != 2:
-        raise ValueError("mean must be an [N, D] table, got shape %s" % (tuple(mean.shape),))
-    n, dim = int(mean.shape[0]), int(mean.shape[1])
+    n, dim = _table_shape(mean)
     _check_information_sizes(n, lat_sizes, n_bins, None if rows is not None else n_samples)
     if n != int(np.prod(lat_sizes)):
         raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (n, lat_sizes))
     if dim < 1:
         raise ValueError("mean must have one latent dimension or more")
-    if rows is not None:
-        rows = torch.as_tensor(rows).to(torch.int64).reshape(-1)
-        if rows.numel() < 1 or not (0 <= int(rows.min()) and int(rows.max()) < n):
-            raise ValueError("rows must hold one row number or more, each in [0, %d)" % n)     # (the kernels do not check them)
-    if not bool(torch.isfinite(mean).all()):
-        raise ValueError("the table of means holds a NaN or an infinity")
-    if not mean.is_cuda:
-        raise _lib.DvaeHipError("information_scores_from_table needs the table on the GPU (there is no CPU / PyTorch fallback "
-                                "for the information-score kernels)")
-    dev = mean.device
-    table = mean.detach().to(torch.float32).contiguous()
-    if rows is not None:
-        rows = rows.to(dev).contiguous()
-    elif n_samples is not None:
-        gen = torch.Generator(device=dev).manual_seed(int(seed))
-        rows = torch.randperm(n, generator=gen, device=dev)[:int(n_samples)].contiguous()
-    S = n if rows is None else int(rows.numel())
+    table, rows, S, dev = _select_rows(mean, rows, n_samples, seed, "information_scores_from_table", "information-score")
     I = _infolib.lib()
     st = _stream()
     sizes_dev = torch.tensor(lat_sizes, dtype=torch.int32, device=dev)
@@ -895,9 +919,7 @@ def irs_from_table(mean, lat_sizes, diff_quantile=0.99, factor_bins=20, n_sample
     irs_from_statistics plus {"n_groups", "n_samples", "diff_quantile", "factor_bins"}: Python and numpy values."""
     lat_sizes = [int(k) for k in lat_sizes]
     K = len(lat_sizes)
-    if mean.dim() != 2:
-        raise ValueError("mean must be an [N, D] table, got shape %s" % (tuple(mean.shape),))
-    n, dim = int(mean.shape[0]), int(mean.shape[1])
+    n, dim = _table_shape(mean)
     _check_irs_arguments(n, lat_sizes, diff_quantile, factor_bins, None if rows is not None else n_samples)
     if n != int(np.prod(lat_sizes)):
         raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (n, lat_sizes))
@@ -907,23 +929,7 @@ def irs_from_table(mean, lat_sizes, diff_quantile=0.99, factor_bins=20, n_sample
     total = 1 + sum(n_groups)
     if total * dim > _irslib.MAX_PAIRS:
         raise ValueError("%d groups x %d latents: the kernels take at most %d pairs" % (total, dim, _irslib.MAX_PAIRS))
-    if rows is not None:
-        rows = torch.as_tensor(rows).to(torch.int64).reshape(-1)
-        if rows.numel() < 1 or not (0 <= int(rows.min()) and int(rows.max()) < n):
-            raise ValueError("rows must hold one row number or more, each in [0, %d)" % n)     # (the kernels do not check them)
-    if not bool(torch.isfinite(mean).all()):
-        raise ValueError("the table of means holds a NaN or an infinity")
-    if not mean.is_cuda:
-        raise _lib.DvaeHipError("irs_from_table needs the table on the GPU (there is no CPU / PyTorch fallback for the "
-                                "interventional-robustness kernels)")
-    dev = mean.device
-    table = mean.detach().to(torch.float32).contiguous()
-    if rows is not None:
-        rows = rows.to(dev).contiguous()
-    elif n_samples is not None:
-        gen = torch.Generator(device=dev).manual_seed(int(seed))
-        rows = torch.randperm(n, generator=gen, device=dev)[:int(n_samples)].contiguous()
-    S = n if rows is None else int(rows.numel())
+    table, rows, S, dev = _select_rows(mean, rows, n_samples, seed, "irs_from_table", "interventional-robustness")
     R = _irslib.lib()
     st = _stream()
     sizes_dev = torch.tensor(lat_sizes, dtype=torch.int32, device=dev)
@@ -980,8 +986,8 @@ def unsupervised_scores_from_statistics(col_min, col_max, cov, counts, n_bins, a
     gaussian_wasserstein_correlation_norm = that / sum v; both 0.0 without a live column (eigvalsh leaves an ABSOLUTE error of about
     2^-53 max(v)^2 in every eigenvalue, so a live column whose variance is below 1e-4 of the largest costs the score up to
     1e-8 sum v: harmless for reading it, and the reason the tests keep their near-collapsed columns above that);
-    mutual_information [D, D]: nats between the discretised columns d and e from the integer counts, as
-    information_scores_from_statistics forms it (c S / (row col), zero cells skipped), symmetric, zero diagonal;
+    mutual_information [D, D]: nats between the discretised columns d and e from the integer counts
+    (mutual_information_from_counts), symmetric, zero diagonal;
     mutual_info_score = sum of it / (D^2 - D), over ALL D columns as disentanglement_lib does (0.0 for D = 1);
     active_units = #{d : cov[d, d] > active_threshold} (Burda et al. 2016);  variances = diag cov."""
     col_min, col_max = np.asarray(col_min), np.asarray(col_max)
@@ -1004,15 +1010,8 @@ def unsupervised_scores_from_statistics(col_min, col_max, cov, counts, n_bins, a
     P = D * (D - 1) // 2
     if P:
         block = np.asarray(counts).astype(np.int64).reshape(P, n_bins, n_bins).astype(np.float64)
-        S = block[0].sum()
-        row, col = block.sum(axis=2, keepdims=True), block.sum(axis=1, keepdims=True)
-        # P / (P_row P_col) = c S / (row col) from the integer counts: both products are exact in fp64, so a pair with a collapsed
-        # latent (row = S) gives log(1) = 0 exactly
-        nz = block > 0
-        term = np.zeros_like(block)
-        term[nz] = block[nz] / S * np.log((block * S)[nz] / (row * col)[nz])
         upper = np.triu_indices(D, 1)                                    # (d, e), d < e, in lexicographic order: the pairs' own
-        mi[upper] = term.sum(axis=(1, 2))
+        mi[upper] = mutual_information_from_counts(block)
         mi = mi + mi.T
     return {"gaussian_total_correlation": tc, "gaussian_wasserstein_correlation": wass,
             "gaussian_wasserstein_correlation_norm": wass_norm, "mutual_info_score": float(mi.sum() / (D * D - D)) if D > 1 else 0.0,
@@ -1033,27 +1032,9 @@ def unsupervised_scores_from_table(mean, n_bins=20, n_samples=None, seed=0, rows
     dvae_unsup_pair_hist (not for D = 1), ONE copy of the counts, the scores in fp64 on the host.  Returns the dict of
     unsupervised_scores_from_statistics plus {"n_samples", "n_bins"}: Python and numpy values."""
     n_bins = int(n_bins)
-    if mean.dim() != 2:
-        raise ValueError("mean must be an [N, D] table, got shape %s" % (tuple(mean.shape),))
-    n, dim = int(mean.shape[0]), int(mean.shape[1])
+    n, dim = _table_shape(mean)
     _check_unsupervised_arguments(n, dim, n_bins, None if rows is not None else n_samples)
-    if rows is not None:
-        rows = torch.as_tensor(rows).to(torch.int64).reshape(-1)
-        if rows.numel() < 1 or not (0 <= int(rows.min()) and int(rows.max()) < n):
-            raise ValueError("rows must hold one row number or more, each in [0, %d)" % n)     # (the kernels do not check them)
-    if not bool(torch.isfinite(mean).all()):
-        raise ValueError("the table of means holds a NaN or an infinity")
-    if not mean.is_cuda:
-        raise _lib.DvaeHipError("unsupervised_scores_from_table needs the table on the GPU (there is no CPU / PyTorch fallback "
-                                "for the label-free score kernels)")
-    dev = mean.device
-    table = mean.detach().to(torch.float32).contiguous()
-    if rows is not None:
-        rows = rows.to(dev).contiguous()
-    elif n_samples is not None:
-        gen = torch.Generator(device=dev).manual_seed(int(seed))
-        rows = torch.randperm(n, generator=gen, device=dev)[:int(n_samples)].contiguous()
-    S = n if rows is None else int(rows.numel())
+    table, rows, S, dev = _select_rows(mean, rows, n_samples, seed, "unsupervised_scores_from_table", "label-free score")
     U = _unsuplib.lib()
     st = _stream()
     ws = torch.empty(max(U.dvae_unsup_moments_ws_floats(n, dim, S), U.dvae_unsup_pair_hist_ws_floats(n, dim, S, n_bins), 1),

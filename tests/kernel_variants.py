@@ -81,9 +81,9 @@ VARIANTS = [
     _v("k_down32<4, false>", "dvae_conv4s2_fwd, dvae_conv32_down", "Hs == 4, no mask (output NHWC or NCHW)", "conv_mfma.hip:396", V + "test_conv32_at_the_persistent_grid_switch[1024-4]"),
     _v("k_down32<4, true>", "dvae_convT4s2_dgrad, dvae_conv32_down", "Hs == 4, mask", "conv_mfma.hip:395", V + "test_conv32_at_the_persistent_grid_switch[1025-4]"),
     _v("k_wgrad32<16>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "Hs == 16 with the small side NCHW or DVAE_WGRAD_WS=0", "conv_mfma.hip:433", None,
-       "run_wgrad (capi.hip:54) passes small_nchw = 1 for Hs == 4 only, and " + _DEBUG_ONLY % "DVAE_WGRAD_WS"),
+       "run_wgrad (capi.hip:45) passes small_nchw = 1 for Hs == 4 only, and " + _DEBUG_ONLY % "DVAE_WGRAD_WS"),
     _v("k_wgrad32<8>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "Hs == 8 with the small side NCHW or DVAE_WGRAD_WS=0", "conv_mfma.hip:433", None,
-       "run_wgrad (capi.hip:54) passes small_nchw = 1 for Hs == 4 only, and " + _DEBUG_ONLY % "DVAE_WGRAD_WS"),
+       "run_wgrad (capi.hip:45) passes small_nchw = 1 for Hs == 4 only, and " + _DEBUG_ONLY % "DVAE_WGRAD_WS"),
     _v("k_wgrad32<4>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "Hs == 4 (small side NHWC or NCHW)", "conv_mfma.hip:433", V + "test_wgrad32_at_the_reduction_form_switch[767-4-True-False]"),
     _v("k_wgrad32_reduce<false>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "32 <-> 32 channels, N < WGR_LEAN_MIN_IMAGES = 768", "conv_mfma.hip:375", V + "test_wgrad32_at_the_reduction_form_switch[767-8-False-False]"),
     _v("k_wgrad32_reduce<true>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "32 <-> 32 channels, N >= 768", "conv_mfma.hip:373", V + "test_wgrad32_at_the_reduction_form_switch[768-8-False-False]"),

@@ -3,9 +3,9 @@
 
     python tools/isa_identity.py PARENT_TREE [--out profiles/NAME.txt] [--work DIR] [--jobs N] [--builds shipped,debug]
 
-PARENT_TREE is a checkout of the commit to compare against (e.g. `git worktree add /tmp/parent HEAD~1`).  Every file of
-build.py's SOURCES, EVAL_SOURCES, SCORE_SOURCES and INFO_SOURCES (all four libraries) is compiled to device-only assembly in both trees with the project's flags, once plain and once with
--DDVAE_DEBUG_SWITCHES.  Comments and assembler directives are stripped; what is left (labels + instructions) is compared per
+PARENT_TREE is a checkout of the commit to compare against (e.g. `git worktree add /tmp/parent HEAD~1`).  Every source of
+every target in build.py's TARGETS table is compiled to device-only assembly in both trees with the project's flags, once
+plain and once with -DDVAE_DEBUG_SWITCHES.  Comments and assembler directives are stripped; what is left (labels + instructions) is compared per
 function, together with each kernel's .vgpr_count / .sgpr_count / .private_segment_fixed_size / .group_segment_fixed_size
 and the "; Occupancy:" comment.  Prints one line per file and build, and for every kernel that differs the resource lines
 of both sides.  Exit status 1 when anything differs.
@@ -24,7 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, PKG))
 import build as dvae_build  # noqa: E402
 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--offload-device-only", "-S"]
-ALL_SOURCES = dvae_build.SOURCES + dvae_build.EVAL_SOURCES + dvae_build.SCORE_SOURCES + dvae_build.INFO_SOURCES
+ALL_SOURCES = dvae_build.ALL_SOURCES
 META = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
