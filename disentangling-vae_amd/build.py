@@ -7,6 +7,10 @@ include/.  Target "" is libdvae_hip.so, the training library; every other target
 nothing of one target is linked into another.  All targets share FLAGS and the up-to-date
 logic, each under a stamp of its own (build/flags.txt, build/flags_NAME.txt).  The module's X_LIB / X_SOURCES /
 X_HEADERS names (LIB / SOURCES / HEADERS for the training library) are derived from the table.
+EXTRA_TARGETS is a second table of the same (name, sources, header) rows, built right after TARGETS through the same
+_target() / _build_target() path and given the same derived names (UDR_LIB / UDR_SOURCES / UDR_HEADERS).  The two tables are
+ONE list in spirit: tests/test_score_plumbing_host.py pins TARGETS (its length, its names, ALL_SOURCES, tools/isa_identity.py)
+and existing tests do not change with a feature, so a library added since stands here; the tables merge when that pin can move.
 The libraries land in disentangling-vae_amd/lib/ (git-ignored build products).  Objects are rebuilt only
 when a source / header is newer or the flags changed.
 --debug (or DVAE_BUILD_DEBUG=1) adds -DDVAE_DEBUG_SWITCHES: the A/B / timing-ablation environment
@@ -33,6 +37,10 @@ TARGETS = [
     ("irs", ["factor_irs"], "dvae_irs_hip.h"),             # interventional robustness score
     ("unsup", ["latent_pairs"], "dvae_unsup_hip.h"),       # Gaussian total correlation, Wasserstein correlation, latent-latent mutual information
 ]
+# libraries added since the pin on TARGETS (module docstring): the same rows, the same build path
+EXTRA_TARGETS = [
+    ("udr", ["latent_ranks"], "dvae_udr_hip.h"),           # unsupervised disentanglement ranking: tie-averaged ranks, KL per dimension
+]
 HEADERS = sorted(glob.glob(os.path.join(SRC, "*.h"))) + [os.path.join(HERE, "..", "include", "dvae_hip.h")]
 
 
@@ -43,7 +51,7 @@ def _target(name, sources, header):
     return os.path.join(HERE, "lib", "libdvae%s_hip.so" % infix), sources, headers, os.path.join(OBJ, "flags%s.txt" % infix)
 
 
-for _row in TARGETS:        # LIB / SOURCES / HEADERS of the training library, EVAL_LIB / EVAL_SOURCES / EVAL_HEADERS, ... of the others
+for _row in TARGETS + EXTRA_TARGETS:        # LIB / SOURCES / HEADERS of the training library, EVAL_LIB / EVAL_SOURCES / EVAL_HEADERS, ... of the others
     _prefix = _row[0].upper() + "_" if _row[0] else ""
     globals()[_prefix + "LIB"], globals()[_prefix + "SOURCES"], globals()[_prefix + "HEADERS"], _ = _target(*_row)
 ALL_SOURCES = [s for _, sources, _ in TARGETS for s in sources]
@@ -84,14 +92,14 @@ def _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose):
 
 
 def build(force=False, verbose=True, debug=None):
-    """Build every target of TARGETS; returns the path of libdvae_hip.so."""
+    """Build every target of TARGETS, then of EXTRA_TARGETS; returns the path of libdvae_hip.so."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if debug is None:
         debug = os.environ.get("DVAE_BUILD_DEBUG", "0") == "1"
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
     flags = FLAGS + (["-DDVAE_DEBUG_SWITCHES"] if debug else [])
-    for name, sources, header in TARGETS:
+    for name, sources, header in TARGETS + EXTRA_TARGETS:
         lib, sources, headers, stamp = _target(name, sources + (DEBUG_SOURCES if debug and not name else []), header)
         _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose)
     return LIB

@@ -36,6 +36,12 @@
   covariance in fp64 and the D (D - 1) / 2 pair histograms as two HIP passes on the table where it lies
   (libdvae_unsup_hip.so); the statistics cross to the host, where the scores are combined in fp64.
   Written to unsupervised_scores.log by ``__call__(is_unsupervised=True)``.
+* Unsupervised disentanglement ranking (Duan et al. 2020; disentanglement_lib's udr.py), new (``compute_udr`` /
+  ``udr_from_tables``): model selection WITHOUT labels -- a model of a sweep scores high when its informative latents match, one
+  to one, those of the other models.  The KL divergence per dimension and the tie-averaged ranks of every column of every
+  model's table as HIP launches (libdvae_udr_hip.so: a segmented radix sort), the correlation of the rank tables by
+  dvae_unsup_moments; the [D, D] correlation blocks cross to the host, where the Lasso form is fitted and the scores are
+  combined in fp64.  Written to udr.log by ``__call__(udr_models=[...])``.
 """
 import logging
 import math
@@ -46,7 +52,7 @@ from timeit import default_timer
 import numpy as np
 import torch
 
-from . import _evallib, _infolib, _irslib, _lib, _scorelib, _unsuplib
+from . import _evallib, _infolib, _irslib, _lib, _scorelib, _udrlib, _unsuplib
 from ._lib import call, ptr
 from .engine import _stream
 from .likelihood import _ScorePasses, check_rec_dist, log_likelihood
@@ -62,6 +68,7 @@ FACTOR_SCORES_FILE = "factor_scores.log"
 INFORMATION_SCORES_FILE = "information_scores.log"
 IRS_FILE = "irs.log"
 UNSUPERVISED_SCORES_FILE = "unsupervised_scores.log"
+UDR_FILE = "udr.log"
 
 
 class Evaluator:
@@ -78,13 +85,15 @@ class Evaluator:
 
     def __call__(self, data_loader, is_metrics=False, is_losses=True, is_log_likelihood=False, n_samples=128,
                  is_decomposition=False, n_samples_decomposition=10000, is_scores=False, is_information=False,
-                 is_irs=False, is_unsupervised=False):
+                 is_irs=False, is_unsupervised=False, udr_models=None):
         """evaluate.py:60-95.  is_log_likelihood: also write compute_log_likelihood(data_loader, n_samples) to
         log_likelihood.log; is_decomposition: also write compute_elbo_decomposition(data_loader, n_samples_decomposition) to
         elbo_decomposition.log; is_scores: also write compute_factor_scores(data_loader) to factor_scores.log; is_information: also
         write compute_information_scores(data_loader), without its [D, K] matrices, to information_scores.log; is_irs: also write compute_irs(data_loader),
         its arrays as lists, to irs.log; is_unsupervised: also write compute_unsupervised_scores(data_loader), its arrays as lists and
-        without its [D, D] matrix, to unsupervised_scores.log (the return value stays the reference's (metric, losses))."""
+        without its [D, D] matrix, to unsupervised_scores.log; udr_models (the other models of a sweep): also write
+        compute_udr(data_loader, udr_models), its arrays as lists and without raw_correlations, to udr.log (the return value stays
+        the reference's (metric, losses))."""
         start = default_timer()
         is_still_training = self.model.training
         self.model.eval()
@@ -141,6 +150,13 @@ class Evaluator:
             self.logger.info('Unsupervised scores: {}'.format(unsup))
             os.makedirs(self.save_dir, exist_ok=True)
             save_metadata(unsup, self.save_dir, filename=UNSUPERVISED_SCORES_FILE)
+        if udr_models is not None:
+            self.logger.info('Computing the unsupervised disentanglement ranking...')
+            udr = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in self.compute_udr(data_loader, udr_models).items()
+                   if k != "raw_correlations"}
+            self.logger.info('UDR: {}'.format(udr))
+            os.makedirs(self.save_dir, exist_ok=True)
+            save_metadata(udr, self.save_dir, filename=UDR_FILE)
         if is_still_training:
             self.model.train()
         self.logger.info('Finished evaluating after {:.1f} min.'.format((default_timer() - start) / 60))
@@ -354,6 +370,34 @@ class Evaluator:
             if was_training:
                 self.model.train()
         return unsupervised_scores_from_table(mean, n_bins=n_bins, n_samples=n_samples, seed=seed)
+
+    # ------------------------------------------------------------------ unsupervised disentanglement ranking
+    def compute_udr(self, dataloader, other_models, **kw):
+        """UDR of ``self.model`` (model 0) and ``other_models`` (udr_from_tables below, on the posterior means and log-variances
+        of the whole data set; ``kw`` are its keyword arguments).  The loader is walked ONCE and every batch goes through every
+        model's native encoder, so the rows of the tables line up even on a shuffling loader.  The data set needs no known factors
+        of variation; every argument that can be is checked before any device work; the train / eval mode of every model is
+        restored."""
+        models = [self.model] + list(other_models)
+        ds = getattr(dataloader, "dataset", None)
+        _check_udr_arguments(len(models), len(ds) if hasattr(ds, "__len__") else None, None, **kw)
+        was_training = [m.training for m in models]
+        chunks = [[] for _ in models]
+        try:
+            for m in models:
+                m.to(self.device).eval()
+            with torch.no_grad():
+                for x, _label in dataloader:
+                    x = x.to(self.device)
+                    for i, m in enumerate(models):
+                        chunks[i].append(m.encoder(x))
+        finally:
+            for m, training in zip(models, was_training):
+                if training:
+                    m.train()
+        means = [torch.cat([mu for mu, _ in c]) for c in chunks]
+        logvars = [torch.cat([lv for _, lv in c]) for c in chunks]
+        return udr_from_tables(means, logvars, **kw)
 
     # ------------------------------------------------------------------ MIG / AAM (evaluate.py:119-317)
     def compute_metrics(self, dataloader, sample_idx=None, n_samples=10000):
@@ -1056,4 +1100,206 @@ def unsupervised_scores_from_table(mean, n_bins=20, n_samples=None, seed=0, rows
         counts = counts_dev.cpu().numpy()                                          # ONE copy of the counts
     scores = unsupervised_scores_from_statistics(col_min, col_max, cov, counts, n_bins, active_threshold)
     scores.update(n_samples=S, n_bins=n_bins)
+    return scores
+
+
+# ---------------------------------------------------------------------- unsupervised disentanglement ranking on tables of q(z|x)
+UDR_MAX_D = _unsuplib.MAX_D // 2                                         # a pair of models is one table of dvae_unsup_moments
+UDR_CORRELATIONS = ("spearman", "lasso")
+LASSO_STOP = 1e-13                                                       # largest coefficient change of a sweep
+LASSO_MAX_SWEEPS = 100000
+
+
+def _check_udr_arguments(n_models, n, dim, correlation="spearman", n_samples=None, seed=0, rows=None, kl_threshold=0.01,
+                         filter_low_kl=True, lasso_alpha=0.1):
+    """n / dim: None where not known yet (a data set without __len__; before the encoders ran).  The keyword arguments are those of
+    udr_from_tables: an unknown one is a TypeError here, before any device work."""
+    if n_models < 2:
+        raise ValueError("UDR compares the models of a sweep: two or more are needed, got %d" % n_models)
+    if correlation not in UDR_CORRELATIONS:
+        raise ValueError("correlation must be one of %s, got %r" % (UDR_CORRELATIONS, correlation))
+    if rows is None and n_samples is not None and int(n_samples) < 1:
+        raise ValueError("n_samples must be at least 1 or None, got %r" % (n_samples,))
+    if not (math.isfinite(float(kl_threshold)) and float(kl_threshold) >= 0):
+        raise ValueError("kl_threshold must be a finite number >= 0, got %r" % (kl_threshold,))
+    if not (math.isfinite(float(lasso_alpha)) and float(lasso_alpha) >= 0):
+        raise ValueError("lasso_alpha must be a finite number >= 0, got %r" % (lasso_alpha,))
+    int(seed)
+    if n is not None:
+        if n < 1:
+            raise ValueError("the tables must hold one row or more")
+        if rows is None and n_samples is not None and int(n_samples) > n:
+            raise ValueError("n_samples must lie in [1, %d] (rows are drawn without replacement) or be None, got %r" % (n, n_samples))
+        if rows is None and (n if n_samples is None else int(n_samples)) > _udrlib.MAX_ROWS:
+            raise ValueError("UDR ranks at most %d rows: pass n_samples" % _udrlib.MAX_ROWS)
+    if dim is not None and not 1 <= dim <= UDR_MAX_D:
+        raise ValueError("the tables must have between 1 and %d latent dimensions, got %d" % (UDR_MAX_D, dim))
+
+
+def udr_pair_score(R):
+    """disentanglement_lib's relative_strength_disentanglement of a non-negative [A, B] matrix, fp64:
+    0.5 (mean_b max_a R^2 / sum_a R + mean_a max_b R^2 / sum_b R); a 0 / 0 term counts as 0; an EMPTY matrix (a model without an
+    informative latent) scores 0.0 -- a stated deviation: disentanglement_lib raises there."""
+    R = np.asarray(R, dtype=np.float64)
+    if R.ndim != 2 or R.size == 0:
+        return 0.0
+
+    def side(axis):
+        top, total = R.max(axis=axis) ** 2, R.sum(axis=axis)
+        return float(np.mean(np.divide(top, total, out=np.zeros_like(top), where=total > 0)))
+    return 0.5 * (side(0) + side(1))
+
+
+def udr_model_scores(pairwise):
+    """[M, M] pair scores -> [M]: the score of model i is the median over j != i of pairwise[j, i] (udr.py)."""
+    pairwise = np.asarray(pairwise, dtype=np.float64)
+    return np.array([np.median(np.delete(pairwise[:, i], i)) for i in range(pairwise.shape[0])])
+
+
+def lasso_from_gram(G, c, alpha, stop=LASSO_STOP, max_sweeps=LASSO_MAX_SWEEPS):
+    """argmin_w (1 / 2S) ||y - X w||^2 + alpha ||w||_1 from G = X^T X / S [A, A] and c = X^T y / S [A] by cyclic coordinate descent
+    in fp64 (sklearn.linear_model.Lasso's objective and sweep order): w_a = soft(c_a - sum_{k != a} G_ak w_k, alpha) / G_aa; a
+    coordinate with G_aa = 0 (a masked or constant latent) is skipped and stays 0; stops when the largest coefficient change of a
+    sweep is <= ``stop``."""
+    G, c = np.asarray(G, dtype=np.float64), np.asarray(c, dtype=np.float64)
+    w = np.zeros(G.shape[0])
+    live = [a for a in range(G.shape[0]) if G[a, a] > 0]
+    for _sweep in range(max_sweeps):
+        worst = 0.0
+        for a in live:
+            rho = c[a] - G[a] @ w + G[a, a] * w[a]
+            new = math.copysign(max(abs(rho) - alpha, 0.0), rho) / G[a, a]
+            worst = max(worst, abs(new - w[a]))
+            w[a] = new
+        if worst <= stop:
+            break
+    return w
+
+
+def udr_correlation_from_cov(cov, mask_a, mask_b):
+    """fp64 covariance [2D, 2D] of the concatenated tables of two models (a first) -> |Pearson correlation| block [D, D] of a's
+    columns with b's, 0 where a variance is 0 or a latent is masked out."""
+    D = cov.shape[0] // 2
+    v = np.diag(cov)
+    ok_a, ok_b = (v[:D] > 0) & mask_a, (v[D:] > 0) & mask_b
+    R = np.zeros((D, D))
+    blk = np.ix_(ok_a, ok_b)
+    R[blk] = np.abs(cov[:D, D:][blk] / np.sqrt(np.outer(v[:D][ok_a], v[D:][ok_b])))
+    return R
+
+
+def udr_lasso_from_cov(cov, mask_a, mask_b, alpha):
+    """fp64 covariance [2D, 2D] of the concatenated raw means of two models (a first) -> [D, D]: |w[a]| of latent a of model a when
+    the Lasso predicts latent b of model b.  The Pearson blocks with zero-variance and masked columns as zero rows and columns ARE
+    X^T X / S and X^T Y / S of disentanglement_lib's standardised, masked representations."""
+    D = cov.shape[0] // 2
+    v = np.diag(cov)
+    ok = np.concatenate([(v[:D] > 0) & mask_a, (v[D:] > 0) & mask_b])
+    corr = np.zeros_like(cov)
+    blk = np.ix_(ok, ok)
+    corr[blk] = cov[blk] / np.sqrt(np.outer(v[ok], v[ok]))
+    G, C = corr[:D, :D], corr[:D, D:]
+    return np.stack([np.abs(lasso_from_gram(G, C[:, b], alpha)) for b in range(D)], axis=1)
+
+
+def udr_from_statistics(kl, cov_of_pair, correlation="spearman", kl_threshold=0.01, filter_low_kl=True, lasso_alpha=0.1):
+    """The host half of udr_from_tables, fp64.  kl [M, D]: dvae_udr_kl_dims of every model; cov_of_pair(i, j), i < j: the [2D, 2D]
+    covariance (dvae_unsup_moments) of model i's table beside model j's -- the rank tables for "spearman", the raw means for
+    "lasso"."""
+    kl = np.asarray(kl, dtype=np.float64)
+    M, D = kl.shape
+    mask = kl > kl_threshold
+    raw, pairwise = np.zeros((M, M, D, D)), np.zeros((M, M))
+    for i in range(M):
+        for j in range(i + 1, M):
+            cov = np.asarray(cov_of_pair(i, j), dtype=np.float64)
+            flip = np.block([[cov[D:, D:], cov[D:, :D]], [cov[:D, D:], cov[:D, :D]]])
+            if correlation == "spearman":
+                raw[i, j] = udr_correlation_from_cov(cov, mask[i], mask[j])
+                raw[j, i] = raw[i, j].T
+            else:
+                raw[i, j] = udr_lasso_from_cov(cov, mask[i], mask[j], lasso_alpha)
+                raw[j, i] = udr_lasso_from_cov(flip, mask[j], mask[i], lasso_alpha)
+            for a, b in ((i, j), (j, i)):
+                pairwise[a, b] = udr_pair_score(raw[a, b][np.ix_(mask[a], mask[b])] if filter_low_kl else raw[a, b])
+    return {"model_scores": udr_model_scores(pairwise), "pairwise_scores": pairwise, "raw_correlations": raw, "kl": kl,
+            "n_active": mask.sum(axis=1)}
+
+
+def udr_from_tables(means, logvars, correlation="spearman", n_samples=None, seed=0, rows=None, kl_threshold=0.01, filter_low_kl=True,
+                    lasso_alpha=0.1):
+    """Unsupervised disentanglement ranking (Duan et al. 2020; disentanglement_lib's udr.py) of M >= 2 models given as their fp32
+    [N, D] tables of posterior means and log-variances (on the GPU; the same N and the same D <= 32 for all): no factor of
+    variation is needed.
+
+    kl [M, D] = dvae_udr_kl_dims of every model; a latent is informative when kl > kl_threshold.
+    "spearman": dvae_udr_ranks of every model's means (exact tie-averaged ranks; ranks do not depend on standardisation, so none
+    is applied), dvae_unsup_moments of the [S, 2D] rank tables of every pair, R_ij[a, b] = |cov / sqrt(var var)|, 0 where a
+    variance is 0 or a latent is not informative.  "lasso": the same moments of the raw means; R_ij[a, b] = |w_a| of the Lasso
+    (lasso_alpha; lasso_from_gram) that predicts latent b of model j from the latents of model i.
+    pairwise_scores[i, j] = udr_pair_score of R_ij restricted to the informative latents (filter_low_kl), diagonal 0;
+    model_scores[i] = the median over j != i of pairwise_scores[j, i].
+
+    n_samples=None: every row; else rows = randperm(N)[:n_samples] from a private generator seeded with ``seed`` (the same seed
+    gives the same bits, the global random states are untouched); ``rows`` injects the selection; ONE selection serves every
+    model.  Every size and argument is checked before any device work, and a table with a NaN or an infinity raises ValueError.
+    All M models go through ONE dvae_unsup_moments call when M D <= 64.  Returns {"model_scores" [M], "pairwise_scores" [M, M],
+    "raw_correlations" [M, M, D, D], "kl" [M, D], "n_active" [M], "n_samples", "correlation"}: Python and numpy values."""
+    means, logvars = list(means), list(logvars)
+    if len(means) != len(logvars):
+        raise ValueError("means and logvars must hold one table per model, got %d and %d" % (len(means), len(logvars)))
+    n, dim = _table_shape(means[0]) if means else (None, None)
+    _check_udr_arguments(len(means), n, dim, correlation, n_samples, seed, rows, kl_threshold, filter_low_kl, lasso_alpha)
+    for t in means + logvars:
+        if _table_shape(t) != (n, dim):
+            raise ValueError("every table must be [%d, %d] like the first, got %s" % (n, dim, tuple(t.shape)))
+    if rows is not None:
+        rows = _checked_rows(rows, n)
+        if rows.numel() > _udrlib.MAX_ROWS:
+            raise ValueError("UDR ranks at most %d rows" % _udrlib.MAX_ROWS)
+    for name, tables in (("means", means), ("log-variances", logvars)):
+        for t in tables:
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError("a table of %s holds a NaN or an infinity" % name)
+    M = len(means)
+    first, rows, S, dev = _select_rows(means[0], rows, n_samples, seed, "udr_from_tables", "ranking")   # ONE selection for all models
+    mus = [first] + [_select_rows(mu, rows, None, seed, "udr_from_tables", "ranking")[0] for mu in means[1:]]
+    lvs = [lv.detach().to(device=dev, dtype=torch.float32).contiguous() for lv in logvars]
+    L, U = _udrlib.lib(), _unsuplib.lib()
+    st = _stream()
+    one_call = M * dim <= _unsuplib.MAX_D
+    wide = M * dim if one_call else 2 * dim
+    ws = torch.empty(max(L.dvae_udr_ranks_ws_floats(n, dim, S), L.dvae_udr_kl_dims_ws_floats(n, dim, S),
+                         U.dvae_unsup_moments_ws_floats(S if correlation == "spearman" else n, wide, S), 1),
+                     dtype=torch.float32, device=dev)
+    kl_dev = torch.empty(M, dim, dtype=torch.float64, device=dev)
+    for i in range(M):
+        _udrlib.call("dvae_udr_kl_dims", ptr(mus[i]), ptr(lvs[i]), ptr(rows), n, dim, S, ptr(ws), ptr(kl_dev[i]), st)
+    if correlation == "spearman":                                                   # [S, D] rank tables: every row of them counts
+        tabs = [torch.empty(S, dim, dtype=torch.float32, device=dev) for _ in range(M)]
+        for i in range(M):
+            _udrlib.call("dvae_udr_ranks", ptr(mus[i]), ptr(rows), n, dim, S, ptr(ws), ptr(tabs[i]), st)
+        tab_rows, tab_n = None, S
+    else:
+        tabs, tab_rows, tab_n = mus, rows, n
+
+    def moments(parts):
+        both = torch.cat(parts, dim=1).contiguous()
+        W = both.shape[1]
+        out = torch.empty(W * W + 2 * W, dtype=torch.float64, device=dev)         # cov, mean, then min and max: 2 W floats in W doubles
+        minmax = out[W * W + W:].view(torch.float32)
+        _unsuplib.call("dvae_unsup_moments", ptr(both), ptr(tab_rows), tab_n, W, S, ptr(ws), ptr(minmax[:W]), ptr(minmax[W:]),
+                       ptr(out[W * W:W * W + W]), ptr(out[:W * W]), st)
+        return out[:W * W].cpu().numpy().reshape(W, W)
+    if one_call:
+        cov_all = moments(tabs)
+
+        def cov_of_pair(i, j):
+            at = np.concatenate([np.arange(i * dim, (i + 1) * dim), np.arange(j * dim, (j + 1) * dim)])
+            return cov_all[np.ix_(at, at)]
+    else:
+        def cov_of_pair(i, j):
+            return moments([tabs[i], tabs[j]])
+    scores = udr_from_statistics(kl_dev.cpu().numpy(), cov_of_pair, correlation, kl_threshold, filter_low_kl, lasso_alpha)
+    scores.update(n_samples=S, correlation=correlation)
     return scores
