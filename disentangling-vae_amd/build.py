@@ -11,6 +11,9 @@ EXTRA_TARGETS is a second table of the same (name, sources, header) rows, built 
 _target() / _build_target() path and given the same derived names (UDR_LIB / UDR_SOURCES / UDR_HEADERS).  The two tables are
 ONE list in spirit: tests/test_score_plumbing_host.py pins TARGETS (its length, its names, ALL_SOURCES, tools/isa_identity.py)
 and existing tests do not change with a feature, so a library added since stands here; the tables merge when that pin can move.
+LATER_TARGETS is the third table of that one list, for the same reason once more: tests/test_udr_host.py pins EXTRA_TARGETS to its
+one row, so a library added after it (DCI_LIB / DCI_SOURCES / DCI_HEADERS) stands there, same rows, same build path.  Its own
+test asserts that its row is IN the table, not what the table is: the next library is one more row of LATER_TARGETS.
 The libraries land in disentangling-vae_amd/lib/ (git-ignored build products).  Objects are rebuilt only
 when a source / header is newer or the flags changed.
 --debug (or DVAE_BUILD_DEBUG=1) adds -DDVAE_DEBUG_SWITCHES: the A/B / timing-ablation environment
@@ -41,6 +44,10 @@ TARGETS = [
 EXTRA_TARGETS = [
     ("udr", ["latent_ranks"], "dvae_udr_hip.h"),           # unsupervised disentanglement ranking: tie-averaged ranks, KL per dimension
 ]
+# libraries added since the pin on EXTRA_TARGETS (module docstring): the same rows, the same build path; add rows here
+LATER_TARGETS = [
+    ("dci", ["boosted_trees"], "dvae_dci_hip.h"),          # DCI: gradient-boosted trees fitted on the device, their importances
+]
 HEADERS = sorted(glob.glob(os.path.join(SRC, "*.h"))) + [os.path.join(HERE, "..", "include", "dvae_hip.h")]
 
 
@@ -51,7 +58,7 @@ def _target(name, sources, header):
     return os.path.join(HERE, "lib", "libdvae%s_hip.so" % infix), sources, headers, os.path.join(OBJ, "flags%s.txt" % infix)
 
 
-for _row in TARGETS + EXTRA_TARGETS:        # LIB / SOURCES / HEADERS of the training library, EVAL_LIB / EVAL_SOURCES / EVAL_HEADERS, ... of the others
+for _row in TARGETS + EXTRA_TARGETS + LATER_TARGETS:        # LIB / SOURCES / HEADERS of the training library, EVAL_LIB / EVAL_SOURCES / EVAL_HEADERS, ... of the others
     _prefix = _row[0].upper() + "_" if _row[0] else ""
     globals()[_prefix + "LIB"], globals()[_prefix + "SOURCES"], globals()[_prefix + "HEADERS"], _ = _target(*_row)
 ALL_SOURCES = [s for _, sources, _ in TARGETS for s in sources]
@@ -92,14 +99,14 @@ def _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose):
 
 
 def build(force=False, verbose=True, debug=None):
-    """Build every target of TARGETS, then of EXTRA_TARGETS; returns the path of libdvae_hip.so."""
+    """Build every target of TARGETS, then of EXTRA_TARGETS, then of LATER_TARGETS; returns the path of libdvae_hip.so."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if debug is None:
         debug = os.environ.get("DVAE_BUILD_DEBUG", "0") == "1"
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
     flags = FLAGS + (["-DDVAE_DEBUG_SWITCHES"] if debug else [])
-    for name, sources, header in TARGETS + EXTRA_TARGETS:
+    for name, sources, header in TARGETS + EXTRA_TARGETS + LATER_TARGETS:
         lib, sources, headers, stamp = _target(name, sources + (DEBUG_SOURCES if debug and not name else []), header)
         _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose)
     return LIB

@@ -42,6 +42,12 @@
   model's table as HIP launches (libdvae_udr_hip.so: a segmented radix sort), the correlation of the rank tables by
   dvae_unsup_moments; the [D, D] correlation blocks cross to the host, where the Lasso form is fitted and the scores are
   combined in fp64.  Written to udr.log by ``__call__(udr_models=[...])``.
+* DCI -- disentanglement, completeness, informativeness (Eastwood & Williams 2018; disentanglement_lib's dci.py), new
+  (``compute_dci`` / ``dci_from_table``): per factor of variation a gradient-boosted tree classifier (scikit-learn's
+  GradientBoostingClassifier with default arguments, restated) is FITTED ON THE DEVICE on the posterior means where they lie
+  (libdvae_dci_hip.so: every stage of every factor is enqueued without a read-back); the [D] importances and the accuracies cross
+  to the host, where the entropies of the [D, K] importance matrix are combined in fp64.  Written to dci.log by
+  ``__call__(is_dci=True)``.
 """
 import logging
 import math
@@ -52,7 +58,7 @@ from timeit import default_timer
 import numpy as np
 import torch
 
-from . import _evallib, _infolib, _irslib, _lib, _scorelib, _udrlib, _unsuplib
+from . import _dcilib, _evallib, _infolib, _irslib, _lib, _scorelib, _udrlib, _unsuplib
 from ._lib import call, ptr
 from .engine import _stream
 from .likelihood import _ScorePasses, check_rec_dist, log_likelihood
@@ -69,6 +75,7 @@ INFORMATION_SCORES_FILE = "information_scores.log"
 IRS_FILE = "irs.log"
 UNSUPERVISED_SCORES_FILE = "unsupervised_scores.log"
 UDR_FILE = "udr.log"
+DCI_FILE = "dci.log"
 
 
 class Evaluator:
@@ -85,7 +92,7 @@ class Evaluator:
 
     def __call__(self, data_loader, is_metrics=False, is_losses=True, is_log_likelihood=False, n_samples=128,
                  is_decomposition=False, n_samples_decomposition=10000, is_scores=False, is_information=False,
-                 is_irs=False, is_unsupervised=False, udr_models=None):
+                 is_irs=False, is_unsupervised=False, udr_models=None, is_dci=False, dci_args=None):
         """evaluate.py:60-95.  is_log_likelihood: also write compute_log_likelihood(data_loader, n_samples) to
         log_likelihood.log; is_decomposition: also write compute_elbo_decomposition(data_loader, n_samples_decomposition) to
         elbo_decomposition.log; is_scores: also write compute_factor_scores(data_loader) to factor_scores.log; is_information: also
@@ -93,7 +100,8 @@ class Evaluator:
         its arrays as lists, to irs.log; is_unsupervised: also write compute_unsupervised_scores(data_loader), its arrays as lists and
         without its [D, D] matrix, to unsupervised_scores.log; udr_models (the other models of a sweep): also write
         compute_udr(data_loader, udr_models), its arrays as lists and without raw_correlations, to udr.log (the return value stays
-        the reference's (metric, losses))."""
+        the reference's (metric, losses)); is_dci: also write compute_dci(data_loader, **dci_args), without its [D, K] matrix, to
+        dci.log."""
         start = default_timer()
         is_still_training = self.model.training
         self.model.eval()
@@ -157,6 +165,12 @@ class Evaluator:
             self.logger.info('UDR: {}'.format(udr))
             os.makedirs(self.save_dir, exist_ok=True)
             save_metadata(udr, self.save_dir, filename=UDR_FILE)
+        if is_dci:
+            self.logger.info('Computing the DCI scores...')
+            dci = {k: v for k, v in self.compute_dci(data_loader, **(dci_args or {})).items() if not isinstance(v, np.ndarray)}
+            self.logger.info('DCI: {}'.format(dci))
+            os.makedirs(self.save_dir, exist_ok=True)
+            save_metadata(dci, self.save_dir, filename=DCI_FILE)
         if is_still_training:
             self.model.train()
         self.logger.info('Finished evaluating after {:.1f} min.'.format((default_timer() - start) / 60))
@@ -398,6 +412,31 @@ class Evaluator:
         means = [torch.cat([mu for mu, _ in c]) for c in chunks]
         logvars = [torch.cat([lv for _, lv in c]) for c in chunks]
         return udr_from_tables(means, logvars, **kw)
+
+    # ------------------------------------------------------------------ DCI
+    def compute_dci(self, dataloader, n_train=10000, n_test=5000, seed=0, n_stages=100):
+        """Disentanglement, completeness and informativeness of the model (dci_from_table below, on the posterior means of the
+        whole data set through the native encoder).  The data-set requirements and errors of compute_factor_scores; every size and
+        argument is checked before any device work; train / eval mode is restored."""
+        ds = getattr(dataloader, "dataset", None)
+        if not (hasattr(ds, "lat_sizes") and hasattr(ds, "lat_names")):
+            raise ValueError("Dataset needs to have known true factors of variations to compute the metric. This does not "
+                             "seem to be the case for {}".format(type(ds).__name__))
+        lat_sizes = [int(k) for k in ds.lat_sizes]
+        n = int(np.prod(lat_sizes)) if lat_sizes else 0
+        _check_dci_arguments(n, None, lat_sizes, n_train, n_test, seed, None, n_stages)
+        if hasattr(ds, "__len__") and len(ds) != n:
+            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (len(ds), lat_sizes))
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            mean, _logvar = self._encode_dataset(dataloader)
+        finally:
+            if was_training:
+                self.model.train()
+        if mean.shape[0] != n:
+            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (mean.shape[0], lat_sizes))
+        return dci_from_table(mean, lat_sizes, n_train=n_train, n_test=n_test, seed=seed, n_stages=n_stages)
 
     # ------------------------------------------------------------------ MIG / AAM (evaluate.py:119-317)
     def compute_metrics(self, dataloader, sample_idx=None, n_samples=10000):
@@ -1303,3 +1342,117 @@ def udr_from_tables(means, logvars, correlation="spearman", n_samples=None, seed
     scores = udr_from_statistics(kl_dev.cpu().numpy(), cov_of_pair, correlation, kl_threshold, filter_low_kl, lasso_alpha)
     scores.update(n_samples=S, correlation=correlation)
     return scores
+
+
+# ---------------------------------------------------------------------- DCI on a table of means
+DCI_LEARNING_RATE = 0.1                                                  # GradientBoostingClassifier's default
+
+
+def _check_dci_arguments(n, dim, lat_sizes, n_train=10000, n_test=5000, seed=0, rows=None, n_stages=100):
+    """n: prod(lat_sizes); dim: None where not known yet (before the encoder ran)."""
+    if len(lat_sizes) < 1 or min(lat_sizes) < 1:
+        raise ValueError("lat_sizes must hold positive sizes, got %s" % (lat_sizes,))
+    if max(lat_sizes) > _dcilib.MAX_CLASSES:
+        raise ValueError("a factor of variation with %d values: the boosted-tree kernels take at most %d classes"
+                         % (max(lat_sizes), _dcilib.MAX_CLASSES))
+    if not 1 <= int(n_train) <= _dcilib.MAX_ROWS:
+        raise ValueError("n_train must lie in [1, %d], got %r" % (_dcilib.MAX_ROWS, n_train))
+    if int(n_test) < 1:
+        raise ValueError("n_test must be at least 1, got %r" % (n_test,))
+    if not 1 <= int(n_stages) <= _dcilib.MAX_STAGES:
+        raise ValueError("n_stages must lie in [1, %d], got %r" % (_dcilib.MAX_STAGES, n_stages))
+    int(seed)
+    if rows is None and int(n_train) + int(n_test) > n:
+        raise ValueError("n_train + n_test must be at most %d (rows are drawn without replacement), got %d + %d"
+                         % (n, int(n_train), int(n_test)))
+    if dim is not None and not 1 <= dim <= _dcilib.MAX_D:
+        raise ValueError("the table must have between 1 and %d latent dimensions, got %d" % (_dcilib.MAX_D, dim))
+
+
+def dci_from_importance(importance):
+    """disentanglement_lib's dci.py on the importance matrix [D, K] (latents x factors), fp64 -> (disentanglement, completeness):
+    disentanglement = sum_d w_d (1 - H_K[(R_d. + 1e-11) normalised]), w_d = sum_k R_dk / sum R; completeness = sum_k w_k (1 -
+    H_D[(R_.k + 1e-11) normalised]), w_k = sum_d R_dk / sum R; H_b the entropy to base b.  A matrix that sums to 0 weighs every
+    latent and every factor alike (disentanglement_lib's fall-back), which gives 0 / 0; base 1 (one factor, one latent) has no
+    entropy: that side counts as 1."""
+    R = np.abs(np.asarray(importance, dtype=np.float64))
+    if R.ndim != 2 or R.size == 0:
+        raise ValueError("importance must be a non-empty [D, K] matrix, got shape %s" % (R.shape,))
+
+    def one_minus_entropy(M, base):                                      # rows of M are distributions
+        if base < 2:
+            return np.ones(M.shape[0])
+        P = (M + 1e-11) / (M + 1e-11).sum(axis=1, keepdims=True)
+        return 1.0 + (P * np.log(P)).sum(axis=1) / math.log(base)
+    D, K = R.shape
+    per_code, per_factor = one_minus_entropy(R, K), one_minus_entropy(R.T, D)
+    W = np.ones_like(R) if R.sum() == 0.0 else R
+    return float((per_code * W.sum(axis=1) / W.sum()).sum()), float((per_factor * W.sum(axis=0) / W.sum()).sum())
+
+
+def dci_from_table(mean, lat_sizes, n_train=10000, n_test=5000, seed=0, rows=None, n_stages=100):
+    """DCI of a representation given as the fp32 [N, D] table ``mean`` (on the GPU) of a data set that enumerates ``lat_sizes`` in
+    row-major order: per factor a gradient-boosted classifier -- scikit-learn's GradientBoostingClassifier() restated
+    (include/dvae_dci_hip.h), ``n_stages`` stages -- predicts the factor from the latents of n_train rows; its normalised
+    feature importances are column k of the [D, K] importance matrix (dci_from_importance), its accuracy on the n_train rows and on
+    n_test others is the informativeness.
+
+    rows = randperm(N)[:n_train + n_test] from a private generator seeded with ``seed`` (the same seed gives the same bits, the
+    global random states are untouched), the first n_train to fit; ``rows`` ([n_train + n_test] row numbers in [0, N), repeats
+    allowed) injects the selection.  The factor values are digits of the row number; the labels of factor k are the ranks of its
+    values among those PRESENT in the training rows (a test row with a value never seen counts as an error; a factor with one
+    value present fits no tree: its column of the matrix is zero and its accuracy 1).  The columns are sorted ONCE (a stable
+    torch.sort) for all factors; every stage of a factor is enqueued by ONE dvae_dci_fit call and nothing is read back until the
+    importances and the predictions of all factors are there.  Every size and argument is checked before any device work, and
+    a table with a NaN or an infinity raises ValueError.  Among exactly equal gains the lowest feature wins, where scikit-learn
+    draws the order of the features from random_state.  Returns {"disentanglement", "completeness", "informativeness_train",
+    "informativeness_test", "importance_matrix" [D, K], "n_train", "n_test", "n_stages"}: Python and numpy values."""
+    lat_sizes = [int(k) for k in lat_sizes]
+    K, n_train, n_test, n_stages = len(lat_sizes), int(n_train), int(n_test), int(n_stages)
+    n, dim = _table_shape(mean)
+    _check_dci_arguments(int(np.prod(lat_sizes)) if lat_sizes else 0, dim, lat_sizes, n_train, n_test, seed, rows, n_stages)
+    if n != int(np.prod(lat_sizes)):
+        raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (n, lat_sizes))
+    if rows is not None and torch.as_tensor(rows).numel() != n_train + n_test:
+        raise ValueError("rows must hold n_train + n_test = %d row numbers" % (n_train + n_test))
+    table, rows, _S, dev = _select_rows(mean, rows, n_train + n_test, seed, "dci_from_table", "boosted-tree")
+    L = _dcilib.lib()
+    st = _stream()
+    train, test = rows[:n_train].contiguous(), rows[n_train:].contiguous()
+    order = torch.sort(table.index_select(0, train), dim=0, stable=True).indices.t().contiguous().to(torch.int32)    # [D, n_train]
+    strides = [int(np.prod(lat_sizes[k + 1:])) for k in range(K)]
+    fits = []
+    for k in range(K):
+        values_train, values_test = ((r // strides[k]) % lat_sizes[k] for r in (train, test))
+        classes = torch.unique(values_train)                             # sorted; its length is the one number the host needs now
+        C = int(classes.numel())
+        T = _dcilib.trees(C)
+        labels = torch.searchsorted(classes, values_train).to(torch.int32).contiguous()
+        ws = torch.empty(max(L.dvae_dci_fit_ws_floats(n, dim, n_train, C, n_stages), 2), dtype=torch.float32, device=dev)
+        raw = torch.empty(n_train, T, dtype=torch.float64, device=dev)
+        importance = torch.empty(dim, dtype=torch.float64, device=dev)
+        n_split = torch.empty(1, dtype=torch.int32, device=dev)
+        feature = torch.empty(n_stages, T, _dcilib.NODES, dtype=torch.int32, device=dev)
+        stats = torch.empty(n_stages, T, _dcilib.NODES, _dcilib.NODE_STATS, dtype=torch.float64, device=dev)
+        prior = torch.empty(T, dtype=torch.float64, device=dev)
+        _dcilib.call("dvae_dci_fit", ptr(table), ptr(train), ptr(order), ptr(labels), n, dim, n_train, C, n_stages, DCI_LEARNING_RATE,
+                     1, ptr(raw), ptr(prior), ptr(ws), ptr(importance), ptr(n_split), ptr(feature), ptr(stats), st)
+        raw_test = prior.expand(n_test, T).contiguous()
+        _dcilib.call("dvae_dci_predict", ptr(table), ptr(test), n, dim, n_test, C, n_stages, DCI_LEARNING_RATE, ptr(feature),
+                     ptr(stats), ptr(raw_test), st)
+
+        def accuracy(raw_scores, values):
+            picked = (raw_scores[:, 0] > 0).long() if C == 2 else raw_scores.argmax(dim=1)
+            return (classes[picked] == values).double().mean()
+        fits.append((importance, n_split, accuracy(raw, values_train), accuracy(raw_test, values_test)))
+    matrix = np.zeros((dim, K))
+    acc = np.zeros((K, 2))
+    for k, (importance, n_split, acc_train, acc_test) in enumerate(fits):      # the read-back, after every factor was enqueued
+        total, count = importance.cpu().numpy(), int(n_split.item())
+        if count > 0 and total.sum() > 0:
+            matrix[:, k] = np.abs(total / count / (total / count).sum())
+        acc[k] = acc_train.item(), acc_test.item()
+    disentanglement, completeness = dci_from_importance(matrix)
+    return {"disentanglement": disentanglement, "completeness": completeness, "informativeness_train": float(acc[:, 0].mean()),
+            "informativeness_test": float(acc[:, 1].mean()), "importance_matrix": matrix, "n_train": n_train, "n_test": n_test,
+            "n_stages": n_stages}
