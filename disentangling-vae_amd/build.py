@@ -12,7 +12,7 @@ _target() / _build_target() path and given the same derived names (UDR_LIB / UDR
 ONE list in spirit: tests/test_score_plumbing_host.py pins TARGETS (its length, its names, ALL_SOURCES, tools/isa_identity.py)
 and existing tests do not change with a feature, so a library added since stands here; the tables merge when that pin can move.
 LATER_TARGETS is the third table of that one list, for the same reason once more: tests/test_udr_host.py pins EXTRA_TARGETS to its
-one row, so a library added after it (DCI_LIB / DCI_SOURCES / DCI_HEADERS) stands there, same rows, same build path.  Its own
+one row, so the libraries added after it (DCI_LIB / DCI_SOURCES / DCI_HEADERS, DIP_LIB / ...) stand there, same rows, same build path.  Its own
 test asserts that its row is IN the table, not what the table is: the next library is one more row of LATER_TARGETS.
 The libraries land in disentangling-vae_amd/lib/ (git-ignored build products).  Objects are rebuilt only
 when a source / header is newer or the flags changed.
@@ -47,6 +47,7 @@ EXTRA_TARGETS = [
 # libraries added since the pin on EXTRA_TARGETS (module docstring): the same rows, the same build path; add rows here
 LATER_TARGETS = [
     ("dci", ["boosted_trees"], "dvae_dci_hip.h"),          # DCI: gradient-boosted trees fitted on the device, their importances
+    ("dip", ["dip_cov"], "dvae_dip_hip.h"),                # DIP-VAE I / II: batch covariance, the regulariser and its gradients (a TRAINING loss)
 ]
 HEADERS = sorted(glob.glob(os.path.join(SRC, "*.h"))) + [os.path.join(HERE, "..", "include", "dvae_hip.h")]
 

@@ -1,5 +1,6 @@
 """Loss plugins with the API of disvae/models/losses.py (get_loss_f, BaseLoss, BetaHLoss,
-BetaBLoss, FactorKLoss, BtcvaeLoss, LOSSES, RECON_DIST) on the HIP kernels.
+BetaBLoss, FactorKLoss, BtcvaeLoss, LOSSES, RECON_DIST) on the HIP kernels, plus DipVaeLoss / DIP_LOSSES
+(DIP-VAE-I / II, which the reference does not have).
 
 Two ways in:
   * ``loss(data, recon, latent_dist, is_train, storer, latent_sample=...)`` -- the reference
@@ -16,6 +17,7 @@ import contextlib
 
 import torch
 
+from .. import _diplib
 from .. import _lib
 from .. import optim
 from .._lib import call, ptr, record_py
@@ -28,6 +30,7 @@ from ..schedule import build_policy, replay_mode, switches
 
 LOSSES = ["VAE", "betaH", "betaB", "factor", "btcvae"]  # losses.py:17
 RECON_DIST = ["bernoulli", "laplace", "gaussian"]        # losses.py:18
+DIP_LOSSES = ["dipI", "dipII"]                           # DIP-VAE-I / II (Kumar et al. 2018): not in the reference, so not in LOSSES
 
 
 def get_loss_f(loss_name, **kwargs_parse):
@@ -47,6 +50,9 @@ def get_loss_f(loss_name, **kwargs_parse):
     elif loss_name == "btcvae":
         return BtcvaeLoss(kwargs_parse["n_data"], alpha=kwargs_parse["btcvae_A"], beta=kwargs_parse["btcvae_B"],
                           gamma=kwargs_parse["btcvae_G"], **kwargs_all)
+    elif loss_name in DIP_LOSSES:
+        return DipVaeLoss(dip_type="i" if loss_name == "dipI" else "ii", lambda_od=kwargs_parse.get("dip_lambda_od", 10.),
+                          lambda_d_factor=kwargs_parse.get("dip_lambda_d_factor"), **kwargs_all)
     else:
         assert loss_name not in LOSSES
         raise ValueError("Uknown loss : {}".format(loss_name))
@@ -402,6 +408,38 @@ class _BtcvaeFn(torch.autograd.Function):
         return dz, dmu, dlv, None, None, None
 
 
+def _dip_launches(mu, logvar, lambda_od, lambda_d, ws, dmu, dlv, out, loss_io, stream):
+    """The two launches of libdvae_dip_hip.so (include/dvae_dip_hip.h) on a [B, D] batch; logvar None: DIP-VAE-I.  Through
+    record_py: a recorded plan re-issues them with these arguments, a hipGraph captures them."""
+    B, D = mu.shape
+    record_py(_diplib.call, "dvae_dip_moments", ptr(mu), ptr(logvar), B, D, ptr(ws), stream)
+    record_py(_diplib.call, "dvae_dip_grad", ptr(mu), ptr(logvar), B, D, float(lambda_od), float(lambda_d), ptr(ws), ptr(dmu),
+              ptr(dlv), ptr(out), loss_io, stream)
+
+
+class _DipFn(torch.autograd.Function):
+    """The DIP-VAE regulariser R(mu, logvar) (logvar None: type I) -> 0-d tensor; value and both gradients come from the same
+    two launches as in the fused step, so backward only scales what forward saved."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, lambda_od, lambda_d):
+        mu = mu.contiguous()
+        logvar = None if logvar is None else logvar.contiguous()
+        B, D = mu.shape
+        f64 = lambda n: torch.empty(n, dtype=torch.float64, device=mu.device)
+        ws, out = f64(_diplib.ws_doubles(B, D)), f64(_diplib.out_doubles(D))
+        dmu = torch.empty_like(mu)
+        dlv = None if logvar is None else torch.empty_like(mu)
+        _dip_launches(mu, logvar, lambda_od, lambda_d, ws, dmu, dlv, out, None, _stream())
+        ctx.save_for_backward(dmu, dlv)
+        return out[0].float()
+
+    @staticmethod
+    def backward(ctx, gout):
+        dmu, dlv = ctx.saved_tensors
+        return dmu * gout, None if dlv is None else dlv * gout, None, None
+
+
 def u8_to_f32(x):
     """ToTensor's arithmetic on a uint8 device tensor: float(v) / 255 (dvae_u8_to_f32)."""
     x = x.contiguous()
@@ -461,6 +499,12 @@ class _SingleOptimizerLoss(BaseLoss):
 
     def _coefs(self, is_train):
         raise NotImplementedError
+
+    def _regulariser(self, buf, sc, B, D, is_train, stream):
+        """Hook of _device_step: launches on `stream` behind the loss epilogue that add a term to sc.scal[S_LOSS] -> its
+        (dmu_x, dlv_x) for the FC chain's backward pass (None: no such term, no launch).  Only for steps whose epilogue is not
+        deferred (StepPolicy.late_join: beta-TCVAE and sharded steps), or the term would be added before the epilogue writes."""
+        return None
 
     def fused_step(self, data, model, optimizer, storer, eps=None):
         is_train = model.training
@@ -528,6 +572,12 @@ class _SingleOptimizerLoss(BaseLoss):
             elif btc:
                 eng._join_side()
             self._finish_loss(sc, klb, D, rowstats, B, None, Bg, s)
+        # a regulariser of the batch's (mu, logvar) beyond the KL term (DIP-VAE): its launches behind the epilogue on this
+        # stream, its gradients into the FC chain like the estimator's; nothing for the reference's losses
+        reg = self._regulariser(buf, sc, B, D, is_train, s)
+        if reg is not None:
+            assert wait is None, "a regulariser hook behind a deferred epilogue"
+            dmu, dlv = reg
         if not is_train:
             return
 
@@ -558,6 +608,92 @@ class BetaHLoss(_SingleOptimizerLoss):
         anneal_reg = linear_annealing(0, 1, self.n_train_steps, self.steps_anneal) if is_train else 1
         loss = rec_loss + anneal_reg * (self.beta * kl_loss)
         if storer is not None:
+            storer['loss'].append(loss.item())
+        return loss
+
+
+class DipVaeLoss(_SingleOptimizerLoss):
+    """DIP-VAE-I / DIP-VAE-II (Kumar et al. 2018; disentanglement_lib's DIPVAE -- the reference has no counterpart):
+
+        loss = rec + anneal * KL + lambda_od sum_{d != e} C_de^2 + lambda_d sum_d (C_dd - 1)^2,   lambda_d = lambda_d_factor * lambda_od
+
+    with C the biased covariance of the batch's posterior means (type "i"), plus the diagonal of the batch mean of
+    exp(logvar) (type "ii").  rec and KL are BetaHLoss's with beta = 1, and steps_anneal acts on the KL term as there; the
+    regulariser is never annealed.  lambda_d_factor None: 10 for type I, 1 for type II (disentanglement_lib's defaults).
+    The regulariser couples the whole batch: data-parallel steps are not built (fused_step raises under a communicator of
+    more than one rank)."""
+    KIND = _lib.LOSS_BETAH
+    STORED = (('recon_loss', _lib.S_REC), ('kl_loss', _lib.S_KL), ('dip_loss', None), ('loss', _lib.S_LOSS))
+
+    def __init__(self, dip_type="i", lambda_od=10., lambda_d_factor=None, **kwargs):
+        super().__init__(**kwargs)
+        if dip_type not in ("i", "ii"):
+            raise ValueError("dip_type must be 'i' or 'ii', got {!r}".format(dip_type))
+        self.dip_type = dip_type
+        self.beta = 1
+        self.lambda_od = float(lambda_od)
+        self.lambda_d_factor = float({"i": 10., "ii": 1.}[dip_type] if lambda_d_factor is None else lambda_d_factor)
+        self._dip = {}
+
+    @property
+    def lambda_d(self):
+        return self.lambda_d_factor * self.lambda_od
+
+    def _coefs(self, is_train):
+        anneal = linear_annealing(0, 1, self.n_train_steps, self.steps_anneal) if is_train else 1
+        return dict(ANNEAL=anneal, BETA=self.beta)
+
+    def _dip_buf(self, device, name, n):
+        """fp64 buffers of the two launches, allocated once: ("ws", B, D) the workspace, ("out", D) value and covariance."""
+        t = self._dip.get((device,) + name)
+        if t is None:
+            _lib.note_alloc()
+            t = self._dip[(device,) + name] = torch.zeros(n, dtype=torch.float64, device=device)
+        return t
+
+    def _regulariser(self, buf, sc, B, D, is_train, stream):
+        """R on top of the epilogue's rec + anneal * KL in sc.scal[S_LOSS] (dvae_dip_grad's loss_io: no third launch) -> the
+        gradients for the FC chain; evaluation: the value only."""
+        ws = self._dip_buf(sc.device, ("ws", B, D), _diplib.ws_doubles(B, D))
+        out = self._dip_buf(sc.device, ("out", D), _diplib.out_doubles(D))
+        lv = buf.logvar if self.dip_type == "ii" else None
+        dmu = sc.latent("dip_dmu", B, D) if is_train else None
+        dlv = sc.latent("dip_dlv", B, D) if is_train and lv is not None else None
+        _dip_launches(buf.mu, lv, self.lambda_od, self.lambda_d, ws, dmu, dlv, out, ptr(sc.scal) + 4 * _lib.S_LOSS, stream)
+        return dmu, dlv
+
+    def _replay_key(self, model, data, injected, pol):
+        return super()._replay_key(model, data, injected, pol) + (self.lambda_od, self.lambda_d, self.dip_type)
+
+    def _store(self, storer, sc, D, keys=None):
+        if storer is None:
+            return
+        vals = sc.scal.tolist()
+        dip = self._dip[(sc.device, "out", D)][0].item()        # fp64 [R, R_od, R_d, C]: a second small copy, on logging steps only
+        for key, slot in self.STORED:
+            if key == 'kl_loss':
+                self._store_kl(storer, vals, D)
+            else:
+                storer[key].append(dip if key == 'dip_loss' else vals[slot])
+
+    def fused_step(self, data, model, optimizer, storer, eps=None):
+        if self._world()[0] > 1:
+            raise NotImplementedError(
+                "DIP-VAE under data parallelism is not built: the covariance couples the GLOBAL batch, so a sharded step has to "
+                "gather the latents of every rank first, as the beta-TCVAE estimator does (Comm.all_gather_latents)")
+        return super().fused_step(data, model, optimizer, storer, eps=eps)
+
+    def __call__(self, data, recon_data, latent_dist, is_train, storer, **kwargs):
+        storer = self._pre_call(is_train, storer)
+        sc = self.scratch(recon_data.device)
+        rec_loss = _reconstruction_loss(data, recon_data, storer=storer, distribution=self.rec_dist, scratch=sc)
+        kl_loss = _kl_normal_loss(*latent_dist, storer, scratch=sc)
+        mu, logvar = latent_dist
+        dip_loss = _DipFn.apply(mu, logvar if self.dip_type == "ii" else None, self.lambda_od, self.lambda_d)
+        anneal_reg = linear_annealing(0, 1, self.n_train_steps, self.steps_anneal) if is_train else 1
+        loss = rec_loss + anneal_reg * (self.beta * kl_loss) + dip_loss
+        if storer is not None:
+            storer['dip_loss'].append(dip_loss.item())
             storer['loss'].append(loss.item())
         return loss
 
