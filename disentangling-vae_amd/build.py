@@ -7,13 +7,6 @@ include/.  Target "" is libdvae_hip.so, the training library; every other target
 nothing of one target is linked into another.  All targets share FLAGS and the up-to-date
 logic, each under a stamp of its own (build/flags.txt, build/flags_NAME.txt).  The module's X_LIB / X_SOURCES /
 X_HEADERS names (LIB / SOURCES / HEADERS for the training library) are derived from the table.
-EXTRA_TARGETS is a second table of the same (name, sources, header) rows, built right after TARGETS through the same
-_target() / _build_target() path and given the same derived names (UDR_LIB / UDR_SOURCES / UDR_HEADERS).  The two tables are
-ONE list in spirit: tests/test_score_plumbing_host.py pins TARGETS (its length, its names, ALL_SOURCES, tools/isa_identity.py)
-and existing tests do not change with a feature, so a library added since stands here; the tables merge when that pin can move.
-LATER_TARGETS is the third table of that one list, for the same reason once more: tests/test_udr_host.py pins EXTRA_TARGETS to its
-one row, so the libraries added after it (DCI_LIB / DCI_SOURCES / DCI_HEADERS, DIP_LIB / ...) stand there, same rows, same build path.  Its own
-test asserts that its row is IN the table, not what the table is: the next library is one more row of LATER_TARGETS.
 The libraries land in disentangling-vae_amd/lib/ (git-ignored build products).  Objects are rebuilt only
 when a source / header is newer or the flags changed.
 --debug (or DVAE_BUILD_DEBUG=1) adds -DDVAE_DEBUG_SWITCHES: the A/B / timing-ablation environment
@@ -30,7 +23,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 DEBUG_SOURCES = []          # experimental kernel files of the training library: only in --debug builds
-# (name, sources in csrc/, public header in include/): "" is the training library, the others are the evaluation-side libraries
+# (name, sources in csrc/, public header in include/): "" is the training library; the next library is one more row
 TARGETS = [
     ("", ["conv_generic", "conv_mfma", "conv_down_dma", "conv_up_ws", "conv_wgrad_ws", "conv_thin", "conv_thin_ws", "conv_up_thin_mm", "linear", "linear_narrow", "gemm_dma", "linear_grouped", "fc_chain", "stage", "loss",
           "latent_wide", "metrics", "adam", "comm", "viz", "loglik", "plan", "capi"], "dvae_hip.h"),
@@ -39,13 +32,7 @@ TARGETS = [
     ("info", ["factor_info"], "dvae_info_hip.h"),          # discretised MIG, modularity, SAP
     ("irs", ["factor_irs"], "dvae_irs_hip.h"),             # interventional robustness score
     ("unsup", ["latent_pairs"], "dvae_unsup_hip.h"),       # Gaussian total correlation, Wasserstein correlation, latent-latent mutual information
-]
-# libraries added since the pin on TARGETS (module docstring): the same rows, the same build path
-EXTRA_TARGETS = [
     ("udr", ["latent_ranks"], "dvae_udr_hip.h"),           # unsupervised disentanglement ranking: tie-averaged ranks, KL per dimension
-]
-# libraries added since the pin on EXTRA_TARGETS (module docstring): the same rows, the same build path; add rows here
-LATER_TARGETS = [
     ("dci", ["boosted_trees"], "dvae_dci_hip.h"),          # DCI: gradient-boosted trees fitted on the device, their importances
     ("dip", ["dip_cov"], "dvae_dip_hip.h"),                # DIP-VAE I / II: batch covariance, the regulariser and its gradients (a TRAINING loss)
 ]
@@ -59,7 +46,7 @@ def _target(name, sources, header):
     return os.path.join(HERE, "lib", "libdvae%s_hip.so" % infix), sources, headers, os.path.join(OBJ, "flags%s.txt" % infix)
 
 
-for _row in TARGETS + EXTRA_TARGETS + LATER_TARGETS:        # LIB / SOURCES / HEADERS of the training library, EVAL_LIB / EVAL_SOURCES / EVAL_HEADERS, ... of the others
+for _row in TARGETS:        # LIB / SOURCES / HEADERS of the training library, EVAL_LIB / EVAL_SOURCES / EVAL_HEADERS, ... of the others
     _prefix = _row[0].upper() + "_" if _row[0] else ""
     globals()[_prefix + "LIB"], globals()[_prefix + "SOURCES"], globals()[_prefix + "HEADERS"], _ = _target(*_row)
 ALL_SOURCES = [s for _, sources, _ in TARGETS for s in sources]
@@ -100,14 +87,14 @@ def _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose):
 
 
 def build(force=False, verbose=True, debug=None):
-    """Build every target of TARGETS, then of EXTRA_TARGETS, then of LATER_TARGETS; returns the path of libdvae_hip.so."""
+    """Build every target of TARGETS, in its order; returns the path of libdvae_hip.so."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if debug is None:
         debug = os.environ.get("DVAE_BUILD_DEBUG", "0") == "1"
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
     flags = FLAGS + (["-DDVAE_DEBUG_SWITCHES"] if debug else [])
-    for name, sources, header in TARGETS + EXTRA_TARGETS + LATER_TARGETS:
+    for name, sources, header in TARGETS:
         lib, sources, headers, stamp = _target(name, sources + (DEBUG_SOURCES if debug and not name else []), header)
         _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose)
     return LIB

@@ -1,12 +1,19 @@
-"""The one ctypes loader behind the score libraries' bindings (_evallib.py, _scorelib.py, _infolib.py, _irslib.py, _unsuplib.py).
+"""The one ctypes loader behind the bindings of every library but the training library's (_evallib.py, _scorelib.py, _infolib.py,
+_irslib.py, _unsuplib.py, _udrlib.py, _dcilib.py, _diplib.py).
 
-Each of those modules states what is its own -- path, mirrored constants, SIGNATURES, _RESTYPE -- and keeps a module-level
-lib() / call() pair in front of one Binding.  _lib.py (the training library, with plan recording) does not go through here.
+Each of those modules states what is its own -- its short name, mirrored constants, SIGNATURES, _RESTYPE -- and keeps a
+module-level LIB_PATH and lib() / call() pair in front of one Binding.for_library(name, ...), which derives the rest from the
+name: lib/libdvae_NAME_hip.so, its DVAE_NAME_HIP_LIB override and the dvae_NAME_last_error symbol.  _lib.py (the training
+library, with plan recording) does not go through here.
 """
 import ctypes
 import os
 
 from ._lib import DvaeHipError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+# the argument types of the SIGNATURES tables
+p, i, l, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_double      # noqa: E741
 
 
 class Binding:
@@ -15,6 +22,12 @@ class Binding:
         self.path, self.signatures, self.restype, self.last_error, self.kernels = path, signatures, restype, last_error, kernels
         self.soname = "lib%s_hip.so" % last_error[:-len("_last_error")]
         self._lib = None
+
+    @classmethod
+    def for_library(cls, name, signatures, restype, kernels):
+        """The binding of libdvae_NAME_hip.so in ../lib, or wherever the environment's DVAE_NAME_HIP_LIB says."""
+        path = os.environ.get("DVAE_%s_HIP_LIB" % name.upper(), os.path.join(_HERE, "..", "lib", "libdvae_%s_hip.so" % name))
+        return cls(path, signatures, restype, "dvae_%s_last_error" % name, kernels)
 
     def lib(self):
         """Load (once) and return the ctypes handle; raises if the library is absent."""

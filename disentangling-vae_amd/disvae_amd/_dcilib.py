@@ -3,18 +3,13 @@
 GradientBoostingClassifier with default arguments restated, fitted on a table of posterior means where it lies; their
 impurity-based feature importances and their raw scores on held-out rows.
 
-An eighth library next to libdvae_hip.so (_lib.py), libdvae_eval_hip.so (_evallib.py), libdvae_score_hip.so (_scorelib.py),
-libdvae_info_hip.so (_infolib.py), libdvae_irs_hip.so (_irslib.py), libdvae_unsup_hip.so (_unsuplib.py) and libdvae_udr_hip.so
-(_udrlib.py), loaded lazily on first use.  As there, the library is the product: no CPU or PyTorch fallback, a missing shared
-object or symbol fails loudly.  Calls go straight to the library -- they are never recorded into a launch plan.
+A library of its own next to libdvae_hip.so (_lib.py) and the other score libraries (one row each of build.py's TARGETS), loaded
+lazily on first use.  As there, the library is the product: no CPU or PyTorch fallback, a missing shared object or symbol fails
+loudly.  Calls go straight to the library -- they are never recorded into a launch plan.
 """
 import ctypes
-import os
 
-from ._cabi import Binding
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("DVAE_DCI_HIP_LIB", os.path.join(_HERE, "..", "lib", "libdvae_dci_hip.so"))
+from ._cabi import Binding, d as _d, i as _i, l as _l, p as _p
 
 VERSION = 1                  # DVAE_DCI_VERSION
 MAX_D = 64                   # DVAE_DCI_MAX_D: D above it is refused
@@ -29,11 +24,6 @@ NODE_STATS = 5               # DVAE_DCI_NODE_STATS: threshold, value, n, sum r, 
 LAUNCHES_PER_STAGE = 8       # DVAE_DCI_LAUNCHES_PER_STAGE
 LDS_BYTES = 160 * 1024       # of a CDNA4 compute unit: ROW_LDS_BYTES * MAX_ROWS + LDS_SCRATCH stays within it
 
-_p = ctypes.c_void_p
-_i = ctypes.c_int
-_l = ctypes.c_long
-_d = ctypes.c_double
-
 # name -> argtypes (all return int unless listed in _RESTYPE)
 SIGNATURES = {
     "dvae_dci_version": [],
@@ -45,7 +35,8 @@ SIGNATURES = {
 }
 _RESTYPE = {"dvae_dci_last_error": ctypes.c_char_p, "dvae_dci_fit_ws_floats": ctypes.c_size_t}
 
-_binding = Binding(LIB_PATH, SIGNATURES, _RESTYPE, "dvae_dci_last_error", "boosted-tree")
+_binding = Binding.for_library("dci", SIGNATURES, _RESTYPE, "boosted-tree")
+LIB_PATH = _binding.path       # DVAE_DCI_HIP_LIB overrides it
 
 
 def trees(C):

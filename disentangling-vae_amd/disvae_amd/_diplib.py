@@ -2,29 +2,20 @@
 training losses (Kumar et al. 2018 in disentanglement_lib's form) -- the biased covariance of a batch of posterior means, the
 regulariser that pulls it towards the identity, and its gradients with respect to the means and the log-variances.
 
-A ninth library next to libdvae_hip.so (_lib.py) and the seven score libraries, loaded lazily on first use.  As there, the
-library is the product: no CPU or PyTorch fallback, a missing shared object or symbol fails loudly.  Unlike the score libraries
-this one takes part in the training step: models/losses.py issues its launches through _lib.record_py, so a recorded plan
-re-issues them and a hipGraph captures them like any launch.
+A library of its own next to libdvae_hip.so (_lib.py) and the score libraries (one row each of build.py's TARGETS), loaded
+lazily on first use.  As there, the library is the product: no CPU or PyTorch fallback, a missing shared object or symbol fails
+loudly.  Unlike the score libraries this one takes part in the training step: models/losses.py issues its launches through
+_lib.record_py, so a recorded plan re-issues them and a hipGraph captures them like any launch.
 """
 import ctypes
-import os
 
-from ._cabi import Binding
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("DVAE_DIP_HIP_LIB", os.path.join(_HERE, "..", "lib", "libdvae_dip_hip.so"))
+from ._cabi import Binding, d as _d, i as _i, l as _l, p as _p
 
 VERSION = 1                  # DVAE_DIP_VERSION
 MAX_D = 128                  # DVAE_DIP_MAX_D: D above it is refused
 THREADS = 256                # DVAE_DIP_THREADS: a workgroup
 BLOCK_ROWS = 32              # DVAE_DIP_BLOCK_ROWS: rows of one trip; ceil(B / BLOCK_ROWS) workgroups ...
 MAX_GROUPS = 64              # DVAE_DIP_MAX_GROUPS: ... at most; above BLOCK_ROWS * MAX_GROUPS rows a workgroup makes several trips
-
-_p = ctypes.c_void_p
-_i = ctypes.c_int
-_l = ctypes.c_long
-_d = ctypes.c_double
 
 # name -> argtypes (all return int unless listed in _RESTYPE)
 SIGNATURES = {
@@ -36,7 +27,8 @@ SIGNATURES = {
 }
 _RESTYPE = {"dvae_dip_last_error": ctypes.c_char_p, "dvae_dip_ws_doubles": ctypes.c_size_t}
 
-_binding = Binding(LIB_PATH, SIGNATURES, _RESTYPE, "dvae_dip_last_error", "DIP-VAE")
+_binding = Binding.for_library("dip", SIGNATURES, _RESTYPE, "DIP-VAE")
+LIB_PATH = _binding.path       # DVAE_DIP_HIP_LIB overrides it
 
 
 def groups(B):

@@ -5,20 +5,12 @@ or PyTorch fallback, a missing shared object or symbol fails loudly.  Calls go s
 recorded into a launch plan (graph.py replays the training step only).
 """
 import ctypes
-import os
 
-from ._cabi import Binding
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("DVAE_EVAL_HIP_LIB", os.path.join(_HERE, "..", "lib", "libdvae_eval_hip.so"))
+from ._cabi import Binding, i as _i, l as _l, p as _p
 
 VERSION = 1                  # DVAE_EVAL_VERSION
 JOINT_CHUNK = 2048           # DVAE_EVAL_JOINT_CHUNK: data points per workgroup of the joint log-density kernel (at least)
 JOINT_MAX_CHUNKS = 256       # DVAE_EVAL_JOINT_MAX_CHUNKS
-
-_p = ctypes.c_void_p
-_i = ctypes.c_int
-_l = ctypes.c_long
 
 # name -> argtypes (all return int unless listed in _RESTYPE)
 SIGNATURES = {
@@ -30,7 +22,8 @@ SIGNATURES = {
 }
 _RESTYPE = {"dvae_eval_last_error": ctypes.c_char_p, "dvae_eval_joint_logq_ws_floats": ctypes.c_size_t}
 
-_binding = Binding(LIB_PATH, SIGNATURES, _RESTYPE, "dvae_eval_last_error", "evaluation")
+_binding = Binding.for_library("eval", SIGNATURES, _RESTYPE, "evaluation")
+LIB_PATH = _binding.path       # DVAE_EVAL_HIP_LIB overrides it
 
 
 def lib():

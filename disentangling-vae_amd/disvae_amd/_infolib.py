@@ -7,12 +7,8 @@ fails loudly.  Calls go straight to the library -- they are never recorded into 
 step only).
 """
 import ctypes
-import os
 
-from ._cabi import Binding
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("DVAE_INFO_HIP_LIB", os.path.join(_HERE, "..", "lib", "libdvae_info_hip.so"))
+from ._cabi import Binding, i as _i, l as _l, p as _p
 
 VERSION = 1                  # DVAE_INFO_VERSION
 MAX_FACTORS = 8              # DVAE_INFO_MAX_FACTORS: K above it is refused
@@ -22,10 +18,6 @@ MOMENTS_BLOCK_ROWS = 1024    # DVAE_INFO_MOMENTS_BLOCK_ROWS: rows of one workgro
 HIST_BLOCK_ROWS = 4096       # DVAE_INFO_HIST_BLOCK_ROWS: ... and of the histogram pass,
 MAX_BLOCKS = 1024            # DVAE_INFO_MAX_BLOCKS: until that many workgroups (per latent) are reached; then the chunks grow
 HIST_LDS_INTS = 8192         # DVAE_INFO_HIST_LDS_INTS: the most n_bins * sum(lat_sizes) counters that are kept in LDS
-
-_p = ctypes.c_void_p
-_i = ctypes.c_int
-_l = ctypes.c_long
 
 # name -> argtypes (all return int unless listed in _RESTYPE)
 SIGNATURES = {
@@ -39,7 +31,8 @@ SIGNATURES = {
 _RESTYPE = {"dvae_info_last_error": ctypes.c_char_p, "dvae_info_moments_ws_floats": ctypes.c_size_t,
             "dvae_info_hist_ws_floats": ctypes.c_size_t}
 
-_binding = Binding(LIB_PATH, SIGNATURES, _RESTYPE, "dvae_info_last_error", "information-score")
+_binding = Binding.for_library("info", SIGNATURES, _RESTYPE, "information-score")
+LIB_PATH = _binding.path       # DVAE_INFO_HIP_LIB overrides it
 
 
 def lib():

@@ -8,12 +8,8 @@ a missing shared object or symbol fails loudly.  Calls go straight to the librar
 (graph.py replays the training step only).
 """
 import ctypes
-import os
 
-from ._cabi import Binding
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("DVAE_IRS_HIP_LIB", os.path.join(_HERE, "..", "lib", "libdvae_irs_hip.so"))
+from ._cabi import Binding, i as _i, l as _l, p as _p
 
 VERSION = 1                  # DVAE_IRS_VERSION
 MAX_FACTORS = 8              # DVAE_IRS_MAX_FACTORS: K above it is refused
@@ -25,10 +21,6 @@ MAX_BLOCKS = 512             # DVAE_IRS_MAX_BLOCKS: until that many chunks are r
 SELECT_LDS_GROUPS = 40       # DVAE_IRS_SELECT_LDS_GROUPS: groups of one factor whose digit histograms one workgroup keeps in LDS
 SELECT_PASSES = 4            # DVAE_IRS_SELECT_PASSES: 8-bit passes of the radix select
 MAX_PAIRS = 4194304          # DVAE_IRS_MAX_PAIRS: the most total_groups * D
-
-_p = ctypes.c_void_p
-_i = ctypes.c_int
-_l = ctypes.c_long
 
 # name -> argtypes (all return int unless listed in _RESTYPE)
 SIGNATURES = {
@@ -42,7 +34,8 @@ SIGNATURES = {
 _RESTYPE = {"dvae_irs_last_error": ctypes.c_char_p, "dvae_irs_group_means_ws_floats": ctypes.c_size_t,
             "dvae_irs_group_order_stats_ws_floats": ctypes.c_size_t}
 
-_binding = Binding(LIB_PATH, SIGNATURES, _RESTYPE, "dvae_irs_last_error", "interventional-robustness")
+_binding = Binding.for_library("irs", SIGNATURES, _RESTYPE, "interventional-robustness")
+LIB_PATH = _binding.path       # DVAE_IRS_HIP_LIB overrides it
 
 
 def lib():

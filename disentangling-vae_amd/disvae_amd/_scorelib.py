@@ -6,20 +6,12 @@ the library is the product: no CPU or PyTorch fallback, a missing shared object 
 the library -- they are never recorded into a launch plan (graph.py replays the training step only).
 """
 import ctypes
-import os
 
-from ._cabi import Binding
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("DVAE_SCORE_HIP_LIB", os.path.join(_HERE, "..", "lib", "libdvae_score_hip.so"))
+from ._cabi import Binding, i as _i, l as _l, p as _p
 
 VERSION = 1                  # DVAE_SCORE_VERSION
 WAVE_MAX_L = 256             # DVAE_SCORE_WAVE_MAX_L: the longest group that one wave reduces (longer: a whole workgroup)
 VOTE_LDS_BINS = 8192         # DVAE_SCORE_VOTE_LDS_BINS: the most K * D vote counters that are counted in LDS
-
-_p = ctypes.c_void_p
-_i = ctypes.c_int
-_l = ctypes.c_long
 
 # name -> argtypes (all return int unless listed in _RESTYPE)
 SIGNATURES = {
@@ -32,7 +24,8 @@ SIGNATURES = {
 }
 _RESTYPE = {"dvae_score_last_error": ctypes.c_char_p, "dvae_score_group_var_ws_floats": ctypes.c_size_t}
 
-_binding = Binding(LIB_PATH, SIGNATURES, _RESTYPE, "dvae_score_last_error", "score")
+_binding = Binding.for_library("score", SIGNATURES, _RESTYPE, "score")
+LIB_PATH = _binding.path       # DVAE_SCORE_HIP_LIB overrides it
 
 
 def lib():

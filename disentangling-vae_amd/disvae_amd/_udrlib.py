@@ -8,12 +8,8 @@ use.  As there, the library is the product: no CPU or PyTorch fallback, a missin
 straight to the library -- they are never recorded into a launch plan (graph.py replays the training step only).
 """
 import ctypes
-import os
 
-from ._cabi import Binding
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("DVAE_UDR_HIP_LIB", os.path.join(_HERE, "..", "lib", "libdvae_udr_hip.so"))
+from ._cabi import Binding, i as _i, l as _l, p as _p
 
 VERSION = 1                  # DVAE_UDR_VERSION
 MAX_D = 64                   # DVAE_UDR_MAX_D: D above it is refused
@@ -23,10 +19,6 @@ CHUNK_ROWS = 2048            # DVAE_UDR_CHUNK_ROWS: above, rows of one workgroup
 MAX_CHUNKS = 256             # DVAE_UDR_MAX_CHUNKS: until that many chunks (per column) are reached; then the chunks grow
 KL_BLOCK_ROWS = 64           # DVAE_UDR_KL_BLOCK_ROWS: rows one thread of the KL pass adds in order,
 KL_MAX_CHUNKS = 4096         # DVAE_UDR_KL_MAX_CHUNKS: until that many chunks are reached; then they grow
-
-_p = ctypes.c_void_p
-_i = ctypes.c_int
-_l = ctypes.c_long
 
 # name -> argtypes (all return int unless listed in _RESTYPE)
 SIGNATURES = {
@@ -40,7 +32,8 @@ SIGNATURES = {
 _RESTYPE = {"dvae_udr_last_error": ctypes.c_char_p, "dvae_udr_ranks_ws_floats": ctypes.c_size_t,
             "dvae_udr_kl_dims_ws_floats": ctypes.c_size_t}
 
-_binding = Binding(LIB_PATH, SIGNATURES, _RESTYPE, "dvae_udr_last_error", "ranking")
+_binding = Binding.for_library("udr", SIGNATURES, _RESTYPE, "ranking")
+LIB_PATH = _binding.path       # DVAE_UDR_HIP_LIB overrides it
 
 
 def lib():

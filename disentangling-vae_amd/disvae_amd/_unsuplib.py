@@ -8,12 +8,8 @@ product: no CPU or PyTorch fallback, a missing shared object or symbol fails lou
 are never recorded into a launch plan (graph.py replays the training step only).
 """
 import ctypes
-import os
 
-from ._cabi import Binding
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("DVAE_UNSUP_HIP_LIB", os.path.join(_HERE, "..", "lib", "libdvae_unsup_hip.so"))
+from ._cabi import Binding, i as _i, l as _l, p as _p
 
 VERSION = 1                  # DVAE_UNSUP_VERSION
 MAX_D = 64                   # DVAE_UNSUP_MAX_D: D above it is refused
@@ -23,10 +19,6 @@ HIST_BLOCK_ROWS = 4096       # DVAE_UNSUP_HIST_BLOCK_ROWS: ... and of the histog
 MAX_BLOCKS = 1024            # DVAE_UNSUP_MAX_BLOCKS: until that many workgroups (per tile of pairs) are reached; then the chunks grow
 MOMENTS_THREAD_SUMS = 9      # DVAE_UNSUP_MOMENTS_THREAD_SUMS: sums one thread of the moments pass keeps at most (256 threads)
 HIST_LDS_INTS = 4096         # DVAE_UNSUP_HIST_LDS_INTS: the counters of one tile of pairs, n_bins^2 per pair, one pair at least
-
-_p = ctypes.c_void_p
-_i = ctypes.c_int
-_l = ctypes.c_long
 
 # name -> argtypes (all return int unless listed in _RESTYPE)
 SIGNATURES = {
@@ -40,7 +32,8 @@ SIGNATURES = {
 _RESTYPE = {"dvae_unsup_last_error": ctypes.c_char_p, "dvae_unsup_moments_ws_floats": ctypes.c_size_t,
             "dvae_unsup_pair_hist_ws_floats": ctypes.c_size_t}
 
-_binding = Binding(LIB_PATH, SIGNATURES, _RESTYPE, "dvae_unsup_last_error", "label-free score")
+_binding = Binding.for_library("unsup", SIGNATURES, _RESTYPE, "label-free score")
+LIB_PATH = _binding.path       # DVAE_UNSUP_HIP_LIB overrides it
 
 
 def lib():

@@ -105,76 +105,45 @@ class Evaluator:
         start = default_timer()
         is_still_training = self.model.training
         self.model.eval()
-        metric, losses = None, None
-        if is_metrics:
-            self.logger.info('Computing metrics...')
-            metrics = self.compute_metrics(data_loader)
-            self.logger.info('Losses: {}'.format(metrics))
+        matrices, nothing = (lambda k, v: isinstance(v, np.ndarray) and v.ndim > 1), (lambda k, v: False)
+        # (wanted, what is being computed, the call, what the log and the file leave out (None: the result as it is; else the
+        # arrays that stay become lists), the label of the result line, the file)
+        outputs = [
+            (is_metrics, 'metrics', lambda: self.compute_metrics(data_loader), None, 'Losses', METRICS_FILENAME),
+            (is_losses, 'losses', lambda: self.compute_losses(data_loader), None, 'Losses', TEST_LOSSES_FILE),
+            (is_log_likelihood, 'the importance-weighted log-likelihood',
+             lambda: self.compute_log_likelihood(data_loader, n_samples=n_samples), None, 'Log-likelihood', LOG_LIKELIHOOD_FILE),
+            (is_decomposition, 'the ELBO decomposition over the data set',
+             lambda: self.compute_elbo_decomposition(data_loader, n_samples=n_samples_decomposition), None, 'ELBO decomposition',
+             ELBO_DECOMPOSITION_FILE),
+            (is_scores, 'the FactorVAE and beta-VAE scores', lambda: self.compute_factor_scores(data_loader), None,
+             'Disentanglement scores', FACTOR_SCORES_FILE),
+            (is_information, 'the discretised MIG, modularity and SAP scores', lambda: self.compute_information_scores(data_loader),
+             matrices, 'Information scores', INFORMATION_SCORES_FILE),
+            (is_irs, 'the interventional robustness score', lambda: self.compute_irs(data_loader), nothing, 'IRS', IRS_FILE),
+            (is_unsupervised, 'the label-free scores', lambda: self.compute_unsupervised_scores(data_loader), matrices,
+             'Unsupervised scores', UNSUPERVISED_SCORES_FILE),
+            (udr_models is not None, 'the unsupervised disentanglement ranking', lambda: self.compute_udr(data_loader, udr_models),
+             lambda k, v: k == "raw_correlations", 'UDR', UDR_FILE),
+            (is_dci, 'the DCI scores', lambda: self.compute_dci(data_loader, **(dci_args or {})),
+             lambda k, v: isinstance(v, np.ndarray), 'DCI', DCI_FILE),
+        ]
+        written = {}
+        for wanted, what, compute, left_out, label, filename in outputs:
+            if not wanted:
+                continue
+            self.logger.info('Computing {}...'.format(what))
+            result = compute()
+            if left_out is not None:
+                result = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in result.items() if not left_out(k, v)}
+            self.logger.info('{}: {}'.format(label, result))
             os.makedirs(self.save_dir, exist_ok=True)
-            save_metadata(metrics, self.save_dir, filename=METRICS_FILENAME)
-        if is_losses:
-            self.logger.info('Computing losses...')
-            losses = self.compute_losses(data_loader)
-            self.logger.info('Losses: {}'.format(losses))
-            os.makedirs(self.save_dir, exist_ok=True)
-            save_metadata(losses, self.save_dir, filename=TEST_LOSSES_FILE)
-        if is_log_likelihood:
-            self.logger.info('Computing the importance-weighted log-likelihood...')
-            ll = self.compute_log_likelihood(data_loader, n_samples=n_samples)
-            self.logger.info('Log-likelihood: {}'.format(ll))
-            os.makedirs(self.save_dir, exist_ok=True)
-            save_metadata(ll, self.save_dir, filename=LOG_LIKELIHOOD_FILE)
-        if is_decomposition:
-            self.logger.info('Computing the ELBO decomposition over the data set...')
-            dec = self.compute_elbo_decomposition(data_loader, n_samples=n_samples_decomposition)
-            self.logger.info('ELBO decomposition: {}'.format(dec))
-            os.makedirs(self.save_dir, exist_ok=True)
-            save_metadata(dec, self.save_dir, filename=ELBO_DECOMPOSITION_FILE)
-        if is_scores:
-            self.logger.info('Computing the FactorVAE and beta-VAE scores...')
-            scores = self.compute_factor_scores(data_loader)
-            self.logger.info('Disentanglement scores: {}'.format(scores))
-            os.makedirs(self.save_dir, exist_ok=True)
-            save_metadata(scores, self.save_dir, filename=FACTOR_SCORES_FILE)
-        if is_information:
-            self.logger.info('Computing the discretised MIG, modularity and SAP scores...')
-            info = self.compute_information_scores(data_loader)
-            info = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in info.items()
-                    if not (isinstance(v, np.ndarray) and v.ndim > 1)}
-            self.logger.info('Information scores: {}'.format(info))
-            os.makedirs(self.save_dir, exist_ok=True)
-            save_metadata(info, self.save_dir, filename=INFORMATION_SCORES_FILE)
-        if is_irs:
-            self.logger.info('Computing the interventional robustness score...')
-            irs = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in self.compute_irs(data_loader).items()}
-            self.logger.info('IRS: {}'.format(irs))
-            os.makedirs(self.save_dir, exist_ok=True)
-            save_metadata(irs, self.save_dir, filename=IRS_FILE)
-        if is_unsupervised:
-            self.logger.info('Computing the label-free scores...')
-            unsup = self.compute_unsupervised_scores(data_loader)
-            unsup = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in unsup.items()
-                     if not (isinstance(v, np.ndarray) and v.ndim > 1)}
-            self.logger.info('Unsupervised scores: {}'.format(unsup))
-            os.makedirs(self.save_dir, exist_ok=True)
-            save_metadata(unsup, self.save_dir, filename=UNSUPERVISED_SCORES_FILE)
-        if udr_models is not None:
-            self.logger.info('Computing the unsupervised disentanglement ranking...')
-            udr = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in self.compute_udr(data_loader, udr_models).items()
-                   if k != "raw_correlations"}
-            self.logger.info('UDR: {}'.format(udr))
-            os.makedirs(self.save_dir, exist_ok=True)
-            save_metadata(udr, self.save_dir, filename=UDR_FILE)
-        if is_dci:
-            self.logger.info('Computing the DCI scores...')
-            dci = {k: v for k, v in self.compute_dci(data_loader, **(dci_args or {})).items() if not isinstance(v, np.ndarray)}
-            self.logger.info('DCI: {}'.format(dci))
-            os.makedirs(self.save_dir, exist_ok=True)
-            save_metadata(dci, self.save_dir, filename=DCI_FILE)
+            save_metadata(result, self.save_dir, filename=filename)
+            written[filename] = result
         if is_still_training:
             self.model.train()
         self.logger.info('Finished evaluating after {:.1f} min.'.format((default_timer() - start) / 60))
-        return metric, losses
+        return None, written.get(TEST_LOSSES_FILE)       # (metric, losses) of the reference; metric stays None, also with is_metrics
 
     def compute_losses(self, dataloader):
         """evaluate.py:97-117."""
@@ -242,13 +211,7 @@ class Evaluator:
             raise ValueError("eps must have shape (%d, %d), got %s" % (S, dim, tuple(eps.shape)))
         if sample_idx is not None and not (0 <= int(sample_idx.min()) and int(sample_idx.max()) < n):
             raise ValueError("sample_idx must hold rows in [0, %d)" % n)            # (the kernels do not check them)
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            table = _LatentTable(*self._encode_dataset(dataloader))
-        finally:
-            if was_training:
-                self.model.train()
+        table = _LatentTable(*self._encode(dataloader))
         if table.n != n:
             raise ValueError("the loader yielded %d images, its data set has %d" % (table.n, n))
         dev = table.mean.device
@@ -297,24 +260,9 @@ class Evaluator:
         ``lat_names``, the loader iterates the data set in factor order and the data set enumerates ``lat_sizes``.  Every size
         is checked before any device work; train / eval mode is restored.  Returns {"factor_vae_train", "factor_vae_eval",
         "beta_vae_train", "beta_vae_eval", "n_active", "n_train", "n_eval", "batch_size"}."""
-        ds = getattr(dataloader, "dataset", None)
-        if not (hasattr(ds, "lat_sizes") and hasattr(ds, "lat_names")):
-            raise ValueError("Dataset needs to have known true factors of variations to compute the metric. This does not "
-                             "seem to be the case for {}".format(type(ds).__name__))
-        lat_sizes = [int(k) for k in ds.lat_sizes]
-        n = int(np.prod(lat_sizes))
+        _ds, lat_sizes, n = self._factor_sizes(dataloader)
         _check_score_sizes(n, lat_sizes, n_train, n_eval, batch_size, n_variance)
-        if hasattr(ds, "__len__") and len(ds) != n:
-            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (len(ds), lat_sizes))
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            mean, _logvar = self._encode_dataset(dataloader)
-        finally:
-            if was_training:
-                self.model.train()
-        if mean.shape[0] != n:
-            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (mean.shape[0], lat_sizes))
+        mean, _logvar = self._encode(dataloader, n, lat_sizes)
         return factor_scores_from_table(mean, lat_sizes, n_train=n_train, n_eval=n_eval, batch_size=batch_size,
                                         n_variance=n_variance, active_threshold=active_threshold, seed=seed, draws=draws)
 
@@ -323,24 +271,9 @@ class Evaluator:
         """Discretised MIG, modularity and continuous-factor SAP of the model (information_scores_from_table below, on the
         posterior means of the whole data set through the native encoder).  The data-set requirements and errors of
         compute_factor_scores; every size is checked before any device work; train / eval mode is restored."""
-        ds = getattr(dataloader, "dataset", None)
-        if not (hasattr(ds, "lat_sizes") and hasattr(ds, "lat_names")):
-            raise ValueError("Dataset needs to have known true factors of variations to compute the metric. This does not "
-                             "seem to be the case for {}".format(type(ds).__name__))
-        lat_sizes = [int(k) for k in ds.lat_sizes]
-        n = int(np.prod(lat_sizes)) if lat_sizes else 0
+        _ds, lat_sizes, n = self._factor_sizes(dataloader)
         _check_information_sizes(n, lat_sizes, n_bins, n_samples)
-        if hasattr(ds, "__len__") and len(ds) != n:
-            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (len(ds), lat_sizes))
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            mean, _logvar = self._encode_dataset(dataloader)
-        finally:
-            if was_training:
-                self.model.train()
-        if mean.shape[0] != n:
-            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (mean.shape[0], lat_sizes))
+        mean, _logvar = self._encode(dataloader, n, lat_sizes)
         return information_scores_from_table(mean, lat_sizes, n_bins=n_bins, n_samples=n_samples, seed=seed)
 
     # ------------------------------------------------------------------ interventional robustness score
@@ -348,24 +281,9 @@ class Evaluator:
         """Interventional robustness score of the model (irs_from_table below, on the posterior means of the whole data set
         through the native encoder).  The data-set requirements and errors of compute_factor_scores; every size and argument is
         checked before any device work; train / eval mode is restored."""
-        ds = getattr(dataloader, "dataset", None)
-        if not (hasattr(ds, "lat_sizes") and hasattr(ds, "lat_names")):
-            raise ValueError("Dataset needs to have known true factors of variations to compute the metric. This does not "
-                             "seem to be the case for {}".format(type(ds).__name__))
-        lat_sizes = [int(k) for k in ds.lat_sizes]
-        n = int(np.prod(lat_sizes)) if lat_sizes else 0
+        _ds, lat_sizes, n = self._factor_sizes(dataloader)
         _check_irs_arguments(n, lat_sizes, diff_quantile, factor_bins, n_samples)
-        if hasattr(ds, "__len__") and len(ds) != n:
-            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (len(ds), lat_sizes))
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            mean, _logvar = self._encode_dataset(dataloader)
-        finally:
-            if was_training:
-                self.model.train()
-        if mean.shape[0] != n:
-            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (mean.shape[0], lat_sizes))
+        mean, _logvar = self._encode(dataloader, n, lat_sizes)
         return irs_from_table(mean, lat_sizes, diff_quantile=diff_quantile, factor_bins=factor_bins, n_samples=n_samples, seed=seed)
 
     # ------------------------------------------------------------------ label-free scores
@@ -376,13 +294,7 @@ class Evaluator:
         work; train / eval mode is restored."""
         ds = getattr(dataloader, "dataset", None)
         _check_unsupervised_arguments(len(ds) if hasattr(ds, "__len__") else None, None, n_bins, n_samples)
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            mean, _logvar = self._encode_dataset(dataloader)
-        finally:
-            if was_training:
-                self.model.train()
+        mean, _logvar = self._encode(dataloader)
         return unsupervised_scores_from_table(mean, n_bins=n_bins, n_samples=n_samples, seed=seed)
 
     # ------------------------------------------------------------------ unsupervised disentanglement ranking
@@ -418,24 +330,9 @@ class Evaluator:
         """Disentanglement, completeness and informativeness of the model (dci_from_table below, on the posterior means of the
         whole data set through the native encoder).  The data-set requirements and errors of compute_factor_scores; every size and
         argument is checked before any device work; train / eval mode is restored."""
-        ds = getattr(dataloader, "dataset", None)
-        if not (hasattr(ds, "lat_sizes") and hasattr(ds, "lat_names")):
-            raise ValueError("Dataset needs to have known true factors of variations to compute the metric. This does not "
-                             "seem to be the case for {}".format(type(ds).__name__))
-        lat_sizes = [int(k) for k in ds.lat_sizes]
-        n = int(np.prod(lat_sizes)) if lat_sizes else 0
+        _ds, lat_sizes, n = self._factor_sizes(dataloader)
         _check_dci_arguments(n, None, lat_sizes, n_train, n_test, seed, None, n_stages)
-        if hasattr(ds, "__len__") and len(ds) != n:
-            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (len(ds), lat_sizes))
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            mean, _logvar = self._encode_dataset(dataloader)
-        finally:
-            if was_training:
-                self.model.train()
-        if mean.shape[0] != n:
-            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (mean.shape[0], lat_sizes))
+        mean, _logvar = self._encode(dataloader, n, lat_sizes)
         return dci_from_table(mean, lat_sizes, n_train=n_train, n_test=n_test, seed=seed, n_stages=n_stages)
 
     # ------------------------------------------------------------------ MIG / AAM (evaluate.py:119-317)
@@ -446,17 +343,11 @@ class Evaluator:
         ``{'MIG': ..., 'AAM': ...}`` and writes the reference's ``metric_helpers.pth``.
         sample_idx: optional sequence of injected ``randperm`` draws (parity tests): the marginal one first, then one per
         (factor, value) in the reference's loop order."""
-        ds = dataloader.dataset
-        if not (hasattr(ds, "lat_sizes") and hasattr(ds, "lat_names")):
-            raise ValueError("Dataset needs to have known true factors of variations to compute the metric. This does not "
-                             "seem to be the case for {}".format(type(ds).__name__))
-        lat_sizes = [int(k) for k in ds.lat_sizes]
+        ds, lat_sizes, n = self._factor_sizes(dataloader)
         draws = iter(sample_idx) if sample_idx is not None else None
         take = (lambda: None) if draws is None else (lambda: next(draws))
         self.logger.info("Computing the empirical distribution q(z|x).")
-        table = _LatentTable(*self._encode_dataset(dataloader))
-        if table.n != int(np.prod(lat_sizes)):
-            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (table.n, lat_sizes))
+        table = _LatentTable(*self._encode(dataloader, n, lat_sizes))
         self.logger.info("Estimating the marginal entropy.")
         H_z = self._entropies(table, None, n_samples, take())                      # H[z_j]                 [D]
         H_zCv = torch.zeros(len(lat_sizes), table.dim, device=self.device)         # H[z_j | v_k]           [K, D]
@@ -469,6 +360,34 @@ class Evaluator:
         os.makedirs(self.save_dir, exist_ok=True)
         torch.save(scores, os.path.join(self.save_dir, METRIC_HELPERS_FILE))        # same keys as evaluate.py:151-156
         return {'MIG': scores["mig"].item(), 'AAM': scores["aam"].item()}
+
+    @staticmethod
+    def _factor_sizes(dataloader):
+        """(data set, lat_sizes as ints, the number of images a data set that enumerates them holds) of a loader whose data set
+        has known factors of variation."""
+        ds = getattr(dataloader, "dataset", None)
+        if not (hasattr(ds, "lat_sizes") and hasattr(ds, "lat_names")):
+            raise ValueError("Dataset needs to have known true factors of variations to compute the metric. This does not "
+                             "seem to be the case for {}".format(type(ds).__name__))
+        lat_sizes = [int(k) for k in ds.lat_sizes]
+        return ds, lat_sizes, int(np.prod(lat_sizes))            # (no factor: 1; every _check_* refuses that before it reads n)
+
+    def _encode(self, dataloader, n=None, lat_sizes=None):
+        """_encode_dataset in eval mode, train / eval mode restored.  n: the data set must tell that length, where it tells one
+        (checked before the encoder runs), and the loader must yield that many images."""
+        ds = getattr(dataloader, "dataset", None)
+        if n is not None and hasattr(ds, "__len__") and len(ds) != n:
+            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (len(ds), lat_sizes))
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            mean, logvar = self._encode_dataset(dataloader)
+        finally:
+            if was_training:
+                self.model.train()
+        if n is not None and mean.shape[0] != n:
+            raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (mean.shape[0], lat_sizes))
+        return mean, logvar
 
     def _encode_dataset(self, dataloader):
         """(mean, logvar) of q(z|x) for every image of the data set, [N, D] each on the device, through the native encoder
@@ -539,10 +458,22 @@ def disentanglement_scores(H_z, H_zCv, lat_sizes):
             "aam_k": aam_k, "aam": aam_k.mean()}
 
 
-# ---------------------------------------------------------------------- FactorVAE / beta-VAE scores on a table of means
-def _check_score_sizes(n, lat_sizes, n_train, n_eval, batch_size, n_variance):
+# ---------------------------------------------------------------------- lines that the _check_* functions below share
+def _check_lat_sizes(lat_sizes, max_factors=None):
     if len(lat_sizes) < 1 or min(lat_sizes) < 1:
         raise ValueError("lat_sizes must hold positive sizes, got %s" % (lat_sizes,))
+    if max_factors is not None and len(lat_sizes) > max_factors:
+        raise ValueError("%d factors of variation: the kernels take at most %d" % (len(lat_sizes), max_factors))
+
+
+def _check_n_samples(n, n_samples):
+    if n_samples is not None and not 1 <= int(n_samples) <= n:
+        raise ValueError("n_samples must lie in [1, %d] (rows are drawn without replacement) or be None, got %r" % (n, n_samples))
+
+
+# ---------------------------------------------------------------------- FactorVAE / beta-VAE scores on a table of means
+def _check_score_sizes(n, lat_sizes, n_train, n_eval, batch_size, n_variance):
+    _check_lat_sizes(lat_sizes)
     if max(lat_sizes) < 2:
         raise ValueError("no factor of variation takes two values or more: lat_sizes=%s" % (lat_sizes,))
     if int(n_train) < 1 or int(n_eval) < 1:
@@ -791,16 +722,12 @@ def mutual_information_from_counts(block):
 
 # ---------------------------------------------------------------------- discretised MIG / modularity / SAP on a table of means
 def _check_information_sizes(n, lat_sizes, n_bins, n_samples):
-    if len(lat_sizes) < 1 or min(lat_sizes) < 1:
-        raise ValueError("lat_sizes must hold positive sizes, got %s" % (lat_sizes,))
-    if len(lat_sizes) > _infolib.MAX_FACTORS:
-        raise ValueError("%d factors of variation: the kernels take at most %d" % (len(lat_sizes), _infolib.MAX_FACTORS))
+    _check_lat_sizes(lat_sizes, _infolib.MAX_FACTORS)
     if not 1 <= int(n_bins) <= _infolib.MAX_BINS:
         raise ValueError("n_bins must lie in [1, %d], got %r" % (_infolib.MAX_BINS, n_bins))
     if min(lat_sizes) < 2:
         raise ValueError("a factor of variation with one value has no entropy (the MIG divides by it): lat_sizes=%s" % (lat_sizes,))
-    if n_samples is not None and not 1 <= int(n_samples) <= n:
-        raise ValueError("n_samples must lie in [1, %d] (rows are drawn without replacement) or be None, got %r" % (n, n_samples))
+    _check_n_samples(n, n_samples)
 
 
 def histogram_edges(lo, hi, n_bins):
@@ -919,10 +846,7 @@ def irs_group_map(lat_sizes, factor_bins=20):
 
 
 def _check_irs_arguments(n, lat_sizes, diff_quantile, factor_bins, n_samples):
-    if len(lat_sizes) < 1 or min(lat_sizes) < 1:
-        raise ValueError("lat_sizes must hold positive sizes, got %s" % (lat_sizes,))
-    if len(lat_sizes) > _irslib.MAX_FACTORS:
-        raise ValueError("%d factors of variation: the kernels take at most %d" % (len(lat_sizes), _irslib.MAX_FACTORS))
+    _check_lat_sizes(lat_sizes, _irslib.MAX_FACTORS)
     if not 0.0 <= float(diff_quantile) <= 1.0:
         raise ValueError("diff_quantile must lie in [0, 1], got %r" % (diff_quantile,))
     if factor_bins is not None and int(factor_bins) < 1:
@@ -930,8 +854,7 @@ def _check_irs_arguments(n, lat_sizes, diff_quantile, factor_bins, n_samples):
     most = max(lat_sizes) if factor_bins is None else min(max(lat_sizes), int(factor_bins))
     if most > _irslib.MAX_GROUPS:
         raise ValueError("%d groups of one factor: the kernels take at most %d (use factor_bins)" % (most, _irslib.MAX_GROUPS))
-    if n_samples is not None and not 1 <= int(n_samples) <= n:
-        raise ValueError("n_samples must lie in [1, %d] (rows are drawn without replacement) or be None, got %r" % (n, n_samples))
+    _check_n_samples(n, n_samples)
 
 
 def irs_quantile_ranks(counts, diff_quantile):
@@ -1049,8 +972,7 @@ def _check_unsupervised_arguments(n, dim, n_bins, n_samples):
     if n is not None:
         if n < 1:
             raise ValueError("the table of means must hold one row or more")
-        if n_samples is not None and int(n_samples) > n:
-            raise ValueError("n_samples must lie in [1, %d] (rows are drawn without replacement) or be None, got %r" % (n, n_samples))
+        _check_n_samples(n, n_samples)
     if dim is not None and not 1 <= dim <= _unsuplib.MAX_D:
         raise ValueError("mean must have between 1 and %d latent dimensions, got %d" % (_unsuplib.MAX_D, dim))
 
@@ -1167,8 +1089,8 @@ def _check_udr_arguments(n_models, n, dim, correlation="spearman", n_samples=Non
     if n is not None:
         if n < 1:
             raise ValueError("the tables must hold one row or more")
-        if rows is None and n_samples is not None and int(n_samples) > n:
-            raise ValueError("n_samples must lie in [1, %d] (rows are drawn without replacement) or be None, got %r" % (n, n_samples))
+        if rows is None:
+            _check_n_samples(n, n_samples)
         if rows is None and (n if n_samples is None else int(n_samples)) > _udrlib.MAX_ROWS:
             raise ValueError("UDR ranks at most %d rows: pass n_samples" % _udrlib.MAX_ROWS)
     if dim is not None and not 1 <= dim <= UDR_MAX_D:
@@ -1350,8 +1272,7 @@ DCI_LEARNING_RATE = 0.1                                                  # Gradi
 
 def _check_dci_arguments(n, dim, lat_sizes, n_train=10000, n_test=5000, seed=0, rows=None, n_stages=100):
     """n: prod(lat_sizes); dim: None where not known yet (before the encoder ran)."""
-    if len(lat_sizes) < 1 or min(lat_sizes) < 1:
-        raise ValueError("lat_sizes must hold positive sizes, got %s" % (lat_sizes,))
+    _check_lat_sizes(lat_sizes)
     if max(lat_sizes) > _dcilib.MAX_CLASSES:
         raise ValueError("a factor of variation with %d values: the boosted-tree kernels take at most %d classes"
                          % (max(lat_sizes), _dcilib.MAX_CLASSES))

@@ -1,5 +1,5 @@
 """CPU: the host side of the DCI scores -- the eighth library's C-ABI (include/dvae_dci_hip.h == disvae_amd/_dcilib.py == the built
-libdvae_dci_hip.so), its row of build.py's LATER_TARGETS, the LDS budget, dci_from_importance on hand-made matrices, the fp64
+libdvae_dci_hip.so), its row of build.py's TARGETS, the LDS budget, dci_from_importance on hand-made matrices, the fp64
 restatement (tests/dci_ref.py) against the installed scikit-learn, the preconditions the GPU tests rely on, and the argument errors
 raised before any library load.
 
@@ -33,7 +33,7 @@ import torch
 
 import dci_ref as R
 import disvae_amd
-from disvae_amd import _dcilib, _lib, _udrlib
+from disvae_amd import _cabi, _dcilib, _lib, _udrlib
 from disvae_amd import evaluate as E
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,7 +59,7 @@ def _nm(path, *flags):
     return subprocess.run([nm] + list(flags) + [path], capture_output=True, text=True, check=True).stdout
 
 
-def test_header_ctypes_table_and_exports_agree():
+def test_header_ctypes_table_and_exports_agree(monkeypatch):
     declared = sorted(set(re.findall(r"\b(dvae_dci_[a-zA-Z0-9_]+)\s*\(", _header())))
     assert declared == sorted(_dcilib.SIGNATURES) and len(declared) == 6
     assert declared == sorted(["dvae_dci_version", "dvae_dci_last_error", "dvae_dci_trees", "dvae_dci_fit_ws_floats",
@@ -83,7 +83,10 @@ def test_header_ctypes_table_and_exports_agree():
     assert _dcilib.lib().dvae_dci_version() == _dcilib.VERSION == 1
     assert os.path.basename(_dcilib.LIB_PATH) == "libdvae_dci_hip.so"
     binding = open(_dcilib.__file__).read()
-    assert 'os.environ.get("DVAE_DCI_HIP_LIB"' in binding and "Binding(LIB_PATH, SIGNATURES, _RESTYPE" in binding
+    assert 'Binding.for_library("dci", SIGNATURES, _RESTYPE' in binding and "LIB_PATH = _binding.path" in binding
+    assert _dcilib._binding.last_error == "dvae_dci_last_error" and _dcilib._binding.signatures is _dcilib.SIGNATURES
+    monkeypatch.setenv("DVAE_DCI_HIP_LIB", "/elsewhere/lib.so")              # the override, read when a binding is made
+    assert _cabi.Binding.for_library("dci", {}, {}, "").path == "/elsewhere/lib.so"
     for name in ("dci_from_table", "dci_from_importance"):
         assert name in disvae_amd.__all__ and getattr(disvae_amd, name) is getattr(E, name)
     assert [_dcilib.lib().dvae_dci_trees(C) for C in (0, 1, 2, 3, 256, 257)] == [0, 1, 1, 3, 256, 0]
@@ -104,17 +107,17 @@ def test_lds_budget():
     assert "DCI_LDS_MAX + DVAE_DCI_LDS_SCRATCH <= 160 * 1024" in src
 
 
-def test_later_targets_row_is_a_row_of_the_build_table():
-    """what test_extra_targets_rows_are_rows_of_the_build_table demands of EXTRA_TARGETS rows, of the LATER_TARGETS rows -- and that
-    "dci" is IN the table, not that the table is ["dci"]: the next library is one more row."""
+def test_dci_row_is_a_row_of_the_build_table():
+    """what test_build_table_drives_the_exported_names_and_the_identity_tool demands of every row of TARGETS, of the dci row -- and
+    that "dci" is IN the table, not what the table is: the next library is one more row."""
     build = _build()
-    assert "dci" in [name for name, _s, _h in build.LATER_TARGETS]
-    assert ("dci", ["boosted_trees"], "dvae_dci_hip.h") in [tuple(row) for row in build.LATER_TARGETS]
-    names = [n for n, _s, _h in build.TARGETS + build.EXTRA_TARGETS + build.LATER_TARGETS]
+    rows = [row for row in build.TARGETS if row[0] == "dci"]
+    assert [tuple(row) for row in rows] == [("dci", ["boosted_trees"], "dvae_dci_hip.h")]
+    names = [n for n, _s, _h in build.TARGETS]
     assert len(names) == len(set(names))
-    taken = {s for _n, sources, _h in build.TARGETS + build.EXTRA_TARGETS for s in sources}
+    taken = {s for n, sources, _h in build.TARGETS if n != "dci" for s in sources}
     text = {f: open(os.path.join(CSRC, f)).read() for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))}
-    for name, sources, header in build.LATER_TARGETS:
+    for name, sources, header in rows:
         prefix = name.upper() + "_"
         lib, srcs, headers = (getattr(build, prefix + suffix) for suffix in ("LIB", "SOURCES", "HEADERS"))
         assert srcs == sources and all(os.path.exists(os.path.join(build.SRC, s + ".hip")) for s in srcs)
@@ -125,14 +128,12 @@ def test_later_targets_row_is_a_row_of_the_build_table():
         assert all(os.path.exists(h) for h in headers)
         assert {os.path.basename(h) for h in headers} - {"dvae_hip.h", header} == {f for f in os.listdir(CSRC) if f.endswith(".h")}
         assert build._target(name, sources, header)[3] == os.path.join(build.OBJ, "flags_%s.txt" % name)
-        assert not set(sources) & taken                                   # no source is shared with another table or row
+        assert not set(sources) & taken                                   # no source is shared with another row
         taken |= set(sources)
         includes = [len(re.findall(r'^#include "last_error\.h"', text[s + ".hip"], re.M)) for s in sources]
         assert sum(includes) == 1 and max(includes) == 1
         assert os.path.exists(lib)                                        # build() built it
-    assert build.ALL_SOURCES == [s for _n, sources, _h in build.TARGETS for s in sources]   # the pinned list stays on TARGETS
-    doc = build.__doc__
-    assert "EXTRA_TARGETS" in doc and "LATER_TARGETS" in doc and "ONE list in spirit" in doc
+    assert set(build.DCI_SOURCES) <= set(build.ALL_SOURCES)               # tools/isa_identity.py compares them
 
 
 def test_source_obeys_the_rules_of_the_shared_plumbing():

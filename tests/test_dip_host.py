@@ -1,6 +1,6 @@
 """CPU: the host side of the DIP-VAE I / II losses -- the fp64 restatement (tests/dip_ref.py) against the literal
 disentanglement_lib form and numpy.cov, its analytic gradients against torch autograd, the ninth library's C-ABI
-(include/dvae_dip_hip.h == disvae_amd/_diplib.py == the built libdvae_dip_hip.so), its row of build.py's LATER_TARGETS, the keys
+(include/dvae_dip_hip.h == disvae_amd/_diplib.py == the built libdvae_dip_hip.so), its row of build.py's TARGETS, the keys
 get_loss_f reads, the refusal of data-parallel steps before any device work, and e32: the ratio error / bound that an fp32 numpy
 restatement attains on the tables and shapes of the GPU tests (tests/test_gpu_dip.py multiplies its fp32 bound by
 max(1, 4 e32)).
@@ -22,7 +22,7 @@ import torch
 
 import dip_ref as R
 import disvae_amd
-from disvae_amd import _diplib, _lib, _dcilib
+from disvae_amd import _cabi, _diplib, _lib, _dcilib
 from disvae_amd.models import losses as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -118,7 +118,7 @@ def _nm(path, *flags):
     return subprocess.run([nm] + list(flags) + [path], capture_output=True, text=True, check=True).stdout
 
 
-def test_header_ctypes_table_and_exports_agree():
+def test_header_ctypes_table_and_exports_agree(monkeypatch):
     declared = sorted(set(re.findall(r"\b(dvae_dip_[a-zA-Z0-9_]+)\s*\(", _header())))
     assert declared == sorted(_diplib.SIGNATURES)
     assert declared == sorted(["dvae_dip_version", "dvae_dip_last_error", "dvae_dip_ws_doubles", "dvae_dip_moments", "dvae_dip_grad"])
@@ -138,7 +138,10 @@ def test_header_ctypes_table_and_exports_agree():
     assert _diplib.lib().dvae_dip_version() == _diplib.VERSION == 1
     assert os.path.basename(_diplib.LIB_PATH) == "libdvae_dip_hip.so"
     binding = open(_diplib.__file__).read()
-    assert 'os.environ.get("DVAE_DIP_HIP_LIB"' in binding and "Binding(LIB_PATH, SIGNATURES, _RESTYPE" in binding
+    assert 'Binding.for_library("dip", SIGNATURES, _RESTYPE' in binding and "LIB_PATH = _binding.path" in binding
+    assert _diplib._binding.last_error == "dvae_dip_last_error" and _diplib._binding.signatures is _diplib.SIGNATURES
+    monkeypatch.setenv("DVAE_DIP_HIP_LIB", "/elsewhere/lib.so")              # the override, read when a binding is made
+    assert _cabi.Binding.for_library("dip", {}, {}, "").path == "/elsewhere/lib.so"
     assert "DipVaeLoss" in disvae_amd.__all__ and disvae_amd.DipVaeLoss is L.DipVaeLoss
     # k_dip_grad's LDS at the largest D: G fp32 [D, D], the centred rows of a trip and two vectors in fp64 -- within a CDNA4 compute unit
     D = _diplib.MAX_D
@@ -159,18 +162,18 @@ def test_workspace_sizes_and_the_chunking_mirror():
     assert _diplib.out_doubles(10) == 103
 
 
-def test_later_targets_has_the_dip_row():
+def test_build_table_has_the_dip_row():
     build = _build()
-    assert ("dip", ["dip_cov"], "dvae_dip_hip.h") in [tuple(row) for row in build.LATER_TARGETS]
-    names = [n for n, _s, _h in build.TARGETS + build.EXTRA_TARGETS + build.LATER_TARGETS]
+    assert ("dip", ["dip_cov"], "dvae_dip_hip.h") in [tuple(row) for row in build.TARGETS]
+    names = [n for n, _s, _h in build.TARGETS]
     assert len(names) == len(set(names)) >= 9                             # nine libraries (the next one is one more row)
-    others = {s for n, sources, _h in build.TARGETS + build.EXTRA_TARGETS + build.LATER_TARGETS if n != "dip" for s in sources}
+    others = {s for n, sources, _h in build.TARGETS if n != "dip" for s in sources}
     assert "dip_cov" not in others and build.DIP_SOURCES == ["dip_cov"]
     assert os.path.basename(build.DIP_LIB) == "libdvae_dip_hip.so" and os.path.exists(build.DIP_LIB)
     assert sorted(os.path.basename(h) for h in build.DIP_HEADERS if "include" in h.split(os.sep)) == ["dvae_dip_hip.h", "dvae_hip.h"]
     assert {os.path.basename(h) for h in build.DIP_HEADERS} - {"dvae_hip.h", "dvae_dip_hip.h"} == \
         {f for f in os.listdir(CSRC) if f.endswith(".h")}
-    assert build.ALL_SOURCES == [s for _n, sources, _h in build.TARGETS for s in sources]
+    assert "dip_cov" in build.ALL_SOURCES                                  # tools/isa_identity.py compares it
     # nothing of another library is linked in or included
     src = open(os.path.join(CSRC, "dip_cov.hip")).read()
     assert sorted(re.findall(r'^#include "([^"]+)"', src, re.M)) == ["../../include/dvae_dip_hip.h", "common.h", "last_error.h", "table_stats.h"]

@@ -1,5 +1,5 @@
 """CPU: the plumbing the score libraries share -- csrc/table_stats.h and csrc/last_error.h stay the one home of their helpers,
-disvae_amd/_cabi.py is the one loader behind the five bindings, build.py's TARGETS drives every build and tools/isa_identity.py,
+disvae_amd/_cabi.py is the one loader behind the eight bindings, build.py's TARGETS drives every build and tools/isa_identity.py,
 and evaluate.py's mutual information from counts is the expression the two *_from_statistics functions used to spell out."""
 import importlib.util
 import os
@@ -8,7 +8,7 @@ import re
 import numpy as np
 import pytest
 
-from disvae_amd import _cabi, _evallib, _infolib, _irslib, _lib, _scorelib, _unsuplib
+from disvae_amd import _cabi, _dcilib, _diplib, _evallib, _infolib, _irslib, _lib, _scorelib, _udrlib, _unsuplib
 from disvae_amd.evaluate import mutual_information_from_counts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,6 +26,12 @@ BINDINGS = {
               [DUMMY, DUMMY, DUMMY, DUMMY, DUMMY, 60, 3, 3, 10, 12, 13, 5, DUMMY, DUMMY, DUMMY, None], 13),
     _unsuplib: ("latent_pairs.hip", "dvae_unsup_last_error", "dvae_unsup_moments",
                 [DUMMY, DUMMY, 60, 3, 10, DUMMY, DUMMY, DUMMY, DUMMY, DUMMY, None], 9),
+    _udrlib: ("latent_ranks.hip", "dvae_udr_last_error", "dvae_udr_ranks",
+              [DUMMY, DUMMY, 60, 3, 10, DUMMY, DUMMY, None], 6),
+    _dcilib: ("boosted_trees.hip", "dvae_dci_last_error", "dvae_dci_predict",
+              [DUMMY, DUMMY, 60, 3, 10, 3, 5, 0.1, DUMMY, DUMMY, DUMMY, None], 10),
+    _diplib: ("dip_cov.hip", "dvae_dip_last_error", "dvae_dip_moments",
+              [DUMMY, DUMMY, 40, 3, DUMMY, DUMMY], 4),
 }
 
 
@@ -51,7 +57,7 @@ def test_score_helpers_have_one_home():
     assert homes(r"^void set_error\([^;{]*\)\s*\{") == ["last_error.h"]
     assert homes(r"\bthread_local\b") == ["last_error.h"]
     build = _load("dvae_build_plumbing", "disentangling-vae_amd", "build.py")
-    assert len(build.TARGETS) == 6
+    assert len(build.TARGETS) == 9
     for _name, sources, _header in build.TARGETS:
         includes = [len(re.findall(r'^#include "last_error\.h"', text[s + ".hip"], re.M)) for s in sources]
         assert sum(includes) == 1 and max(includes) == 1, (sources, includes)
@@ -108,7 +114,7 @@ def test_call_loads_through_the_modules_lib(mod, monkeypatch):
 # ---- 3. the build table ---------------------------------------------------------------------------------------------------------
 def test_build_table_drives_the_exported_names_and_the_identity_tool():
     build = _load("dvae_build_plumbing", "disentangling-vae_amd", "build.py")
-    assert [name for name, _s, _h in build.TARGETS] == ["", "eval", "score", "info", "irs", "unsup"]
+    assert [name for name, _s, _h in build.TARGETS] == ["", "eval", "score", "info", "irs", "unsup", "udr", "dci", "dip"]
     for name, sources, header in build.TARGETS:
         prefix = name.upper() + "_" if name else ""
         lib, srcs, headers = (getattr(build, prefix + suffix) for suffix in ("LIB", "SOURCES", "HEADERS"))
@@ -127,7 +133,8 @@ def test_build_table_drives_the_exported_names_and_the_identity_tool():
     union = [s for _n, sources, _h in build.TARGETS for s in sources]
     assert len(union) == len(set(union))
     isa = _load("dvae_isa_identity_plumbing", "tools", "isa_identity.py")
-    assert sorted(isa.ALL_SOURCES) == sorted(union) and len(isa.ALL_SOURCES) == len(union)
+    assert sorted(isa.ALL_SOURCES) == sorted(union) and len(isa.ALL_SOURCES) == len(union) == 31
+    assert build.ALL_SOURCES == union
 
 
 # ---- 4. mutual information from counts ------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """CPU: the host side of the unsupervised disentanglement ranking -- the seventh library's C-ABI (include/dvae_udr_hip.h ==
-disvae_amd/_udrlib.py == the built libdvae_udr_hip.so), its row of build.py's EXTRA_TARGETS, the fp64 restatement
+disvae_amd/_udrlib.py == the built libdvae_udr_hip.so), its row of build.py's TARGETS, the fp64 restatement
 (tests/udr_ref.py) against scipy and sklearn where they exist, the pair and model scores on hand-made matrices, the host
 combination of evaluate.py against the restatement, the precondition of the GPU tests' bounds, and the argument errors raised
 before any library load.
@@ -21,7 +21,7 @@ import torch
 
 import udr_ref as R
 import disvae_amd
-from disvae_amd import _lib, _udrlib, _unsuplib
+from disvae_amd import _cabi, _lib, _udrlib, _unsuplib
 from disvae_amd import evaluate as E
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -49,7 +49,7 @@ def _nm(path, *flags):
     return subprocess.run([nm] + list(flags) + [path], capture_output=True, text=True, check=True).stdout
 
 
-def test_header_ctypes_table_and_exports_agree():
+def test_header_ctypes_table_and_exports_agree(monkeypatch):
     declared = sorted(set(re.findall(r"\b(dvae_udr_[a-zA-Z0-9_]+)\s*\(", _header())))
     assert declared == sorted(_udrlib.SIGNATURES) and len(declared) == 6
     assert declared == sorted(["dvae_udr_version", "dvae_udr_last_error", "dvae_udr_ranks_ws_floats", "dvae_udr_ranks",
@@ -74,18 +74,21 @@ def test_header_ctypes_table_and_exports_agree():
     assert _udrlib.lib().dvae_udr_version() == _udrlib.VERSION == 1
     assert os.path.basename(_udrlib.LIB_PATH) == "libdvae_udr_hip.so"
     binding = open(_udrlib.__file__).read()
-    assert 'os.environ.get("DVAE_UDR_HIP_LIB"' in binding and "Binding(LIB_PATH, SIGNATURES, _RESTYPE" in binding
+    assert 'Binding.for_library("udr", SIGNATURES, _RESTYPE' in binding and "LIB_PATH = _binding.path" in binding
+    assert _udrlib._binding.last_error == "dvae_udr_last_error" and _udrlib._binding.signatures is _udrlib.SIGNATURES
+    monkeypatch.setenv("DVAE_UDR_HIP_LIB", "/elsewhere/lib.so")              # the override, read when a binding is made
+    assert _cabi.Binding.for_library("udr", {}, {}, "").path == "/elsewhere/lib.so"
     assert "udr_from_tables" in disvae_amd.__all__ and disvae_amd.udr_from_tables is E.udr_from_tables
 
 
-def test_extra_targets_rows_are_rows_of_the_build_table():
-    """what test_build_table_drives_the_exported_names_and_the_identity_tool demands of TARGETS rows, of EXTRA_TARGETS rows"""
+def test_udr_row_is_a_row_of_the_build_table():
+    """what test_build_table_drives_the_exported_names_and_the_identity_tool demands of every row of TARGETS, of the udr row"""
     build = _build()
-    assert [name for name, _s, _h in build.EXTRA_TARGETS] == ["udr"]
-    taken = {s for _n, sources, _h in build.TARGETS for s in sources}
-    assert not {n for n, _s, _h in build.TARGETS} & {n for n, _s, _h in build.EXTRA_TARGETS}
+    rows = [row for row in build.TARGETS if row[0] == "udr"]
+    assert [tuple(row) for row in rows] == [("udr", ["latent_ranks"], "dvae_udr_hip.h")]
+    taken = {s for n, sources, _h in build.TARGETS if n != "udr" for s in sources}
     text = {f: open(os.path.join(CSRC, f)).read() for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))}
-    for name, sources, header in build.EXTRA_TARGETS:
+    for name, sources, header in rows:
         prefix = name.upper() + "_"
         lib, srcs, headers = (getattr(build, prefix + suffix) for suffix in ("LIB", "SOURCES", "HEADERS"))
         assert srcs == sources and all(os.path.exists(os.path.join(build.SRC, s + ".hip")) for s in srcs)
@@ -97,14 +100,12 @@ def test_extra_targets_rows_are_rows_of_the_build_table():
         csrc_headers = {os.path.basename(h) for h in headers} - {"dvae_hip.h", header}
         assert csrc_headers == {f for f in os.listdir(CSRC) if f.endswith(".h")}
         assert build._target(name, sources, header)[3] == os.path.join(build.OBJ, "flags_%s.txt" % name)
-        assert not set(sources) & taken                                   # no source is shared with TARGETS
+        assert not set(sources) & taken                                   # no source is shared with another row
         taken |= set(sources)
         includes = [len(re.findall(r'^#include "last_error\.h"', text[s + ".hip"], re.M)) for s in sources]
         assert sum(includes) == 1 and max(includes) == 1
         assert os.path.exists(lib)                                        # build() built it
-    assert build.ALL_SOURCES == [s for _n, sources, _h in build.TARGETS for s in sources]   # the pinned list stays on TARGETS
-    doc = build.__doc__
-    assert "EXTRA_TARGETS" in doc and "ONE list in spirit" in doc
+    assert set(build.UDR_SOURCES) <= set(build.ALL_SOURCES)               # tools/isa_identity.py compares them
 
 
 def test_call_raises_with_the_librarys_own_error_text():
