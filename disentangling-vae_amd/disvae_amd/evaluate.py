@@ -48,6 +48,14 @@
   (libdvae_dci_hip.so: every stage of every factor is enqueued without a read-back); the [D] importances and the accuracies cross
   to the host, where the entropies of the [D, K] importance matrix are combined in fp64.  Written to dci.log by
   ``__call__(is_dci=True)``.
+* Prediction-based scores, new, on the entry points that are there (no new kernel): the downstream task (Locatello et al. 2019,
+  section 5.4; ``compute_downstream_task`` / ``downstream_task_from_table``), unfairness (Locatello et al. 2019b;
+  ``compute_fairness`` / ``fairness_from_table``) and explicitness (Ridgeway & Mozer 2018; ``compute_explicitness`` /
+  ``explicitness_from_table``).  The first two fit and evaluate DCI's boosted trees (libdvae_dci_hip.so; ``_BoostedFactor``, which
+  dci_from_table shares) -- on growing training sets, and on rows whose sensitive factor was intervened on, predicted by row
+  number without a copy of the table; the third ranks the class probabilities of the beta-VAE score's logistic regression with
+  dvae_udr_ranks: a ROC AUC is a rank sum.  Written to downstream_task.log / fairness.log / explicitness.log by
+  ``__call__(is_downstream=True, is_fairness=True, is_explicitness=True)``.
 """
 import logging
 import math
@@ -76,6 +84,9 @@ IRS_FILE = "irs.log"
 UNSUPERVISED_SCORES_FILE = "unsupervised_scores.log"
 UDR_FILE = "udr.log"
 DCI_FILE = "dci.log"
+DOWNSTREAM_TASK_FILE = "downstream_task.log"
+FAIRNESS_FILE = "fairness.log"
+EXPLICITNESS_FILE = "explicitness.log"
 
 
 class Evaluator:
@@ -92,7 +103,8 @@ class Evaluator:
 
     def __call__(self, data_loader, is_metrics=False, is_losses=True, is_log_likelihood=False, n_samples=128,
                  is_decomposition=False, n_samples_decomposition=10000, is_scores=False, is_information=False,
-                 is_irs=False, is_unsupervised=False, udr_models=None, is_dci=False, dci_args=None):
+                 is_irs=False, is_unsupervised=False, udr_models=None, is_dci=False, dci_args=None, is_downstream=False,
+                 is_fairness=False, is_explicitness=False, downstream_args=None, fairness_args=None, explicitness_args=None):
         """evaluate.py:60-95.  is_log_likelihood: also write compute_log_likelihood(data_loader, n_samples) to
         log_likelihood.log; is_decomposition: also write compute_elbo_decomposition(data_loader, n_samples_decomposition) to
         elbo_decomposition.log; is_scores: also write compute_factor_scores(data_loader) to factor_scores.log; is_information: also
@@ -101,7 +113,9 @@ class Evaluator:
         without its [D, D] matrix, to unsupervised_scores.log; udr_models (the other models of a sweep): also write
         compute_udr(data_loader, udr_models), its arrays as lists and without raw_correlations, to udr.log (the return value stays
         the reference's (metric, losses)); is_dci: also write compute_dci(data_loader, **dci_args), without its [D, K] matrix, to
-        dci.log."""
+        dci.log; is_downstream / is_fairness / is_explicitness: also write compute_downstream_task(data_loader, **downstream_args) to
+        downstream_task.log, compute_fairness(data_loader, **fairness_args) to fairness.log and compute_explicitness(data_loader,
+        **explicitness_args) to explicitness.log, their arrays as lists."""
         start = default_timer()
         is_still_training = self.model.training
         self.model.eval()
@@ -127,6 +141,12 @@ class Evaluator:
              lambda k, v: k == "raw_correlations", 'UDR', UDR_FILE),
             (is_dci, 'the DCI scores', lambda: self.compute_dci(data_loader, **(dci_args or {})),
              lambda k, v: isinstance(v, np.ndarray), 'DCI', DCI_FILE),
+            (is_downstream, 'the downstream-task accuracies', lambda: self.compute_downstream_task(data_loader, **(downstream_args or {})),
+             None, 'Downstream task', DOWNSTREAM_TASK_FILE),
+            (is_fairness, 'the unfairness scores', lambda: self.compute_fairness(data_loader, **(fairness_args or {})), nothing,
+             'Fairness', FAIRNESS_FILE),
+            (is_explicitness, 'the explicitness score', lambda: self.compute_explicitness(data_loader, **(explicitness_args or {})),
+             nothing, 'Explicitness', EXPLICITNESS_FILE),
         ]
         written = {}
         for wanted, what, compute, left_out, label, filename in outputs:
@@ -334,6 +354,34 @@ class Evaluator:
         _check_dci_arguments(n, None, lat_sizes, n_train, n_test, seed, None, n_stages)
         mean, _logvar = self._encode(dataloader, n, lat_sizes)
         return dci_from_table(mean, lat_sizes, n_train=n_train, n_test=n_test, seed=seed, n_stages=n_stages)
+
+    # ------------------------------------------------------------------ downstream task / fairness / explicitness
+    def compute_downstream_task(self, dataloader, n_train=(10, 100, 1000, 10000), n_test=5000, seed=0, n_stages=100):
+        """Downstream-task accuracies and sample efficiency of the model (downstream_task_from_table below, on the posterior means
+        of the whole data set through the native encoder).  The data-set requirements and errors of compute_factor_scores; every
+        size and argument is checked before any device work; train / eval mode is restored."""
+        _ds, lat_sizes, n = self._factor_sizes(dataloader)
+        _check_downstream_arguments(n, None, lat_sizes, n_train, n_test, seed, None, n_stages)
+        mean, _logvar = self._encode(dataloader, n, lat_sizes)
+        return downstream_task_from_table(mean, lat_sizes, n_train=n_train, n_test=n_test, seed=seed, n_stages=n_stages)
+
+    def compute_fairness(self, dataloader, n_train=10000, n_test_per_value=100, seed=0, n_stages=100):
+        """Unfairness of the model's representation (fairness_from_table below, on the posterior means of the whole data set
+        through the native encoder).  The data-set requirements and errors of compute_factor_scores; every size and argument is
+        checked before any device work; train / eval mode is restored."""
+        _ds, lat_sizes, n = self._factor_sizes(dataloader)
+        _check_fairness_arguments(n, None, lat_sizes, n_train, n_test_per_value, seed, n_stages)
+        mean, _logvar = self._encode(dataloader, n, lat_sizes)
+        return fairness_from_table(mean, lat_sizes, n_train=n_train, n_test_per_value=n_test_per_value, seed=seed, n_stages=n_stages)
+
+    def compute_explicitness(self, dataloader, n_train=10000, n_test=5000, seed=0):
+        """Explicitness of the model's representation (explicitness_from_table below, on the posterior means of the whole data set
+        through the native encoder).  The data-set requirements and errors of compute_factor_scores; every size and argument is
+        checked before any device work; train / eval mode is restored."""
+        _ds, lat_sizes, n = self._factor_sizes(dataloader)
+        _check_dci_arguments(n, None, lat_sizes, n_train, n_test, seed, None, 1)
+        mean, _logvar = self._encode(dataloader, n, lat_sizes)
+        return explicitness_from_table(mean, lat_sizes, n_train=n_train, n_test=n_test, seed=seed)
 
     # ------------------------------------------------------------------ MIG / AAM (evaluate.py:119-317)
     def compute_metrics(self, dataloader, sample_idx=None, n_samples=10000):
@@ -1311,6 +1359,72 @@ def dci_from_importance(importance):
     return float((per_code * W.sum(axis=1) / W.sum()).sum()), float((per_factor * W.sum(axis=0) / W.sum()).sum())
 
 
+def _factor_strides(lat_sizes):
+    """stride_k of a data set that enumerates lat_sizes row-major: factor k of row r is (r // stride_k) % lat_sizes[k]."""
+    return [int(np.prod(lat_sizes[k + 1:])) for k in range(len(lat_sizes))]
+
+
+def _column_order(table, train):
+    """int32 [D, S]: the stable ascending order of every column of table[train] -- dvae_dci_fit's `order`, ONE sort for all factors."""
+    return torch.sort(table.index_select(0, train), dim=0, stable=True).indices.t().contiguous().to(torch.int32)
+
+
+class _BoostedFactor:
+    """The boosted-tree classifier of ONE factor of variation, fitted on the device: what dci_from_table and the prediction-based
+    scores (downstream task, fairness) share.  The labels of the ``train`` rows are the ranks of the factor's values among those
+    PRESENT in them (``classes``, sorted); dvae_dci_fit enqueues every stage; ``predict`` enqueues dvae_dci_predict on any row
+    numbers of the table in calls of at most DVAE_DCI_MAX_ROWS rows and picks the class from the raw scores (two classes: the
+    sign of the one score; more: the arg-max, the lowest class on ties).  One value present fits no tree and predicts that
+    value; a row whose value was never seen counts as an error in ``accuracy``.  Nothing here is read back but the number of
+    classes present (the size of the raw scores)."""
+
+    def __init__(self, table, train, order, stride, size, n_stages, st):
+        n, dim = int(table.shape[0]), int(table.shape[1])
+        dev = table.device
+        n_train = int(train.numel())
+        self.table, self.stride, self.size, self.n_stages, self.st = table, int(stride), int(size), int(n_stages), st
+        self.values_train = self.values_of(train)
+        self.classes = torch.unique(self.values_train)                   # sorted; its length is the one number the host needs now
+        self.C = C = int(self.classes.numel())
+        self.T = T = _dcilib.trees(C)
+        labels = torch.searchsorted(self.classes, self.values_train).to(torch.int32).contiguous()
+        ws = torch.empty(max(_dcilib.lib().dvae_dci_fit_ws_floats(n, dim, n_train, C, n_stages), 2), dtype=torch.float32, device=dev)
+        raw = torch.empty(n_train, T, dtype=torch.float64, device=dev)
+        self.importance = torch.empty(dim, dtype=torch.float64, device=dev)
+        self.n_split = torch.empty(1, dtype=torch.int32, device=dev)
+        self.feature = torch.empty(n_stages, T, _dcilib.NODES, dtype=torch.int32, device=dev)
+        self.stats = torch.empty(n_stages, T, _dcilib.NODES, _dcilib.NODE_STATS, dtype=torch.float64, device=dev)
+        self.prior = torch.empty(T, dtype=torch.float64, device=dev)
+        _dcilib.call("dvae_dci_fit", ptr(table), ptr(train), ptr(order), ptr(labels), n, dim, n_train, C, n_stages, DCI_LEARNING_RATE,
+                     1, ptr(raw), ptr(self.prior), ptr(ws), ptr(self.importance), ptr(self.n_split), ptr(self.feature), ptr(self.stats),
+                     st)
+        self.picked_train = self._picked(raw)                            # the fit's own raw scores: the bits predict(train) gives
+
+    def values_of(self, rows):
+        """The factor's value of every row number."""
+        return (rows // self.stride) % self.size
+
+    def _picked(self, raw):
+        return (raw[:, 0] > 0).long() if self.C == 2 else raw.argmax(dim=1)
+
+    def predict(self, rows):
+        """int64 [S]: the index into ``classes`` of the class predicted for table[rows] (rows int64 [S] on the device, each in
+        [0, N): the kernel does not check them)."""
+        n, dim = int(self.table.shape[0]), int(self.table.shape[1])
+        rows = rows.contiguous()
+        S = int(rows.numel())
+        raw = self.prior.expand(S, self.T).contiguous()
+        for lo in range(0, S, _dcilib.MAX_ROWS):
+            part = min(_dcilib.MAX_ROWS, S - lo)
+            _dcilib.call("dvae_dci_predict", ptr(self.table), ptr(rows[lo:lo + part]), n, dim, part, self.C, self.n_stages,
+                         DCI_LEARNING_RATE, ptr(self.feature), ptr(self.stats), ptr(raw[lo:lo + part]), self.st)
+        return self._picked(raw)
+
+    def accuracy(self, picked, values):
+        """fp64 scalar on the device: the share of rows whose predicted class is their value."""
+        return (self.classes[picked] == values).double().mean()
+
+
 def dci_from_table(mean, lat_sizes, n_train=10000, n_test=5000, seed=0, rows=None, n_stages=100):
     """DCI of a representation given as the fp32 [N, D] table ``mean`` (on the GPU) of a data set that enumerates ``lat_sizes`` in
     row-major order: per factor a gradient-boosted classifier -- scikit-learn's GradientBoostingClassifier() restated
@@ -1337,35 +1451,15 @@ def dci_from_table(mean, lat_sizes, n_train=10000, n_test=5000, seed=0, rows=Non
     if rows is not None and torch.as_tensor(rows).numel() != n_train + n_test:
         raise ValueError("rows must hold n_train + n_test = %d row numbers" % (n_train + n_test))
     table, rows, _S, dev = _select_rows(mean, rows, n_train + n_test, seed, "dci_from_table", "boosted-tree")
-    L = _dcilib.lib()
     st = _stream()
     train, test = rows[:n_train].contiguous(), rows[n_train:].contiguous()
-    order = torch.sort(table.index_select(0, train), dim=0, stable=True).indices.t().contiguous().to(torch.int32)    # [D, n_train]
-    strides = [int(np.prod(lat_sizes[k + 1:])) for k in range(K)]
+    order = _column_order(table, train)
+    strides = _factor_strides(lat_sizes)
     fits = []
     for k in range(K):
-        values_train, values_test = ((r // strides[k]) % lat_sizes[k] for r in (train, test))
-        classes = torch.unique(values_train)                             # sorted; its length is the one number the host needs now
-        C = int(classes.numel())
-        T = _dcilib.trees(C)
-        labels = torch.searchsorted(classes, values_train).to(torch.int32).contiguous()
-        ws = torch.empty(max(L.dvae_dci_fit_ws_floats(n, dim, n_train, C, n_stages), 2), dtype=torch.float32, device=dev)
-        raw = torch.empty(n_train, T, dtype=torch.float64, device=dev)
-        importance = torch.empty(dim, dtype=torch.float64, device=dev)
-        n_split = torch.empty(1, dtype=torch.int32, device=dev)
-        feature = torch.empty(n_stages, T, _dcilib.NODES, dtype=torch.int32, device=dev)
-        stats = torch.empty(n_stages, T, _dcilib.NODES, _dcilib.NODE_STATS, dtype=torch.float64, device=dev)
-        prior = torch.empty(T, dtype=torch.float64, device=dev)
-        _dcilib.call("dvae_dci_fit", ptr(table), ptr(train), ptr(order), ptr(labels), n, dim, n_train, C, n_stages, DCI_LEARNING_RATE,
-                     1, ptr(raw), ptr(prior), ptr(ws), ptr(importance), ptr(n_split), ptr(feature), ptr(stats), st)
-        raw_test = prior.expand(n_test, T).contiguous()
-        _dcilib.call("dvae_dci_predict", ptr(table), ptr(test), n, dim, n_test, C, n_stages, DCI_LEARNING_RATE, ptr(feature),
-                     ptr(stats), ptr(raw_test), st)
-
-        def accuracy(raw_scores, values):
-            picked = (raw_scores[:, 0] > 0).long() if C == 2 else raw_scores.argmax(dim=1)
-            return (classes[picked] == values).double().mean()
-        fits.append((importance, n_split, accuracy(raw, values_train), accuracy(raw_test, values_test)))
+        fit = _BoostedFactor(table, train, order, strides[k], lat_sizes[k], n_stages, st)
+        fits.append((fit.importance, fit.n_split, fit.accuracy(fit.picked_train, fit.values_train),
+                     fit.accuracy(fit.predict(test), fit.values_of(test))))
     matrix = np.zeros((dim, K))
     acc = np.zeros((K, 2))
     for k, (importance, n_split, acc_train, acc_test) in enumerate(fits):      # the read-back, after every factor was enqueued
@@ -1377,3 +1471,310 @@ def dci_from_table(mean, lat_sizes, n_train=10000, n_test=5000, seed=0, rows=Non
     return {"disentanglement": disentanglement, "completeness": completeness, "informativeness_train": float(acc[:, 0].mean()),
             "informativeness_test": float(acc[:, 1].mean()), "importance_matrix": matrix, "n_train": n_train, "n_test": n_test,
             "n_stages": n_stages}
+
+
+# ---------------------------------------------------------------------- prediction-based scores on a table of means
+def _check_table_enumerates(n, lat_sizes):
+    if n != int(np.prod(lat_sizes)):
+        raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (n, lat_sizes))
+
+
+def _prediction_table(mean, caller, kernels):
+    """_select_rows without a selection: the table must be finite, then on the GPU -> (table fp32 contiguous, device)."""
+    table, _rows, _S, dev = _select_rows(mean, None, None, 0, caller, kernels)
+    return table, dev
+
+
+def _check_downstream_arguments(n, dim, lat_sizes, n_train=(10, 100, 1000, 10000), n_test=5000, seed=0, rows=None, n_stages=100):
+    """n: prod(lat_sizes); dim: None where not known yet.  Every size of n_train is held to _check_dci_arguments, in the order given."""
+    try:
+        sizes = [int(s) for s in n_train]
+    except TypeError:
+        raise ValueError("n_train must be a sequence of training-set sizes, got %r" % (n_train,)) from None
+    if not sizes or len(set(sizes)) != len(sizes):
+        raise ValueError("n_train must hold one size or more, each once, got %r" % (n_train,))
+    if rows is not None and len(rows) != len(sizes):
+        raise ValueError("rows must hold one selection per size of n_train: %d, got %d" % (len(sizes), len(rows)))
+    for i, size in enumerate(sizes):
+        _check_dci_arguments(n, dim, lat_sizes, size, n_test, seed, None if rows is None else rows[i], n_stages)
+    return sizes
+
+
+def downstream_task_aggregates(sizes, acc_train, acc_test):
+    """The result of downstream_task_from_table from the accuracies [len(sizes), K] (fp64) of every size and factor: per size n the
+    mean and the smallest accuracy over the factors and every factor's own, and for every n below the largest
+    "{n}:efficiency" = mean test accuracy at n / mean test accuracy at the largest n (disentanglement_lib's downstream_task.py;
+    0 / 0 counts as 0)."""
+    acc_train, acc_test = np.asarray(acc_train, dtype=np.float64), np.asarray(acc_test, dtype=np.float64)
+    out = {}
+    for i, n in enumerate(sizes):
+        for name, acc in (("train", acc_train[i]), ("test", acc_test[i])):
+            out["%d:mean_%s_accuracy" % (n, name)] = float(acc.mean())
+            out["%d:min_%s_accuracy" % (n, name)] = float(acc.min())
+            for k, a in enumerate(acc):
+                out["%d:%s_accuracy_factor_%d" % (n, name, k)] = float(a)
+    largest = max(sizes)
+    top = out["%d:mean_test_accuracy" % largest]
+    for n in sizes:
+        if n != largest:
+            out["%d:efficiency" % n] = out["%d:mean_test_accuracy" % n] / top if top > 0 else 0.0
+    return out
+
+
+def downstream_task_from_table(mean, lat_sizes, n_train=(10, 100, 1000, 10000), n_test=5000, seed=0, rows=None, n_stages=100):
+    """Downstream-task score (Locatello et al. 2019, section 5.4; disentanglement_lib's downstream_task.py with its
+    gradient-boosting predictor) of a representation given as the fp32 [N, D] table ``mean`` (on the GPU) of a data set that
+    enumerates ``lat_sizes`` in row-major order: for every training-set size n of ``n_train``, in the order given, the boosted-tree
+    classifier of dci_from_table (_BoostedFactor: libdvae_dci_hip.so) is fitted per factor on n rows and its accuracy is taken
+    on those rows and on n_test others -- the launches of dci_from_table(n_train=n, rows=rows_n), whose informativeness_train /
+    informativeness_test are "{n}:mean_train_accuracy" / "{n}:mean_test_accuracy" here, bit for bit.
+
+    rows_n = randperm(N)[:n + n_test], one draw per size from ONE private generator seeded with ``seed`` (the same seed gives the
+    same bits, the global random states are untouched), the first n to fit; ``rows`` (a list with one [n + n_test] selection per
+    size, row numbers in [0, N), repeats allowed) injects them.  Labels, unseen values and a factor with one value present: as in
+    dci_from_table.  Every size and argument is checked before any device work (the limits are dci_from_table's, per size), a
+    table with a NaN or an infinity raises ValueError, and nothing is read back until every fit and prediction of every size is
+    enqueued.  Returns downstream_task_aggregates' keys plus "n_train" (the list), "n_test", "n_stages": Python values."""
+    lat_sizes = [int(k) for k in lat_sizes]
+    K, n_test, n_stages = len(lat_sizes), int(n_test), int(n_stages)
+    n, dim = _table_shape(mean)
+    sizes = _check_downstream_arguments(int(np.prod(lat_sizes)) if lat_sizes else 0, dim, lat_sizes, n_train, n_test, seed, rows, n_stages)
+    _check_table_enumerates(n, lat_sizes)
+    if rows is not None:
+        for size, r in zip(sizes, rows):
+            if torch.as_tensor(r).numel() != size + n_test:
+                raise ValueError("rows must hold n_train + n_test = %d row numbers for n_train = %d" % (size + n_test, size))
+        rows = [_checked_rows(r, n) for r in rows]
+    table, dev = _prediction_table(mean, "downstream_task_from_table", "boosted-tree")
+    gen = torch.Generator(device=dev).manual_seed(int(seed))
+    st = _stream()
+    strides = _factor_strides(lat_sizes)
+    enqueued = []
+    for i, size in enumerate(sizes):
+        if rows is not None:
+            rows_n = rows[i].to(dev).contiguous()
+        else:
+            rows_n = torch.randperm(n, generator=gen, device=dev)[:size + n_test].contiguous()
+        train, test = rows_n[:size].contiguous(), rows_n[size:].contiguous()
+        order = _column_order(table, train)
+        for k in range(K):
+            fit = _BoostedFactor(table, train, order, strides[k], lat_sizes[k], n_stages, st)
+            enqueued.append(torch.stack([fit.accuracy(fit.picked_train, fit.values_train),
+                                         fit.accuracy(fit.predict(test), fit.values_of(test))]))
+    acc = torch.stack(enqueued).cpu().numpy().reshape(len(sizes), K, 2)            # ONE read-back, after everything was enqueued
+    scores = downstream_task_aggregates(sizes, acc[:, :, 0], acc[:, :, 1])
+    scores.update(n_train=sizes, n_test=n_test, n_stages=n_stages)
+    return scores
+
+
+def intervened_rows(base, stride, size):
+    """Row numbers [size, P] of the rows ``base`` [P] (a tensor of row numbers of a data set that enumerates its factors
+    row-major) after an intervention on the factor with this stride and size: row c has that factor set to c and every other
+    factor as in ``base`` -- base - ((base // stride) % size) * stride + c * stride."""
+    cleared = base - ((base // stride) % size) * stride
+    return cleared.unsqueeze(0) + torch.arange(size, dtype=base.dtype, device=base.device).unsqueeze(1) * stride
+
+
+def unfairness_from_counts(counts):
+    """disentanglement_lib's inter_group_fairness of a count matrix [classes predicted, values of the sensitive factor], fp64:
+    overall = counts.sum(1) / counts.sum(), p_c = counts[:, c] / counts[:, c].sum(), tv_c = 0.5 sum_y |p_c[y] - overall[y]| ->
+    (sum_c tv_c n_c / sum_c n_c, max_c tv_c) with n_c the column sums; a column without a row takes no part."""
+    counts = np.asarray(counts, dtype=np.float64)
+    if counts.ndim != 2 or counts.size == 0 or counts.sum() <= 0:
+        raise ValueError("counts must be a [classes, values] matrix that counts one row or more, got shape %s" % (counts.shape,))
+    n_c = counts.sum(axis=0)
+    overall = counts.sum(axis=1) / counts.sum()
+    live = np.flatnonzero(n_c > 0)
+    tv = np.array([0.5 * np.abs(counts[:, c] / n_c[c] - overall).sum() for c in live])      # a column at a time: one order of summation
+    return float((tv * n_c[live]).sum() / n_c[live].sum()), float(tv.max())
+
+
+def fairness_from_counts(counts, K):
+    """The host half of fairness_from_table, fp64.  counts: {(i, j): the count matrix of target i under interventions on j}, every
+    ordered pair of the K >= 2 factors -> the two [K, K] matrices of unfairness_from_counts (diagonal 0), their means over the
+    off-diagonal entries and the means of the rows / columns of the first without the diagonal entry."""
+    mean_m, max_m = np.zeros((K, K)), np.zeros((K, K))
+    for (i, j), c in counts.items():
+        mean_m[i, j], max_m[i, j] = unfairness_from_counts(c)
+    off = ~np.eye(K, dtype=bool)
+    return {"mean_unfairness_matrix": mean_m, "max_unfairness_matrix": max_m, "mean_unfairness": float(mean_m[off].mean()),
+            "max_unfairness": float(max_m[off].mean()), "mean_unfairness_per_target": mean_m.sum(axis=1) / (K - 1),
+            "mean_unfairness_per_sensitive": mean_m.sum(axis=0) / (K - 1)}
+
+
+def _check_fairness_arguments(n, dim, lat_sizes, n_train=10000, n_test_per_value=100, seed=0, n_stages=100, rows=None, base_rows=None):
+    """n: prod(lat_sizes); dim: None where not known yet.  The limits of _check_dci_arguments; the base rows are drawn WITH
+    replacement, so only n_train is held to the size of the data set."""
+    _check_dci_arguments(n, dim, lat_sizes, n_train, 1, seed, (), n_stages)       # (): the sum n_train + n_test is not this score's
+    if len(lat_sizes) < 2:
+        raise ValueError("fairness needs a target and a sensitive factor: two factors of variation or more, got lat_sizes=%s" % (lat_sizes,))
+    if int(n_test_per_value) < 1:
+        raise ValueError("n_test_per_value must be at least 1, got %r" % (n_test_per_value,))
+    if rows is None and int(n_train) > n:
+        raise ValueError("n_train must be at most %d (rows are drawn without replacement), got %d" % (n, int(n_train)))
+
+
+def fairness_from_table(mean, lat_sizes, n_train=10000, n_test_per_value=100, seed=0, n_stages=100, rows=None, base_rows=None,
+                        return_details=False):
+    """Unfairness of a representation (Locatello et al. 2019b, On the Fairness of Disentangled Representations;
+    disentanglement_lib's fairness.py) given as the fp32 [N, D] table ``mean`` (on the GPU) of a data set that enumerates
+    ``lat_sizes`` in row-major order: how much the prediction of a target factor i moves when a sensitive factor j is intervened
+    on.  Per factor i the boosted-tree classifier of dci_from_table (_BoostedFactor: libdvae_dci_hip.so) is fitted ONCE on
+    n_train rows; for every ordered pair (i, j), j != i, in row-major order, P = n_test_per_value base rows are drawn uniformly
+    WITH replacement, factor j of every base row is set to each of its values c in turn (intervened_rows: row arithmetic, no copy
+    of the table) and all size_j P rows are predicted on the device (dvae_dci_predict, at most DVAE_DCI_MAX_ROWS rows a call);
+    counts[y, c] = the rows of column c predicted as class y (a bincount on the device; y runs over the classes present in the
+    training rows); mean_unfairness[i, j], max_unfairness[i, j] = unfairness_from_counts(counts), in fp64 on the host.
+
+    Training rows = randperm(N)[:n_train], then the base rows = randint(N, [P]) pair by pair, from ONE private generator seeded
+    with ``seed`` (the same seed gives the same bits, the global random states are untouched); ``rows`` ([n_train] row numbers
+    in [0, N), repeats allowed) and ``base_rows`` ([K, K, P], the diagonal is not used) inject them, each on its own.  Every size
+    and argument is checked before any device work, a table with a NaN or an infinity raises ValueError, and nothing is read
+    back until every fit and prediction is enqueued.  Returns {"mean_unfairness_matrix", "max_unfairness_matrix" [K, K] (target
+    x sensitive, diagonal 0), "mean_unfairness", "max_unfairness" (the means of the two matrices over their off-diagonal
+    entries, as disentanglement_lib reports them), "mean_unfairness_per_target", "mean_unfairness_per_sensitive" [K] (the means of
+    a row / a column of the first matrix without its diagonal entry), "n_train", "n_test_per_value", "n_stages"}: Python and numpy
+    values.  return_details=True: (scores, details) with "classes" (per factor the values present in training) and "predicted"
+    ({(i, j): the predicted VALUES of factor i, int64 [size_j, P]}), host copies."""
+    lat_sizes = [int(k) for k in lat_sizes]
+    K, n_train, P, n_stages = len(lat_sizes), int(n_train), int(n_test_per_value), int(n_stages)
+    n, dim = _table_shape(mean)
+    _check_fairness_arguments(int(np.prod(lat_sizes)) if lat_sizes else 0, dim, lat_sizes, n_train, P, seed, n_stages, rows, base_rows)
+    _check_table_enumerates(n, lat_sizes)
+    if rows is not None:
+        if torch.as_tensor(rows).numel() != n_train:
+            raise ValueError("rows must hold n_train = %d row numbers" % n_train)
+        rows = _checked_rows(rows, n)
+    if base_rows is not None:
+        base_rows = torch.as_tensor(base_rows).to(torch.int64)
+        if tuple(base_rows.shape) != (K, K, P) or not (0 <= int(base_rows.min()) and int(base_rows.max()) < n):
+            raise ValueError("base_rows must have shape (%d, %d, %d) and hold row numbers in [0, %d)" % (K, K, P, n))
+    table, dev = _prediction_table(mean, "fairness_from_table", "boosted-tree")
+    gen = torch.Generator(device=dev).manual_seed(int(seed))
+    st = _stream()
+    strides = _factor_strides(lat_sizes)
+    train = rows.to(dev).contiguous() if rows is not None else torch.randperm(n, generator=gen, device=dev)[:n_train].contiguous()
+    if base_rows is not None:
+        base_rows = base_rows.to(dev)
+    order = _column_order(table, train)
+    fits = [_BoostedFactor(table, train, order, strides[k], lat_sizes[k], n_stages, st) for k in range(K)]
+    counted, predicted = {}, {}
+    for i in range(K):
+        for j in range(K):
+            if j == i:
+                continue
+            base = base_rows[i, j] if base_rows is not None else torch.randint(n, (P,), generator=gen, device=dev)
+            picked = fits[i].predict(intervened_rows(base, strides[j], lat_sizes[j]).reshape(-1))       # [size_j * P], column c first
+            column = torch.arange(lat_sizes[j], device=dev).repeat_interleave(P)
+            counted[i, j] = torch.bincount(picked * lat_sizes[j] + column, minlength=fits[i].C * lat_sizes[j])
+            if return_details:
+                predicted[i, j] = fits[i].classes[picked].view(lat_sizes[j], P)
+    # the read-back, after everything was enqueued
+    scores = fairness_from_counts({(i, j): c.cpu().numpy().reshape(fits[i].C, lat_sizes[j]) for (i, j), c in counted.items()}, K)
+    scores.update(n_train=n_train, n_test_per_value=P, n_stages=n_stages)
+    if not return_details:
+        return scores
+    return scores, {"classes": [f.classes.cpu() for f in fits], "predicted": {ij: v.cpu() for ij, v in predicted.items()}}
+
+
+def auc_from_rank_sums(rank_sum, n_pos, n_rows):
+    """One-vs-rest ROC AUC of every class from the sum R+ of the tie-averaged ranks (1-based, among all n_rows scores of the class's
+    column) of its n+ positive rows: (R+ - n+ (n+ + 1) / 2) / (n+ n-), the Mann-Whitney form, fp64 -> (auc [C], NaN for a class
+    without positives or without negatives; the mean over the other classes, NaN when there is none)."""
+    rank_sum, n_pos = np.asarray(rank_sum, dtype=np.float64), np.asarray(n_pos, dtype=np.float64)
+    n_neg = float(n_rows) - n_pos
+    ok = (n_pos > 0) & (n_neg > 0)
+    auc = np.full(rank_sum.shape, np.nan)
+    auc[ok] = (rank_sum[ok] - n_pos[ok] * (n_pos[ok] + 1.0) / 2.0) / (n_pos[ok] * n_neg[ok])
+    return auc, (float(np.mean(auc[ok])) if ok.any() else float("nan"))
+
+
+def explicitness_from_aucs(auc_train, auc_test):
+    """The per-factor AUCs [K] (NaN: a factor without a class that has positives and negatives) -> the result of
+    explicitness_from_table without its sizes: the means over the factors that have an AUC, NaN when there is none."""
+    out = {}
+    for name, a in (("train", np.asarray(auc_train, dtype=np.float64)), ("test", np.asarray(auc_test, dtype=np.float64))):
+        have = ~np.isnan(a)
+        out["explicitness_" + name] = float(np.mean(a[have])) if have.any() else float("nan")
+        out["explicitness_%s_per_factor" % name] = a
+    return out
+
+
+def class_probabilities(W, b, features):
+    """softmax(features W^T + b) in fp64 on the CPU, [n, C]."""
+    return torch.softmax(torch.as_tensor(features, dtype=torch.float64) @ W.t() + b, dim=1)
+
+
+def explicitness_from_table(mean, lat_sizes, n_train=10000, n_test=5000, seed=0, rows=None, return_details=False):
+    """Explicitness (Ridgeway & Mozer 2018; the second half of disentanglement_lib's modularity_explicitness.py) of a
+    representation given as the fp32 [N, D] table ``mean`` (on the GPU) of a data set that enumerates ``lat_sizes`` in row-major
+    order: per factor the multinomial logistic regression of the beta-VAE score (fit_logistic_regression, C = 1.0, fp64 on the
+    CPU) predicts the factor from the raw latents of n_train rows -- labels are the ranks of the factor's values among those
+    PRESENT in the training rows --; its class probabilities of the training and of the test rows are rounded to fp32 and every
+    class column is ranked on the device (dvae_udr_ranks of libdvae_udr_hip.so: exact tie-averaged ranks, at most DVAE_UDR_MAX_D
+    columns a call); the one-vs-rest AUC of a class is the rank sum of its rows (auc_from_rank_sums, summed in fp64: the ranks
+    are half-integers, the sum is exact), the AUC of a factor the mean over its classes with both positives and negatives among
+    the evaluated rows.  scikit-learn's roc_auc_score raises for a class without positives; here that class is left out, a factor
+    without any such class (one value present: no negatives among the training rows) is NaN in the per-factor arrays and left
+    out of the means (NaN when no factor is left).  A test row with a value never seen in training is a negative of every class.
+
+    Rows as in dci_from_table: randperm(N)[:n_train + n_test] from a private generator seeded with ``seed``, the first n_train to
+    fit; ``rows`` injects the selection.  Every size and argument is checked before any device work (the limits of
+    dci_from_table) and a table with a NaN or an infinity raises ValueError.  Returns {"explicitness_train", "explicitness_test",
+    "explicitness_train_per_factor", "explicitness_test_per_factor" [K], "n_train", "n_test"}: Python and numpy values.
+    return_details=True: (scores, details) with per factor "classes", "W", "b", the fp32 "probabilities_train" /
+    "probabilities_test" that were ranked, "labels_train" / "labels_test" (-1: a value never seen) and the per-class AUCs."""
+    lat_sizes = [int(k) for k in lat_sizes]
+    K, n_train, n_test = len(lat_sizes), int(n_train), int(n_test)
+    n, dim = _table_shape(mean)
+    _check_dci_arguments(int(np.prod(lat_sizes)) if lat_sizes else 0, dim, lat_sizes, n_train, n_test, seed, rows, 1)
+    _check_table_enumerates(n, lat_sizes)
+    if rows is not None and torch.as_tensor(rows).numel() != n_train + n_test:
+        raise ValueError("rows must hold n_train + n_test = %d row numbers" % (n_train + n_test))
+    table, rows, _S, dev = _select_rows(mean, rows, n_train + n_test, seed, "explicitness_from_table", "ranking")
+    L = _udrlib.lib()
+    st = _stream()
+    strides = _factor_strides(lat_sizes)
+    features = table.index_select(0, rows).cpu().double()                          # [n_train + n_test, D]: the fit is the host's
+    rows_host = rows.cpu()
+    sets = (("train", slice(0, n_train)), ("test", slice(n_train, n_train + n_test)))
+    enqueued, details = [], []
+    for k in range(K):
+        values = (rows_host // strides[k]) % lat_sizes[k]
+        classes = torch.unique(values[:n_train])                         # sorted
+        C = int(classes.numel())
+        at = torch.searchsorted(classes, values).clamp(max=C - 1)
+        labels = torch.where(classes[at] == values, at, torch.full_like(at, -1))   # -1: a value never seen in training
+        if C > 1:
+            W, b = fit_logistic_regression(features[:n_train], labels[:n_train], C, C=1.0)
+        else:                                                            # one class: nothing to fit
+            W, b = torch.zeros(1, dim, dtype=torch.float64), torch.zeros(1, dtype=torch.float64)
+        detail = {"classes": classes, "W": W, "b": b}
+        for name, part in sets:
+            S = part.stop - part.start
+            prob = class_probabilities(W, b, features[part]).to(torch.float32).to(dev)                   # [S, C], rounded to fp32
+            lab = labels[part].to(dev)
+            rank_sum = torch.empty(C, dtype=torch.float64, device=dev)
+            for lo in range(0, C, _udrlib.MAX_D):
+                cols = prob[:, lo:lo + _udrlib.MAX_D].contiguous()
+                width = int(cols.shape[1])
+                ws = torch.empty(max(L.dvae_udr_ranks_ws_floats(S, width, S), 1), dtype=torch.float32, device=dev)
+                ranks = torch.empty(S, width, dtype=torch.float32, device=dev)
+                _udrlib.call("dvae_udr_ranks", ptr(cols), None, S, width, S, ptr(ws), ptr(ranks), st)
+                own = lab.unsqueeze(1) == torch.arange(lo, lo + width, device=dev).unsqueeze(0)
+                rank_sum[lo:lo + width] = (ranks.double() * own).sum(dim=0)
+            n_pos = torch.bincount(lab + 1, minlength=C + 1)[1:]
+            enqueued.append((k, name, S, rank_sum, n_pos))
+            detail["probabilities_" + name], detail["labels_" + name] = prob, labels[part]
+        details.append(detail)
+    per_factor = {"train": np.full(K, np.nan), "test": np.full(K, np.nan)}
+    for k, name, S, rank_sum, n_pos in enqueued:                                   # the read-back, after every ranking was enqueued
+        auc, per_factor[name][k] = auc_from_rank_sums(rank_sum.cpu().numpy(), n_pos.cpu().numpy(), S)
+        details[k]["auc_" + name] = auc
+    scores = explicitness_from_aucs(per_factor["train"], per_factor["test"])
+    scores.update(n_train=n_train, n_test=n_test)
+    if not return_details:
+        return scores
+    for d in details:
+        d["probabilities_train"], d["probabilities_test"] = d["probabilities_train"].cpu(), d["probabilities_test"].cpu()
+    return scores, details
