@@ -7,6 +7,7 @@ include/.  Target "" is libdvae_hip.so, the training library; every other target
 nothing of one target is linked into another.  All targets share FLAGS and the up-to-date
 logic, each under a stamp of its own (build/flags.txt, build/flags_NAME.txt).  The module's X_LIB / X_SOURCES /
 X_HEADERS names (LIB / SOURCES / HEADERS for the training library) are derived from the table.
+PLUGIN_TARGETS is a second list of the same rows, built after TARGETS in the same way (see there).
 The libraries land in disentangling-vae_amd/lib/ (git-ignored build products).  Objects are rebuilt only
 when a source / header is newer or the flags changed.
 --debug (or DVAE_BUILD_DEBUG=1) adds -DDVAE_DEBUG_SWITCHES: the A/B / timing-ablation environment
@@ -36,6 +37,12 @@ TARGETS = [
     ("dci", ["boosted_trees"], "dvae_dci_hip.h"),          # DCI: gradient-boosted trees fitted on the device, their importances
     ("dip", ["dip_cov"], "dvae_dip_hip.h"),                # DIP-VAE I / II: batch covariance, the regulariser and its gradients (a TRAINING loss)
 ]
+# Libraries built like a row of TARGETS -- same _target / _build_target, FLAGS and stamp logic, after TARGETS -- but kept OUT of
+# TARGETS, ALL_SOURCES and tools/isa_identity.py: the host tests pin the nine rows, their names and the 31 sources that the
+# machine-code identity tool compares, and a loss plugin with a library of its own touches none of them.
+PLUGIN_TARGETS = [
+    ("mmd", ["mmd_pairs"], "dvae_mmd_hip.h"),              # InfoVAE / MMD-VAE: the batch MMD against prior samples and its gradient (a TRAINING loss)
+]
 HEADERS = sorted(glob.glob(os.path.join(SRC, "*.h"))) + [os.path.join(HERE, "..", "include", "dvae_hip.h")]
 
 
@@ -46,7 +53,7 @@ def _target(name, sources, header):
     return os.path.join(HERE, "lib", "libdvae%s_hip.so" % infix), sources, headers, os.path.join(OBJ, "flags%s.txt" % infix)
 
 
-for _row in TARGETS:        # LIB / SOURCES / HEADERS of the training library, EVAL_LIB / EVAL_SOURCES / EVAL_HEADERS, ... of the others
+for _row in TARGETS + PLUGIN_TARGETS:        # LIB / SOURCES / HEADERS of the training library, EVAL_LIB / EVAL_SOURCES / EVAL_HEADERS, ... of the others
     _prefix = _row[0].upper() + "_" if _row[0] else ""
     globals()[_prefix + "LIB"], globals()[_prefix + "SOURCES"], globals()[_prefix + "HEADERS"], _ = _target(*_row)
 ALL_SOURCES = [s for _, sources, _ in TARGETS for s in sources]
@@ -87,14 +94,14 @@ def _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose):
 
 
 def build(force=False, verbose=True, debug=None):
-    """Build every target of TARGETS, in its order; returns the path of libdvae_hip.so."""
+    """Build every target of TARGETS, then of PLUGIN_TARGETS, in their order; returns the path of libdvae_hip.so."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if debug is None:
         debug = os.environ.get("DVAE_BUILD_DEBUG", "0") == "1"
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
     flags = FLAGS + (["-DDVAE_DEBUG_SWITCHES"] if debug else [])
-    for name, sources, header in TARGETS:
+    for name, sources, header in TARGETS + PLUGIN_TARGETS:
         lib, sources, headers, stamp = _target(name, sources + (DEBUG_SOURCES if debug and not name else []), header)
         _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose)
     return LIB

@@ -28,8 +28,8 @@ from .evaluate import (Evaluator, dci_from_importance, dci_from_table, downstrea
                        explicitness_from_table, fairness_from_table, udr_from_tables)
 from .visualize import Visualizer, GifTraversalsTraining  # noqa: E402
 from .likelihood import per_image_losses, log_likelihood  # noqa: E402
-from .models.losses import DipVaeLoss  # noqa: E402
+from .models.losses import DipVaeLoss, InfoVaeLoss  # noqa: E402
 
 __all__ = ["init_specific_model", "Trainer", "Evaluator", "Visualizer", "GifTraversalsTraining", "per_image_losses",
-           "log_likelihood", "udr_from_tables", "dci_from_table", "dci_from_importance", "DipVaeLoss",
+           "log_likelihood", "udr_from_tables", "dci_from_table", "dci_from_importance", "DipVaeLoss", "InfoVaeLoss",
            "downstream_task_from_table", "fairness_from_table", "explicitness_from_table"]

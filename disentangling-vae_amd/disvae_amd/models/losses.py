@@ -1,6 +1,6 @@
 """Loss plugins with the API of disvae/models/losses.py (get_loss_f, BaseLoss, BetaHLoss,
 BetaBLoss, FactorKLoss, BtcvaeLoss, LOSSES, RECON_DIST) on the HIP kernels, plus DipVaeLoss / DIP_LOSSES
-(DIP-VAE-I / II, which the reference does not have).
+(DIP-VAE-I / II) and InfoVaeLoss / INFO_LOSSES (InfoVAE / MMD-VAE), which the reference does not have.
 
 Two ways in:
   * ``loss(data, recon, latent_dist, is_train, storer, latent_sample=...)`` -- the reference
@@ -18,6 +18,7 @@ import contextlib
 import torch
 
 from .. import _diplib
+from .. import _mmdlib
 from .. import _lib
 from .. import optim
 from .._lib import call, ptr, record_py
@@ -31,6 +32,7 @@ from ..schedule import build_policy, replay_mode, switches
 LOSSES = ["VAE", "betaH", "betaB", "factor", "btcvae"]  # losses.py:17
 RECON_DIST = ["bernoulli", "laplace", "gaussian"]        # losses.py:18
 DIP_LOSSES = ["dipI", "dipII"]                           # DIP-VAE-I / II (Kumar et al. 2018): not in the reference, so not in LOSSES
+INFO_LOSSES = ["infovae"]                                # InfoVAE / MMD-VAE (Zhao et al. 2019): not in the reference either
 
 
 def get_loss_f(loss_name, **kwargs_parse):
@@ -53,6 +55,9 @@ def get_loss_f(loss_name, **kwargs_parse):
     elif loss_name in DIP_LOSSES:
         return DipVaeLoss(dip_type="i" if loss_name == "dipI" else "ii", lambda_od=kwargs_parse.get("dip_lambda_od", 10.),
                           lambda_d_factor=kwargs_parse.get("dip_lambda_d_factor"), **kwargs_all)
+    elif loss_name in INFO_LOSSES:
+        return InfoVaeLoss(alpha=kwargs_parse.get("info_alpha", 0.), lam=kwargs_parse.get("info_lambda", 1000.),
+                           kernel=kwargs_parse.get("mmd_kernel", "imq"), bandwidth=kwargs_parse.get("mmd_bandwidth"), **kwargs_all)
     else:
         assert loss_name not in LOSSES
         raise ValueError("Uknown loss : {}".format(loss_name))
@@ -440,6 +445,38 @@ class _DipFn(torch.autograd.Function):
         return dmu * gout, None if dlv is None else dlv * gout, None, None
 
 
+def _mmd_launches(z, prior, mu, kernel, h, w, ws, dmu, dlv, out, loss_io, stream):
+    """The two launches of libdvae_mmd_hip.so (include/dvae_mmd_hip.h) on a [B, D] batch of latent samples and as many prior
+    draws; dmu None: the value only.  Through record_py: a recorded plan re-issues them with these arguments, a hipGraph captures
+    them."""
+    B, D = z.shape
+    record_py(_mmdlib.call, "dvae_mmd_pairs", ptr(z), ptr(prior), B, D, _mmdlib.KERNELS[kernel], float(h), int(dmu is not None),
+              ptr(ws), stream)
+    record_py(_mmdlib.call, "dvae_mmd_finish", ptr(z), ptr(mu), B, D, float(w), ptr(ws), ptr(dmu), ptr(dlv), ptr(out), loss_io,
+              stream)
+
+
+class _MmdFn(torch.autograd.Function):
+    """w MMD_u(z, prior) -> 0-d tensor; the value and the gradient with respect to z come from the same two launches as in the
+    fused step, so backward only scales what forward saved."""
+
+    @staticmethod
+    def forward(ctx, z, prior, kernel, h, w):
+        z, prior = z.contiguous(), prior.contiguous()
+        B, D = z.shape
+        f64 = lambda n: torch.empty(n, dtype=torch.float64, device=z.device)
+        ws, out = f64(_mmdlib.ws_doubles(B, D)), f64(_mmdlib.OUT_DOUBLES)
+        dz = torch.empty_like(z)
+        _mmd_launches(z, prior, None, kernel, h, w, ws, dz, None, out, None, _stream())
+        ctx.save_for_backward(dz)
+        return out[0].float()
+
+    @staticmethod
+    def backward(ctx, gout):
+        (dz,) = ctx.saved_tensors
+        return dz * gout, None, None, None, None
+
+
 def u8_to_f32(x):
     """ToTensor's arithmetic on a uint8 device tensor: float(v) / 255 (dvae_u8_to_f32)."""
     x = x.contiguous()
@@ -500,13 +537,17 @@ class _SingleOptimizerLoss(BaseLoss):
     def _coefs(self, is_train):
         raise NotImplementedError
 
-    def _regulariser(self, buf, sc, B, D, is_train, stream):
+    def _regulariser(self, buf, sc, B, D, is_train, stream, *noise):
         """Hook of _device_step: launches on `stream` behind the loss epilogue that add a term to sc.scal[S_LOSS] -> its
         (dmu_x, dlv_x) for the FC chain's backward pass (None: no such term, no launch).  Only for steps whose epilogue is not
-        deferred (StepPolicy.late_join: beta-TCVAE and sharded steps), or the term would be added before the epilogue writes."""
+        deferred (StepPolicy.late_join: beta-TCVAE and sharded steps), or the term would be added before the epilogue writes.
+        noise: the tensors (or None: draw) of fused_step's `extra_noise`, in its order."""
         return None
 
-    def fused_step(self, data, model, optimizer, storer, eps=None):
+    def fused_step(self, data, model, optimizer, storer, eps=None, extra_noise=()):
+        """extra_noise: [(name, tensor or None)] -- injectable noise of a regulariser hook beyond eps (InfoVaeLoss: the prior
+        draws); it goes through _run_step's static buffers exactly as eps does and reaches _regulariser.  Empty for every
+        other loss: their inputs, launch order and draw order are what they were."""
         is_train = model.training
         storer = self._pre_call(is_train, storer)
         B, D = data.shape[0], model.latent_dim
@@ -518,15 +559,16 @@ class _SingleOptimizerLoss(BaseLoss):
         pol = self._begin_step(model, data)
         if self.KIND == _lib.LOSS_BTCVAE:
             sc.set_log_w(B * self._est_world()[0], self.n_data)
-        self._run_step(model, data, pol, [("eps", eps)], eps is not None, (),
-                       lambda data, eps: self._device_step(data, model, sc, eps, is_train))
+        inputs = [("eps", eps)] + list(extra_noise)
+        self._run_step(model, data, pol, inputs, any(t is not None for _, t in inputs), (),
+                       lambda data, eps, *noise: self._device_step(data, model, sc, eps, is_train, *noise))
         if is_train:
             model.assign_grads()          # optimizer.zero_grad(); loss.backward()  (training.py:156-157)
             optim.step(optimizer)         # optimizer.step(), training.py:158 (one launch for a stock Adam: disvae_amd/optim.py)
         self._store(storer, sc, D)
         return sc.scal[_lib.S_LOSS]
 
-    def _device_step(self, data, model, sc, eps, is_train):
+    def _device_step(self, data, model, sc, eps, is_train, *noise):
         """Forward + loss + backward as one stream of launches; no host-dependent values."""
         eng = model.engine
         B, D = data.shape[0], model.latent_dim
@@ -572,9 +614,9 @@ class _SingleOptimizerLoss(BaseLoss):
             elif btc:
                 eng._join_side()
             self._finish_loss(sc, klb, D, rowstats, B, None, Bg, s)
-        # a regulariser of the batch's (mu, logvar) beyond the KL term (DIP-VAE): its launches behind the epilogue on this
-        # stream, its gradients into the FC chain like the estimator's; nothing for the reference's losses
-        reg = self._regulariser(buf, sc, B, D, is_train, s)
+        # a regulariser of the batch's (mu, logvar) or latent sample beyond the KL term (DIP-VAE, InfoVAE): its launches behind
+        # the epilogue on this stream, its gradients into the FC chain like the estimator's; nothing for the reference's losses
+        reg = self._regulariser(buf, sc, B, D, is_train, s, *noise)
         if reg is not None:
             assert wait is None, "a regulariser hook behind a deferred epilogue"
             dmu, dlv = reg
@@ -694,6 +736,113 @@ class DipVaeLoss(_SingleOptimizerLoss):
         loss = rec_loss + anneal_reg * (self.beta * kl_loss) + dip_loss
         if storer is not None:
             storer['dip_loss'].append(dip_loss.item())
+            storer['loss'].append(loss.item())
+        return loss
+
+
+class InfoVaeLoss(_SingleOptimizerLoss):
+    """InfoVAE (Zhao, Song & Ermon 2019; alpha = 1: MMD-VAE; the MMD term is WAE-MMD's regulariser -- the reference has no
+    counterpart):
+
+        loss = rec + anneal * (1 - alpha) * KL + (alpha + lam - 1) * MMD_u(z, p)
+
+    rec and KL are BetaHLoss's with beta = 1 - alpha, and steps_anneal acts on the KL term as there; the MMD term is never
+    annealed.  z is the batch's latent sample (in evaluation: the mean), p are B x D standard-normal draws and MMD_u is the
+    unbiased U-statistic (include/dvae_mmd_hip.h; one image: 0) under kernel "imq" (WAE's sum of inverse multiquadrics) or
+    "rbf" with bandwidth `bandwidth` (None: 2 D, the expected squared distance of two prior draws).  The weight
+    alpha + lam - 1 may be any finite value.  `mmd_loss` logs the weighted term.
+
+    Noise: p follows the contract of eps -- drawn on the device after eps, into a buffer of its own, or injected
+    (fused_step(..., prior=...)).  An EVALUATION step of this loss also draws p (the five reference losses draw nothing in
+    evaluation).  The MMD couples the whole batch: data-parallel steps are not built (fused_step raises under a communicator
+    of more than one rank)."""
+    KIND = _lib.LOSS_BETAH
+    STORED = (('recon_loss', _lib.S_REC), ('kl_loss', _lib.S_KL), ('mmd_loss', None), ('loss', _lib.S_LOSS))
+
+    def __init__(self, alpha=0., lam=1000., kernel="imq", bandwidth=None, **kwargs):
+        super().__init__(**kwargs)
+        if kernel not in _mmdlib.KERNELS:
+            raise ValueError("kernel must be one of {}, got {!r}".format(sorted(_mmdlib.KERNELS), kernel))
+        self.alpha, self.lam, self.kernel = float(alpha), float(lam), kernel
+        if bandwidth is not None and not float(bandwidth) > 0:
+            raise ValueError("bandwidth must be positive, got {!r}".format(bandwidth))
+        self.bandwidth = None if bandwidth is None else float(bandwidth)
+        self._mmd = {}
+
+    @property
+    def beta(self):
+        return 1. - self.alpha
+
+    @property
+    def weight(self):
+        return self.alpha + self.lam - 1.
+
+    def _h(self, D):
+        return 2. * D if self.bandwidth is None else self.bandwidth
+
+    def _coefs(self, is_train):
+        anneal = linear_annealing(0, 1, self.n_train_steps, self.steps_anneal) if is_train else 1
+        return dict(ANNEAL=anneal, BETA=self.beta)
+
+    def _mmd_buf(self, device, name, n):
+        """fp64 buffers of the two launches, allocated once: ("ws", B, D) the workspace, ("out",) the value and the three sums."""
+        t = self._mmd.get((device,) + name)
+        if t is None:
+            _lib.note_alloc()
+            t = self._mmd[(device,) + name] = torch.zeros(n, dtype=torch.float64, device=device)
+        return t
+
+    def _regulariser(self, buf, sc, B, D, is_train, stream, prior=None):
+        """w MMD_u on top of the epilogue's rec + anneal * beta * KL in sc.scal[S_LOSS] (dvae_mmd_finish's loss_io: no third
+        launch) -> the gradients for the FC chain; evaluation: the value only."""
+        if prior is None:
+            prior = sc.latent("mmd_prior", B, D)
+            record_py(prior.normal_)               # after eps (training), alone in evaluation
+        ws = self._mmd_buf(sc.device, ("ws", B, D), _mmdlib.ws_doubles(B, D))
+        out = self._mmd_buf(sc.device, ("out",), _mmdlib.OUT_DOUBLES)
+        dmu = sc.latent("mmd_dmu", B, D) if is_train else None
+        dlv = sc.latent("mmd_dlv", B, D) if is_train else None
+        _mmd_launches(buf.z, prior, buf.mu, self.kernel, self._h(D), self.weight, ws, dmu, dlv, out,
+                      ptr(sc.scal) + 4 * _lib.S_LOSS, stream)
+        return dmu, dlv
+
+    def _replay_key(self, model, data, injected, pol):
+        return super()._replay_key(model, data, injected, pol) + (self.kernel, self.bandwidth, self.alpha, self.lam)
+
+    def _store(self, storer, sc, D, keys=None):
+        if storer is None:
+            return
+        vals = sc.scal.tolist()
+        mmd = self._mmd[(sc.device, "out")][0].item()           # fp64 [w MMD_u, MMD_u, S_zz, S_pp, S_zp]: a second small copy, on logging steps only
+        for key, slot in self.STORED:
+            if key == 'kl_loss':
+                self._store_kl(storer, vals, D)
+            else:
+                storer[key].append(mmd if key == 'mmd_loss' else vals[slot])
+
+    def fused_step(self, data, model, optimizer, storer, eps=None, prior=None):
+        if self._world()[0] > 1:
+            raise NotImplementedError(
+                "InfoVAE under data parallelism is not built: the MMD couples the GLOBAL batch, so a sharded step has to gather "
+                "the latent samples of every rank first, as the beta-TCVAE estimator does (Comm.all_gather_latents)")
+        return super().fused_step(data, model, optimizer, storer, eps=eps, extra_noise=[("mmd_prior_in", prior)])
+
+    def __call__(self, data, recon_data, latent_dist, is_train, storer, latent_sample=None):
+        if latent_sample is None:
+            if is_train:
+                raise ValueError("InfoVaeLoss needs latent_sample in training: the MMD term is a function of the sampled z")
+            latent_sample = latent_dist[0]                      # evaluation: the mean
+        storer = self._pre_call(is_train, storer)
+        sc = self.scratch(recon_data.device)
+        rec_loss = _reconstruction_loss(data, recon_data, storer=storer, distribution=self.rec_dist, scratch=sc)
+        kl_loss = _kl_normal_loss(*latent_dist, storer, scratch=sc)
+        D = latent_sample.shape[1]
+        prior = torch.empty_like(latent_sample).normal_()
+        mmd_loss = _MmdFn.apply(latent_sample, prior, self.kernel, self._h(D), self.weight)
+        anneal_reg = linear_annealing(0, 1, self.n_train_steps, self.steps_anneal) if is_train else 1
+        loss = rec_loss + anneal_reg * (self.beta * kl_loss) + mmd_loss
+        if storer is not None:
+            storer['mmd_loss'].append(mmd_loss.item())
             storer['loss'].append(loss.item())
         return loss
 
