@@ -7,7 +7,8 @@ include/.  Target "" is libdvae_hip.so, the training library; every other target
 nothing of one target is linked into another.  All targets share FLAGS and the up-to-date
 logic, each under a stamp of its own (build/flags.txt, build/flags_NAME.txt).  The module's X_LIB / X_SOURCES /
 X_HEADERS names (LIB / SOURCES / HEADERS for the training library) are derived from the table.
-PLUGIN_TARGETS is a second list of the same rows, built after TARGETS in the same way (see there).
+PLUGIN_TARGETS is a second list of the same rows, built after TARGETS in the same way (see there), and SCORE_PLUGIN_TARGETS a
+third, built after both.
 The libraries land in disentangling-vae_amd/lib/ (git-ignored build products).  Objects are rebuilt only
 when a source / header is newer or the flags changed.
 --debug (or DVAE_BUILD_DEBUG=1) adds -DDVAE_DEBUG_SWITCHES: the A/B / timing-ablation environment
@@ -43,6 +44,11 @@ TARGETS = [
 PLUGIN_TARGETS = [
     ("mmd", ["mmd_pairs"], "dvae_mmd_hip.h"),              # InfoVAE / MMD-VAE: the batch MMD against prior samples and its gradient (a TRAINING loss)
 ]
+# A score library added after the rows above were pinned: the same kind of row once more, built after the other two lists through the
+# same helper, and like PLUGIN_TARGETS out of ALL_SOURCES and tools/isa_identity.py.
+SCORE_PLUGIN_TARGETS = [
+    ("sep", ["latent_loo"], "dvae_sep_hip.h"),             # SEPIN / WSEPIN separability: leave-one-out joint entropies under the aggregate posterior
+]
 HEADERS = sorted(glob.glob(os.path.join(SRC, "*.h"))) + [os.path.join(HERE, "..", "include", "dvae_hip.h")]
 
 
@@ -53,7 +59,7 @@ def _target(name, sources, header):
     return os.path.join(HERE, "lib", "libdvae%s_hip.so" % infix), sources, headers, os.path.join(OBJ, "flags%s.txt" % infix)
 
 
-for _row in TARGETS + PLUGIN_TARGETS:        # LIB / SOURCES / HEADERS of the training library, EVAL_LIB / EVAL_SOURCES / EVAL_HEADERS, ... of the others
+for _row in TARGETS + PLUGIN_TARGETS + SCORE_PLUGIN_TARGETS:        # LIB / SOURCES / HEADERS of the training library, EVAL_LIB / EVAL_SOURCES / EVAL_HEADERS, ... of the others
     _prefix = _row[0].upper() + "_" if _row[0] else ""
     globals()[_prefix + "LIB"], globals()[_prefix + "SOURCES"], globals()[_prefix + "HEADERS"], _ = _target(*_row)
 ALL_SOURCES = [s for _, sources, _ in TARGETS for s in sources]
@@ -93,8 +99,15 @@ def _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose):
     return lib
 
 
+def _build_row(hipcc, name, sources, header, flags, debug, force, verbose):
+    """One row of a target list: its library under its own stamp."""
+    lib, sources, headers, stamp = _target(name, sources + (DEBUG_SOURCES if debug and not name else []), header)
+    _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose)
+
+
 def build(force=False, verbose=True, debug=None):
-    """Build every target of TARGETS, then of PLUGIN_TARGETS, in their order; returns the path of libdvae_hip.so."""
+    """Build every target of TARGETS, then of PLUGIN_TARGETS, then of SCORE_PLUGIN_TARGETS, in their order; returns the path of
+    libdvae_hip.so."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if debug is None:
         debug = os.environ.get("DVAE_BUILD_DEBUG", "0") == "1"
@@ -102,8 +115,9 @@ def build(force=False, verbose=True, debug=None):
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
     flags = FLAGS + (["-DDVAE_DEBUG_SWITCHES"] if debug else [])
     for name, sources, header in TARGETS + PLUGIN_TARGETS:
-        lib, sources, headers, stamp = _target(name, sources + (DEBUG_SOURCES if debug and not name else []), header)
-        _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose)
+        _build_row(hipcc, name, sources, header, flags, debug, force, verbose)
+    for name, sources, header in SCORE_PLUGIN_TARGETS:
+        _build_row(hipcc, name, sources, header, flags, debug, force, verbose)
     return LIB
 
 

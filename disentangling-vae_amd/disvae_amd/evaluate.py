@@ -56,6 +56,12 @@
   number without a copy of the table; the third ranks the class probabilities of the beta-VAE score's logistic regression with
   dvae_udr_ranks: a ROC AUC is a rank sum.  Written to downstream_task.log / fairness.log / explicitness.log by
   ``__call__(is_downstream=True, is_fairness=True, is_explicitness=True)``.
+* Separability and informativeness per latent, label-free (Do & Tran 2020: SEPIN, WSEPIN and their relatives), new
+  (``compute_separability_scores`` / ``separability_scores_from_entropies``): the per-dimension refinement of the total
+  correlation.  On the samples of the ELBO decomposition, the leave-one-out joint entropies H[z_!=i] of every latent and the joint
+  entropy from ONE pass over the S x N x D terms (libdvae_sep_hip.so), the marginal entropies by dvae_latent_entropy and the
+  conditional entropies per dimension; 3 D + 1 entropies cross to the host, where the scores are combined in fp64.
+  Written to separability_scores.log by ``__call__(is_separability=True)``.
 """
 import logging
 import math
@@ -66,7 +72,7 @@ from timeit import default_timer
 import numpy as np
 import torch
 
-from . import _dcilib, _evallib, _infolib, _irslib, _lib, _scorelib, _udrlib, _unsuplib
+from . import _dcilib, _evallib, _infolib, _irslib, _lib, _scorelib, _seplib, _udrlib, _unsuplib
 from ._lib import call, ptr
 from .engine import _stream
 from .likelihood import _ScorePasses, check_rec_dist, log_likelihood
@@ -87,6 +93,7 @@ DCI_FILE = "dci.log"
 DOWNSTREAM_TASK_FILE = "downstream_task.log"
 FAIRNESS_FILE = "fairness.log"
 EXPLICITNESS_FILE = "explicitness.log"
+SEPARABILITY_SCORES_FILE = "separability_scores.log"
 
 
 class Evaluator:
@@ -104,7 +111,8 @@ class Evaluator:
     def __call__(self, data_loader, is_metrics=False, is_losses=True, is_log_likelihood=False, n_samples=128,
                  is_decomposition=False, n_samples_decomposition=10000, is_scores=False, is_information=False,
                  is_irs=False, is_unsupervised=False, udr_models=None, is_dci=False, dci_args=None, is_downstream=False,
-                 is_fairness=False, is_explicitness=False, downstream_args=None, fairness_args=None, explicitness_args=None):
+                 is_fairness=False, is_explicitness=False, downstream_args=None, fairness_args=None, explicitness_args=None,
+                 is_separability=False, n_samples_separability=10000):
         """evaluate.py:60-95.  is_log_likelihood: also write compute_log_likelihood(data_loader, n_samples) to
         log_likelihood.log; is_decomposition: also write compute_elbo_decomposition(data_loader, n_samples_decomposition) to
         elbo_decomposition.log; is_scores: also write compute_factor_scores(data_loader) to factor_scores.log; is_information: also
@@ -115,7 +123,8 @@ class Evaluator:
         the reference's (metric, losses)); is_dci: also write compute_dci(data_loader, **dci_args), without its [D, K] matrix, to
         dci.log; is_downstream / is_fairness / is_explicitness: also write compute_downstream_task(data_loader, **downstream_args) to
         downstream_task.log, compute_fairness(data_loader, **fairness_args) to fairness.log and compute_explicitness(data_loader,
-        **explicitness_args) to explicitness.log, their arrays as lists."""
+        **explicitness_args) to explicitness.log, their arrays as lists; is_separability: also write
+        compute_separability_scores(data_loader, n_samples_separability) to separability_scores.log."""
         start = default_timer()
         is_still_training = self.model.training
         self.model.eval()
@@ -147,6 +156,9 @@ class Evaluator:
              'Fairness', FAIRNESS_FILE),
             (is_explicitness, 'the explicitness score', lambda: self.compute_explicitness(data_loader, **(explicitness_args or {})),
              nothing, 'Explicitness', EXPLICITNESS_FILE),
+            (is_separability, 'the separability scores',
+             lambda: self.compute_separability_scores(data_loader, n_samples=n_samples_separability), None, 'Separability scores',
+             SEPARABILITY_SCORES_FILE),
         ]
         written = {}
         for wanted, what, compute, left_out, label, filename in outputs:
@@ -214,6 +226,40 @@ class Evaluator:
         The draws (rows = randperm(N)[:S], eps ~ N(0, I)) come from a private generator seeded with `seed`: the same seed gives
         the same bits, the global random states are untouched; sample_idx ([S] rows, each in [0, N)) / eps ([S, D]) inject
         them.  Train / eval mode is restored.  The handful of scalars is combined on the host."""
+        table, n, dim, S, rows, noise, z = self._posterior_samples(dataloader, n_samples, seed, sample_idx, eps)
+        dev = table.mean.device
+
+        E = _evallib.lib()
+        out = torch.empty(3 * S + 3 + dim, dtype=torch.float32, device=dev)       # logqz, logqz_condx, logpz, H_z, 2 means, H_z_d
+        logqz, logqz_condx, logpz = out[:S], out[S:2 * S], out[2 * S:3 * S]
+        scal = out[3 * S:]
+        ws = torch.empty(max(E.dvae_eval_joint_logq_ws_floats(n, dim, S), _lib.lib().dvae_latent_entropy_ws_floats(n, dim, S)),
+                         dtype=torch.float32, device=dev)
+        st = _stream()
+        _evallib.call("dvae_eval_joint_logq", ptr(z), ptr(table.mean), ptr(table.logvar), n, dim, S, ptr(ws), ptr(logqz),
+                      ptr(scal), st)
+        _evallib.call("dvae_eval_sample_terms", ptr(z), ptr(noise), ptr(table.logvar), ptr(rows), n, dim, S, ptr(logqz_condx),
+                      ptr(logpz), scal.data_ptr() + 4, st)
+        # dvae_latent_entropy reads a [D, S] image whose row d must hold the S samples of z_d: the TRANSPOSED copy of the [S, D]
+        # samples.  This deliberately differs from _entropies below, which hands over the gathered [S, D] block as it lies in
+        # memory to reproduce the reference's MIG numbers (its .view is a reshape that mixes dimensions): here there is no
+        # reference to match, a reshape would evaluate q_d at samples of other dimensions and tc would not be 0 at D = 1.
+        z_ds = z.t().contiguous()
+        call("dvae_latent_entropy", ptr(z_ds), ptr(table.mean), ptr(table.logvar), n, dim, S, ptr(ws), scal.data_ptr() + 12, st)
+        host = [float(v) for v in scal.cpu().double()]                           # ONE device->host copy
+        H_z, mean_logqz_condx, mean_logpz, H_z_d = host[0], host[1], host[2], host[3:]
+        H_zCx = -mean_logqz_condx
+        mi = H_z - H_zCx
+        tc = math.fsum(H_z_d) - H_z
+        dw_kl = -math.fsum(H_z_d) - mean_logpz
+        return {"H_z": H_z, "H_z_d": H_z_d, "H_zCx": H_zCx, "mi": mi, "tc": tc, "dw_kl": dw_kl, "kl": mi + tc + dw_kl,
+                "n_samples": S, "n_data": n}
+
+    def _posterior_samples(self, dataloader, n_samples, seed, sample_idx, eps):
+        """What compute_elbo_decomposition and compute_separability_scores do before their kernels: the sizes and every check
+        (before any device work), the table of q(z|x) over the whole data set, and the draws -- rows = randperm(N)[:S] and
+        eps ~ N(0, I) from a private generator seeded with `seed`, or the injected sample_idx / eps -- so that the same seed
+        gives both methods the same samples.  -> (table, N, D, S, rows [S], noise [S, D], z [S, D])."""
         # every size is known and checked before any device work: a DataLoader tells the length of its data set, a plain
         # sequence of batches is counted
         ds = getattr(dataloader, "dataset", None)
@@ -245,32 +291,44 @@ class Evaluator:
         noise = torch.randn(S, dim, generator=gen, device=dev) if eps is None else eps.to(dev, torch.float32).contiguous()
         mean_s, logvar_s = table.select(rows)
         z = (mean_s + torch.exp(0.5 * logvar_s) * noise).contiguous()
+        return table, n, dim, S, rows, noise, z
 
-        E = _evallib.lib()
-        out = torch.empty(3 * S + 3 + dim, dtype=torch.float32, device=dev)       # logqz, logqz_condx, logpz, H_z, 2 means, H_z_d
-        logqz, logqz_condx, logpz = out[:S], out[S:2 * S], out[2 * S:3 * S]
-        scal = out[3 * S:]
-        ws = torch.empty(max(E.dvae_eval_joint_logq_ws_floats(n, dim, S), _lib.lib().dvae_latent_entropy_ws_floats(n, dim, S)),
+    # ------------------------------------------------------------------ SEPIN / WSEPIN separability
+    def compute_separability_scores(self, dataloader, n_samples=10000, seed=0, sample_idx=None, eps=None):
+        """Separability and informativeness of every latent WITHOUT labels (Do & Tran 2020): how much latent i tells about the
+        image that the other latents do not tell already, sepin[i] = I(x; z_i | z_!=i), its informativeness-weighted sum WSEPIN
+        and what goes with them (separability_scores_from_entropies below), from entropies under the aggregate posterior of ALL
+        N images of the loader, estimated on the S samples compute_elbo_decomposition draws (same arguments, checks, draws and
+        error texts: the same seed gives both the same samples):
+
+            H_loo[i]    = -1/S sum_s log q_!=i(z_s)         leave-one-out joint entropies, and
+            H_z         = -1/S sum_s log q(z_s)             the joint entropy from the same pass  (dvae_sep_loo_logq)
+            H_z_d[i]    = -1/S sum_s log q_i(z_si)          marginal entropies      (dvae_latent_entropy on the [D, S] image of z)
+            H_cond_d[i] = -1/S sum_s log q(z_si | x_n(s))   conditional entropies   (dvae_sep_cond_terms)
+
+        Returns the scores plus H_z, H_z_d, H_loo, H_cond_d, tc, n_samples, n_data.  A latent_dim above the kernels' largest
+        raises ValueError before the encode pass.  Train / eval mode is restored; the scores are combined on the host in fp64."""
+        dim = int(self.model.latent_dim)
+        if dim > _seplib.MAX_D:
+            raise ValueError("%d latent dimensions: the separability kernels take at most %d" % (dim, _seplib.MAX_D))
+        table, n, dim, S, rows, noise, z = self._posterior_samples(dataloader, n_samples, seed, sample_idx, eps)
+        dev = table.mean.device
+        P = _seplib.lib()
+        out64 = torch.empty(2 * dim + 1, dtype=torch.float64, device=dev)         # H_loo [D], H_z, H_cond_d [D]
+        buf = torch.empty((dim + 1) * S + dim, dtype=torch.float32, device=dev)   # logq [D + 1, S], H_z_d [D]
+        logq, H_z_d = buf[:(dim + 1) * S], buf[(dim + 1) * S:]
+        ws = torch.empty(max(P.dvae_sep_loo_logq_ws_floats(n, dim, S), _lib.lib().dvae_latent_entropy_ws_floats(n, dim, S)),
                          dtype=torch.float32, device=dev)
         st = _stream()
-        _evallib.call("dvae_eval_joint_logq", ptr(z), ptr(table.mean), ptr(table.logvar), n, dim, S, ptr(ws), ptr(logqz),
-                      ptr(scal), st)
-        _evallib.call("dvae_eval_sample_terms", ptr(z), ptr(noise), ptr(table.logvar), ptr(rows), n, dim, S, ptr(logqz_condx),
-                      ptr(logpz), scal.data_ptr() + 4, st)
-        # dvae_latent_entropy reads a [D, S] image whose row d must hold the S samples of z_d: the TRANSPOSED copy of the [S, D]
-        # samples.  This deliberately differs from _entropies below, which hands over the gathered [S, D] block as it lies in
-        # memory to reproduce the reference's MIG numbers (its .view is a reshape that mixes dimensions): here there is no
-        # reference to match, a reshape would evaluate q_d at samples of other dimensions and tc would not be 0 at D = 1.
-        z_ds = z.t().contiguous()
-        call("dvae_latent_entropy", ptr(z_ds), ptr(table.mean), ptr(table.logvar), n, dim, S, ptr(ws), scal.data_ptr() + 12, st)
-        host = [float(v) for v in scal.cpu().double()]                           # ONE device->host copy
-        H_z, mean_logqz_condx, mean_logpz, H_z_d = host[0], host[1], host[2], host[3:]
-        H_zCx = -mean_logqz_condx
-        mi = H_z - H_zCx
-        tc = math.fsum(H_z_d) - H_z
-        dw_kl = -math.fsum(H_z_d) - mean_logpz
-        return {"H_z": H_z, "H_z_d": H_z_d, "H_zCx": H_zCx, "mi": mi, "tc": tc, "dw_kl": dw_kl, "kl": mi + tc + dw_kl,
-                "n_samples": S, "n_data": n}
+        _seplib.call("dvae_sep_loo_logq", ptr(z), ptr(table.mean), ptr(table.logvar), n, dim, S, ptr(ws), ptr(logq), ptr(out64), st)
+        _seplib.call("dvae_sep_cond_terms", ptr(noise), ptr(table.logvar), ptr(rows), n, dim, S, out64.data_ptr() + 8 * (dim + 1), st)
+        z_ds = z.t().contiguous()                            # the [D, S] image, as compute_elbo_decomposition hands it over
+        call("dvae_latent_entropy", ptr(z_ds), ptr(table.mean), ptr(table.logvar), n, dim, S, ptr(ws), ptr(H_z_d), st)
+        host = torch.cat([out64, H_z_d.double()]).cpu().tolist()                  # ONE device->host copy
+        H_loo, H_z, H_cond_d, H_marg = host[:dim], host[dim], host[dim + 1:2 * dim + 1], host[2 * dim + 1:]
+        scores = separability_scores_from_entropies(H_z, H_marg, H_loo, H_cond_d)
+        scores.update(H_z=H_z, H_z_d=H_marg, H_loo=H_loo, H_cond_d=H_cond_d, n_samples=S, n_data=n)
+        return scores
 
     # ------------------------------------------------------------------ FactorVAE / beta-VAE scores
     def compute_factor_scores(self, dataloader, n_train=10000, n_eval=5000, batch_size=64, n_variance=10000,
@@ -504,6 +562,43 @@ def disentanglement_scores(H_z, H_zCv, lat_sizes):
     aam_k = torch.where(best > 0, (best - others).clamp(min=0) / best, torch.zeros_like(best))
     return {"marginal_entropies": H_z, "cond_entropies": H_zCv, "mig_k": mig_k, "mig": mig_k.mean(),
             "aam_k": aam_k, "aam": aam_k.mean()}
+
+
+def separability_scores_from_entropies(H_z, H_z_d, H_loo, H_cond_d):
+    """The scores of Do & Tran 2020 from entropies under the aggregate posterior, combined in fp64 (python floats; arrays come
+    back as lists): H_z = H(z), H_z_d[i] = H(z_i), H_loo[i] = H(z_!=i) (D = 1: 0), H_cond_d[i] = H(z_i | x).  q(z|x) is factorised,
+    so H(z_A | x) = sum_{d in A} H_cond_d[d]:
+
+        informativeness[i] = I(x; z_i)        = H_z_d[i] - H_cond_d[i]
+        mi                 = I(x; z)          = H_z - sum_d H_cond_d[d]
+        mi_loo[i]          = I(x; z_!=i)      = H_loo[i] - sum_{d != i} H_cond_d[d]
+        sepin[i]           = I(x; z_i | z_!=i) = mi - mi_loo[i]
+        redundancy[i]      = I(z_i; z_!=i)    = H_z_d[i] + H_loo[i] - H_z            (sepin = informativeness - redundancy)
+        rho[i]             = max(informativeness[i], 0) / sum_j max(informativeness[j], 0)      (all zero: rho = 0, wsepin = 0)
+        wsepin             = sum_i rho[i] sepin[i]
+        sepin_at_k[k-1]    = mean of the k largest sepin[i]
+        dtc                = sum_i H_loo[i] - (D - 1) H_z      (dual total correlation);  tc = sum_i H_z_d[i] - H_z
+
+    Nothing is clamped except inside rho: these are estimates and may come out slightly negative."""
+    H_z = float(H_z)
+    H_z_d, H_loo, H_cond_d = ([float(v) for v in h] for h in (H_z_d, H_loo, H_cond_d))
+    dim = len(H_z_d)
+    if dim < 1 or len(H_loo) != dim or len(H_cond_d) != dim:
+        raise ValueError("H_z_d, H_loo and H_cond_d must hold one entropy per latent dimension, got %d, %d and %d"
+                         % (dim, len(H_loo), len(H_cond_d)))
+    informativeness = [H_z_d[i] - H_cond_d[i] for i in range(dim)]
+    mi = H_z - math.fsum(H_cond_d)
+    mi_loo = [H_loo[i] - math.fsum(H_cond_d[:i] + H_cond_d[i + 1:]) for i in range(dim)]
+    sepin = [mi - mi_loo[i] for i in range(dim)]
+    redundancy = [H_z_d[i] + H_loo[i] - H_z for i in range(dim)]
+    weight = [max(v, 0.0) for v in informativeness]
+    total = math.fsum(weight)
+    rho = [w / total for w in weight] if total > 0.0 else [0.0] * dim
+    wsepin = math.fsum(r * v for r, v in zip(rho, sepin))
+    ranked = sorted(sepin, reverse=True)
+    sepin_at_k = [math.fsum(ranked[:k]) / k for k in range(1, dim + 1)]
+    return {"sepin": sepin, "wsepin": wsepin, "sepin_at_k": sepin_at_k, "informativeness": informativeness, "redundancy": redundancy,
+            "rho": rho, "mi": mi, "mi_loo": mi_loo, "dtc": math.fsum(H_loo) - (dim - 1) * H_z, "tc": math.fsum(H_z_d) - H_z}
 
 
 # ---------------------------------------------------------------------- lines that the _check_* functions below share
