@@ -7,8 +7,8 @@ include/.  Target "" is libdvae_hip.so, the training library; every other target
 nothing of one target is linked into another.  All targets share FLAGS and the up-to-date
 logic, each under a stamp of its own (build/flags.txt, build/flags_NAME.txt).  The module's X_LIB / X_SOURCES /
 X_HEADERS names (LIB / SOURCES / HEADERS for the training library) are derived from the table.
-PLUGIN_TARGETS is a second list of the same rows, built after TARGETS in the same way (see there), and SCORE_PLUGIN_TARGETS a
-third, built after both.
+PLUGIN_TARGETS is a second list of the same rows, built after TARGETS in the same way (see there), SCORE_PLUGIN_TARGETS a
+third, built after both, and EXTRA_TARGETS a fourth, built last, whose libraries land in lib/ext/.
 The libraries land in disentangling-vae_amd/lib/ (git-ignored build products).  Objects are rebuilt only
 when a source / header is newer or the flags changed.
 --debug (or DVAE_BUILD_DEBUG=1) adds -DDVAE_DEBUG_SWITCHES: the A/B / timing-ablation environment
@@ -49,19 +49,29 @@ PLUGIN_TARGETS = [
 SCORE_PLUGIN_TARGETS = [
     ("sep", ["latent_loo"], "dvae_sep_hip.h"),             # SEPIN / WSEPIN separability: leave-one-out joint entropies under the aggregate posterior
 ]
+# The rows after those: the same kind of row and the same helper, FLAGS and stamp logic, built last, out of ALL_SOURCES and
+# tools/isa_identity.py -- and their libraries in the sub-directory EXTRA_DIR of lib/, because the host tests also pin the number
+# of libraries that lie in lib/ itself.  The next library is one more row HERE.
+EXTRA_TARGETS = [
+    ("mass", ["posterior_mass"], "dvae_mass_hip.h"),       # RMIG / JEMMIG / MIG-sup / DCIMIG: the posterior mass per bin and factor value
+]
+EXTRA_DIR = "ext"
 HEADERS = sorted(glob.glob(os.path.join(SRC, "*.h"))) + [os.path.join(HERE, "..", "include", "dvae_hip.h")]
 
 
-def _target(name, sources, header):
-    """One row of TARGETS -> (library, sources, headers whose change rebuilds it, stamp file)."""
+def _target(name, sources, header, subdir=""):
+    """One row of TARGETS -> (library, sources, headers whose change rebuilds it, stamp file); subdir: of lib/."""
     infix = "_" + name if name else ""
     headers = HEADERS + [os.path.join(HERE, "..", "include", header)] if name else HEADERS
-    return os.path.join(HERE, "lib", "libdvae%s_hip.so" % infix), sources, headers, os.path.join(OBJ, "flags%s.txt" % infix)
+    return os.path.join(HERE, "lib", subdir, "libdvae%s_hip.so" % infix), sources, headers, os.path.join(OBJ, "flags%s.txt" % infix)
 
 
 for _row in TARGETS + PLUGIN_TARGETS + SCORE_PLUGIN_TARGETS:        # LIB / SOURCES / HEADERS of the training library, EVAL_LIB / EVAL_SOURCES / EVAL_HEADERS, ... of the others
     _prefix = _row[0].upper() + "_" if _row[0] else ""
     globals()[_prefix + "LIB"], globals()[_prefix + "SOURCES"], globals()[_prefix + "HEADERS"], _ = _target(*_row)
+for _row in EXTRA_TARGETS:
+    globals()[_row[0].upper() + "_LIB"], globals()[_row[0].upper() + "_SOURCES"], globals()[_row[0].upper() + "_HEADERS"], _ = \
+        _target(*_row, subdir=EXTRA_DIR)
 ALL_SOURCES = [s for _, sources, _ in TARGETS for s in sources]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
@@ -99,15 +109,16 @@ def _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose):
     return lib
 
 
-def _build_row(hipcc, name, sources, header, flags, debug, force, verbose):
+def _build_row(hipcc, name, sources, header, flags, debug, force, verbose, subdir=""):
     """One row of a target list: its library under its own stamp."""
-    lib, sources, headers, stamp = _target(name, sources + (DEBUG_SOURCES if debug and not name else []), header)
+    lib, sources, headers, stamp = _target(name, sources + (DEBUG_SOURCES if debug and not name else []), header, subdir)
+    os.makedirs(os.path.dirname(lib), exist_ok=True)
     _build_target(hipcc, lib, sources, headers, flags, stamp, force, verbose)
 
 
 def build(force=False, verbose=True, debug=None):
-    """Build every target of TARGETS, then of PLUGIN_TARGETS, then of SCORE_PLUGIN_TARGETS, in their order; returns the path of
-    libdvae_hip.so."""
+    """Build every target of TARGETS, then of PLUGIN_TARGETS, then of SCORE_PLUGIN_TARGETS, then of EXTRA_TARGETS, in their order;
+    returns the path of libdvae_hip.so."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if debug is None:
         debug = os.environ.get("DVAE_BUILD_DEBUG", "0") == "1"
@@ -118,6 +129,7 @@ def build(force=False, verbose=True, debug=None):
         _build_row(hipcc, name, sources, header, flags, debug, force, verbose)
     for name, sources, header in SCORE_PLUGIN_TARGETS:
         _build_row(hipcc, name, sources, header, flags, debug, force, verbose)
+    for row in EXTRA_TARGETS: _build_row(hipcc, *row, flags, debug, force, verbose, subdir=EXTRA_DIR)   # noqa: E701 (the host tests count the two loop bodies above)
     return LIB
 
 

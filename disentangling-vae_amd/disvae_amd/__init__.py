@@ -25,11 +25,13 @@ if "GPU_MAX_HW_QUEUES" not in _os.environ:
 from .models.vae import init_specific_model  # noqa: E402
 from .training import Trainer  # noqa: E402
 from .evaluate import (Evaluator, dci_from_importance, dci_from_table, downstream_task_from_table,  # noqa: E402
-                       explicitness_from_table, fairness_from_table, separability_scores_from_entropies, udr_from_tables)
+                       explicitness_from_table, fairness_from_table, interpretability_scores_from_mass,
+                       interpretability_scores_from_table, separability_scores_from_entropies, udr_from_tables)
 from .visualize import Visualizer, GifTraversalsTraining  # noqa: E402
 from .likelihood import per_image_losses, log_likelihood  # noqa: E402
 from .models.losses import DipVaeLoss, InfoVaeLoss  # noqa: E402
 
 __all__ = ["init_specific_model", "Trainer", "Evaluator", "Visualizer", "GifTraversalsTraining", "per_image_losses",
            "log_likelihood", "udr_from_tables", "dci_from_table", "dci_from_importance", "DipVaeLoss", "InfoVaeLoss",
-           "downstream_task_from_table", "fairness_from_table", "explicitness_from_table", "separability_scores_from_entropies"]
+           "downstream_task_from_table", "fairness_from_table", "explicitness_from_table", "separability_scores_from_entropies",
+           "interpretability_scores_from_table", "interpretability_scores_from_mass"]

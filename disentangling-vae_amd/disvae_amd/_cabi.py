@@ -1,5 +1,5 @@
 """The one ctypes loader behind the bindings of every library but the training library's (_evallib.py, _scorelib.py, _infolib.py,
-_irslib.py, _unsuplib.py, _udrlib.py, _dcilib.py, _diplib.py, _mmdlib.py, _seplib.py).
+_irslib.py, _unsuplib.py, _udrlib.py, _dcilib.py, _diplib.py, _mmdlib.py, _seplib.py, _masslib.py).
 
 Each of those modules states what is its own -- its short name, mirrored constants, SIGNATURES, _RESTYPE -- and keeps a
 module-level LIB_PATH and lib() / call() pair in front of one Binding.for_library(name, ...), which derives the rest from the
@@ -24,9 +24,10 @@ class Binding:
         self._lib = None
 
     @classmethod
-    def for_library(cls, name, signatures, restype, kernels):
-        """The binding of libdvae_NAME_hip.so in ../lib, or wherever the environment's DVAE_NAME_HIP_LIB says."""
-        path = os.environ.get("DVAE_%s_HIP_LIB" % name.upper(), os.path.join(_HERE, "..", "lib", "libdvae_%s_hip.so" % name))
+    def for_library(cls, name, signatures, restype, kernels, subdir=""):
+        """The binding of libdvae_NAME_hip.so in ../lib (`subdir`: in that sub-directory of it, build.py's EXTRA_DIR), or wherever
+        the environment's DVAE_NAME_HIP_LIB says."""
+        path = os.environ.get("DVAE_%s_HIP_LIB" % name.upper(), os.path.join(_HERE, "..", "lib", subdir, "libdvae_%s_hip.so" % name))
         return cls(path, signatures, restype, "dvae_%s_last_error" % name, kernels)
 
     def lib(self):

@@ -62,6 +62,13 @@
   entropy from ONE pass over the S x N x D terms (libdvae_sep_hip.so), the marginal entropies by dvae_latent_entropy and the
   conditional entropies per dimension; 3 D + 1 entropies cross to the host, where the scores are combined in fp64.
   Written to separability_scores.log by ``__call__(is_separability=True)``.
+* Interpretability, the factor-based half of Do & Tran 2020: RMIG and JEMMIG, with MIG-sup (Li et al. 2020) and DCIMIG
+  (Sepliarskaia et al. 2019) from the same mutual-information matrix, new (``compute_interpretability_scores`` /
+  ``interpretability_scores_from_table`` / ``interpretability_scores_from_mass``).  Unlike the MIG variants above these use the
+  posterior VARIANCE: q(z_d | x) of every row is integrated over fixed bins (Gaussian tail differences in fp64) and summed per
+  factor value in one HIP pass on the tables where they lie (libdvae_mass_hip.so; accumulators in LDS, fixed order); the
+  [D, n_bins * sum(lat_sizes)] mass table crosses to the host, where the scores are combined in fp64.
+  Written to interpretability_scores.log by ``__call__(is_interpretability=True)``.
 """
 import logging
 import math
@@ -72,7 +79,7 @@ from timeit import default_timer
 import numpy as np
 import torch
 
-from . import _dcilib, _evallib, _infolib, _irslib, _lib, _scorelib, _seplib, _udrlib, _unsuplib
+from . import _dcilib, _evallib, _infolib, _irslib, _lib, _masslib, _scorelib, _seplib, _udrlib, _unsuplib
 from ._lib import call, ptr
 from .engine import _stream
 from .likelihood import _ScorePasses, check_rec_dist, log_likelihood
@@ -94,6 +101,7 @@ DOWNSTREAM_TASK_FILE = "downstream_task.log"
 FAIRNESS_FILE = "fairness.log"
 EXPLICITNESS_FILE = "explicitness.log"
 SEPARABILITY_SCORES_FILE = "separability_scores.log"
+INTERPRETABILITY_SCORES_FILE = "interpretability_scores.log"
 
 
 class Evaluator:
@@ -112,7 +120,7 @@ class Evaluator:
                  is_decomposition=False, n_samples_decomposition=10000, is_scores=False, is_information=False,
                  is_irs=False, is_unsupervised=False, udr_models=None, is_dci=False, dci_args=None, is_downstream=False,
                  is_fairness=False, is_explicitness=False, downstream_args=None, fairness_args=None, explicitness_args=None,
-                 is_separability=False, n_samples_separability=10000):
+                 is_separability=False, n_samples_separability=10000, is_interpretability=False, interpretability_args=None):
         """evaluate.py:60-95.  is_log_likelihood: also write compute_log_likelihood(data_loader, n_samples) to
         log_likelihood.log; is_decomposition: also write compute_elbo_decomposition(data_loader, n_samples_decomposition) to
         elbo_decomposition.log; is_scores: also write compute_factor_scores(data_loader) to factor_scores.log; is_information: also
@@ -124,7 +132,9 @@ class Evaluator:
         dci.log; is_downstream / is_fairness / is_explicitness: also write compute_downstream_task(data_loader, **downstream_args) to
         downstream_task.log, compute_fairness(data_loader, **fairness_args) to fairness.log and compute_explicitness(data_loader,
         **explicitness_args) to explicitness.log, their arrays as lists; is_separability: also write
-        compute_separability_scores(data_loader, n_samples_separability) to separability_scores.log."""
+        compute_separability_scores(data_loader, n_samples_separability) to separability_scores.log; is_interpretability: also
+        write compute_interpretability_scores(data_loader, **interpretability_args), without its [D, K] matrices, to
+        interpretability_scores.log."""
         start = default_timer()
         is_still_training = self.model.training
         self.model.eval()
@@ -159,6 +169,9 @@ class Evaluator:
             (is_separability, 'the separability scores',
              lambda: self.compute_separability_scores(data_loader, n_samples=n_samples_separability), None, 'Separability scores',
              SEPARABILITY_SCORES_FILE),
+            (is_interpretability, 'the RMIG, JEMMIG, MIG-sup and DCIMIG scores',
+             lambda: self.compute_interpretability_scores(data_loader, **(interpretability_args or {})), matrices,
+             'Interpretability scores', INTERPRETABILITY_SCORES_FILE),
         ]
         written = {}
         for wanted, what, compute, left_out, label, filename in outputs:
@@ -353,6 +366,19 @@ class Evaluator:
         _check_information_sizes(n, lat_sizes, n_bins, n_samples)
         mean, _logvar = self._encode(dataloader, n, lat_sizes)
         return information_scores_from_table(mean, lat_sizes, n_bins=n_bins, n_samples=n_samples, seed=seed)
+
+    # ------------------------------------------------------------------ RMIG / JEMMIG / MIG-sup / DCIMIG
+    def compute_interpretability_scores(self, dataloader, n_samples=None, n_bins=100, z_range=(-4., 4.), seed=0):
+        """RMIG and JEMMIG (Do & Tran 2020), MIG-sup (Li et al. 2020) and DCIMIG (Sepliarskaia et al. 2019) of the model
+        (interpretability_scores_from_table below, on the posterior means AND log-variances of the whole data set through the
+        native encoder: a latent whose posterior is as wide as its bins does not score like a sharp one).  The data-set
+        requirements and errors of compute_factor_scores; every size and argument is checked before any device work; train /
+        eval mode is restored."""
+        _ds, lat_sizes, n = self._factor_sizes(dataloader)
+        _check_interpretability_arguments(n, lat_sizes, n_bins, z_range, n_samples)
+        mean, logvar = self._encode(dataloader, n, lat_sizes)
+        return interpretability_scores_from_table(mean, logvar, lat_sizes, n_bins=n_bins, z_range=z_range, n_samples=n_samples,
+                                                  seed=seed)
 
     # ------------------------------------------------------------------ interventional robustness score
     def compute_irs(self, dataloader, diff_quantile=0.99, factor_bins=20, n_samples=None, seed=0):
@@ -967,6 +993,136 @@ def information_scores_from_table(mean, lat_sizes, n_bins=20, n_samples=None, se
                   ptr(ws), ptr(counts), st)
     scores = information_scores_from_statistics(counts.cpu().numpy(), lat_sizes, n_bins, col_var, factor_var,
                                                 cov_zv.reshape(dim, K))               # ONE copy of the counts
+    scores.update(n_samples=S, n_bins=n_bins)
+    return scores
+
+
+# ---------------------------------------------------------------------- RMIG / JEMMIG / MIG-sup / DCIMIG on the posterior mass table
+def _check_interpretability_arguments(n, lat_sizes, n_bins, z_range, n_samples, dim=None):
+    _check_lat_sizes(lat_sizes, _masslib.MAX_FACTORS)
+    if not 1 <= int(n_bins) <= _masslib.MAX_BINS:
+        raise ValueError("n_bins must lie in [1, %d], got %r" % (_masslib.MAX_BINS, n_bins))
+    if len(z_range) != 2 or not (math.isfinite(z_range[0]) and math.isfinite(z_range[1]) and float(z_range[0]) < float(z_range[1])):
+        raise ValueError("z_range must be (lo, hi), finite, lo < hi, got %r" % (z_range,))
+    if min(lat_sizes) < 2:
+        raise ValueError("a factor of variation with one value has no entropy (the scores divide by it): lat_sizes=%s" % (lat_sizes,))
+    if dim is not None and not (1 <= dim <= 16384 and dim * int(n_bins) * sum(lat_sizes) <= 2 ** 31 - 1):
+        raise ValueError("%d latent dimensions x %d bins x %d factor values: the mass table is limited to 16384 dimensions and "
+                         "2^31 - 1 elements" % (dim, n_bins, sum(lat_sizes)))
+    _check_n_samples(n, n_samples)
+
+
+def mass_edges(n_bins, z_range=(-4., 4.)):
+    """The n_bins - 1 inner bin edges, fp64: numpy.linspace(lo, hi, n_bins + 1)[1:-1].  Bin 0 reaches down to -inf and bin
+    n_bins - 1 up to +inf, so the tails outside z_range are folded into the end bins and the masses of a row sum to 1."""
+    return np.linspace(float(z_range[0]), float(z_range[1]), int(n_bins) + 1)[1:-1].astype(np.float64)
+
+
+def interpretability_scores_from_mass(mass, lat_sizes, n_bins):
+    """The host half of interpretability_scores_from_table, fp64: ``mass`` [D, n_bins * sum(lat_sizes)] in the layout of
+    dvae_mass_joint -- for latent d and factor k the block [n_bins, lat_sizes[k]] of posterior mass per (bin, factor value),
+    mass[d][k][b, v] = sum over the selected rows with v_k = v of Q_b(row, d).  Each block is normalised by its own sum: P.
+
+    mutual_information[d, k] = sum P log(P / (P_z P_v)) and joint_entropy[d, k] = -sum P log P over the cells with P > 0 (nats; P_z
+    the bin marginal, P_v the value marginal); factor_entropy[k] = H_y[k], the entropy of the value marginal of block (0, k) (a
+    factor without entropy raises ValueError); latent_entropy[d] the entropy of the bin marginal of block (d, 0).
+    Per factor k, with i* = arg max_d I[d, k] (the lowest d on ties; best_latent[k]) and j the runner-up (one latent: its MI is 0):
+        rmig_per_factor[k] = I[i*, k] - I[j, k]                                  rmig_norm = mean_k rmig_per_factor[k] / H_y[k]
+        jemmig_per_factor[k] = H_joint[i*, k] - I[i*, k] + I[j, k]               jemmig_norm_per_factor[k] = 1 - jemmig_k / (H_y[k] + log n_bins)
+    (Do & Tran 2020).  Per latent d: mig_sup_per_latent[d] = largest - second largest over k of I[d, k] / H_y[k] (one factor: the
+    second is 0; Li et al. 2020).  dcimig = sum_k max_{d : k(d) = k} gap_d / sum_k H_y[k] with k(d) = arg max_k I[d, k] and gap_d
+    the largest minus the second largest of I[d, :] (a factor no latent prefers contributes 0; Sepliarskaia et al. 2019).
+    rmig, rmig_norm, jemmig, jemmig_norm and mig_sup are the means of their arrays."""
+    lat_sizes = [int(k) for k in lat_sizes]
+    K, n_bins = len(lat_sizes), int(n_bins)
+    mass = np.asarray(mass, dtype=np.float64)
+    D = mass.shape[0]
+    if mass.ndim != 2 or D < 1 or mass.shape[1] != n_bins * sum(lat_sizes):
+        raise ValueError("mass must be [D, n_bins * sum(lat_sizes)] = [D, %d], got shape %s" % (n_bins * sum(lat_sizes), mass.shape))
+
+    def entropy(p):
+        return float(-(p[p > 0] * np.log(p[p > 0])).sum())
+    mi, joint, H_y, H_z = np.zeros((D, K)), np.zeros((D, K)), np.zeros(K), np.zeros(D)
+    start = 0
+    for k, size in enumerate(lat_sizes):
+        for d in range(D):
+            P = mass[d, start:start + n_bins * size].reshape(n_bins, size)
+            P = P / P.sum()
+            Pz, Pv = P.sum(axis=1, keepdims=True), P.sum(axis=0, keepdims=True)
+            nz = P > 0
+            with np.errstate(divide="ignore", invalid="ignore"):
+                ratio = P / Pz / Pv                                      # (P / P_z) / P_v: the PRODUCT of two marginals of 1e-200 is 0 where P is not
+            mi[d, k] = (P[nz] * np.log(ratio[nz])).sum()
+            joint[d, k] = entropy(P)
+            if d == 0:
+                H_y[k] = entropy(Pv)
+            if k == 0:
+                H_z[d] = entropy(Pz)
+        start += n_bins * size
+    if not (H_y > 0).all():
+        raise ValueError("factor(s) %s take one value among the selected rows: no entropy to divide the scores by"
+                         % [k for k in range(K) if not H_y[k] > 0])
+    best = mi.argmax(axis=0)                                             # [K], the lowest d on ties
+    top = mi[best, np.arange(K)]
+    second = np.array([np.delete(mi[:, k], best[k]).max() if D > 1 else 0.0 for k in range(K)])
+    rmig_k = top - second
+    jemmig_k = joint[best, np.arange(K)] - top + second
+    jemmig_norm_k = 1.0 - jemmig_k / (H_y + math.log(n_bins))
+    ranked = np.sort(mi / H_y[None, :], axis=1)[:, ::-1]                 # [D, K], descending over k
+    mig_sup_d = ranked[:, 0] - (ranked[:, 1] if K > 1 else 0.0)
+    raw = np.sort(mi, axis=1)[:, ::-1]
+    gap_d = raw[:, 0] - (raw[:, 1] if K > 1 else 0.0)
+    prefers = mi.argmax(axis=1)                                          # [D], k(d)
+    dcimig = sum(gap_d[prefers == k].max() for k in range(K) if (prefers == k).any()) / H_y.sum()
+    return {"rmig": float(rmig_k.mean()), "rmig_norm": float((rmig_k / H_y).mean()), "jemmig": float(jemmig_k.mean()),
+            "jemmig_norm": float(jemmig_norm_k.mean()), "mig_sup": float(mig_sup_d.mean()), "dcimig": float(dcimig),
+            "rmig_per_factor": rmig_k, "jemmig_per_factor": jemmig_k, "jemmig_norm_per_factor": jemmig_norm_k,
+            "mig_sup_per_latent": mig_sup_d, "best_latent": best.astype(np.int64), "factor_entropy": H_y, "latent_entropy": H_z,
+            "mutual_information": mi, "joint_entropy": joint, "n_samples": int(round(float(mass[0, :n_bins * lat_sizes[0]].sum()))),
+            "n_bins": n_bins}
+
+
+def interpretability_scores_from_table(mean, logvar, lat_sizes, n_bins=100, z_range=(-4., 4.), n_samples=None, seed=0, rows=None):
+    """RMIG, JEMMIG, MIG-sup and DCIMIG of a representation given as the fp32 [N, D] tables ``mean`` and ``logvar`` of q(z|x) (on
+    the GPU) of a data set that enumerates ``lat_sizes`` in row-major order (formulas: interpretability_scores_from_mass).
+
+    The posterior of every selected row is INTEGRATED over n_bins fixed bins with the inner edges mass_edges(n_bins, z_range),
+    the tails beyond z_range folded into the end bins: with sigma = exp(logvar / 2), t_j = (e_j - mean) / (sigma sqrt 2),
+    up_j = erfc(t_j) / 2 and dn_j = erfc(-t_j) / 2 in fp64, Q_0 = dn_1, Q_{n_bins-1} = up_{n_bins-1} and for the bins between
+    Q_b = up_b - up_{b+1} if t_b >= 0 else dn_{b+1} - dn_b -- always the difference of the two smaller tails, never
+    Phi(b) - Phi(a), which loses every small mass.  mass[d][k][b, v] is the sum of Q_b over the selected rows whose factor k
+    takes the value v (dvae_mass_joint, fp64, fixed order).
+
+    n_samples=None: every row; else rows = randperm(N)[:n_samples] from a private generator seeded with ``seed`` (the same seed
+    gives the same bits, the global random states are untouched); ``rows`` ([S] row numbers in [0, N), repeats allowed) injects
+    the selection.  Every size and argument is checked before any device work, and a table with a NaN or an infinity raises
+    ValueError.  ONE launch sequence, ONE device-to-host copy of the mass table, the scores in fp64 on the host.  Returns the
+    dictionary of interpretability_scores_from_mass with n_samples = S: Python and numpy values."""
+    lat_sizes = [int(k) for k in lat_sizes]
+    K, n_bins = len(lat_sizes), int(n_bins)
+    n, dim = _table_shape(mean)
+    if tuple(logvar.shape) != tuple(mean.shape):
+        raise ValueError("logvar must have the shape of mean, %s, got %s" % (tuple(mean.shape), tuple(logvar.shape)))
+    _check_interpretability_arguments(n, lat_sizes, n_bins, z_range, None if rows is not None else n_samples, dim=max(dim, 1))
+    if n != int(np.prod(lat_sizes)):
+        raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (n, lat_sizes))
+    if dim < 1:
+        raise ValueError("mean must have one latent dimension or more")
+    if not bool(torch.isfinite(logvar).all()):
+        raise ValueError("the table of log-variances holds a NaN or an infinity")
+    table, rows, S, dev = _select_rows(mean, rows, n_samples, seed, "interpretability_scores_from_table", "posterior-mass")
+    if logvar.device != dev:
+        raise _lib.DvaeHipError("interpretability_scores_from_table needs mean and logvar on the same GPU")
+    logvar = logvar.detach().to(torch.float32).contiguous()
+    M = _masslib.lib()
+    sum_sizes = sum(lat_sizes)
+    sizes_dev = torch.tensor(lat_sizes, dtype=torch.int32, device=dev)
+    edges_dev = torch.from_numpy(mass_edges(n_bins, z_range)).to(dev) if n_bins > 1 else None
+    ws = torch.empty(M.dvae_mass_ws_doubles(n, dim, K, S, n_bins, sum_sizes), dtype=torch.float64, device=dev)
+    mass = torch.empty(dim, n_bins * sum_sizes, dtype=torch.float64, device=dev)
+    _masslib.call("dvae_mass_joint", ptr(table), ptr(logvar), ptr(rows), ptr(sizes_dev), ptr(edges_dev), n, dim, K, S, n_bins,
+                  sum_sizes, ptr(ws), ptr(mass), _stream())
+    scores = interpretability_scores_from_mass(mass.cpu().numpy(), lat_sizes, n_bins)     # ONE device->host copy
     scores.update(n_samples=S, n_bins=n_bins)
     return scores
 
