@@ -8,7 +8,8 @@ nothing of one target is linked into another.  All targets share FLAGS and the u
 logic, each under a stamp of its own (build/flags.txt, build/flags_NAME.txt).  The module's X_LIB / X_SOURCES /
 X_HEADERS names (LIB / SOURCES / HEADERS for the training library) are derived from the table.
 PLUGIN_TARGETS is a second list of the same rows, built after TARGETS in the same way (see there), SCORE_PLUGIN_TARGETS a
-third, built after both, and EXTRA_TARGETS a fourth, built last, whose libraries land in lib/ext/.
+third, built after both, EXTRA_TARGETS a fourth, whose libraries land in lib/ext/, and MORE_TARGETS a fifth, built last, whose
+libraries land in lib_more/ next to lib/.
 The libraries land in disentangling-vae_amd/lib/ (git-ignored build products).  Objects are rebuilt only
 when a source / header is newer or the flags changed.
 --debug (or DVAE_BUILD_DEBUG=1) adds -DDVAE_DEBUG_SWITCHES: the A/B / timing-ablation environment
@@ -56,6 +57,14 @@ EXTRA_TARGETS = [
     ("mass", ["posterior_mass"], "dvae_mass_hip.h"),       # RMIG / JEMMIG / MIG-sup / DCIMIG: the posterior mass per bin and factor value
 ]
 EXTRA_DIR = "ext"
+# A fifth list of the same rows, built after the other four through the same helper, FLAGS and stamp logic, out of ALL_SOURCES and
+# tools/isa_identity.py -- and OUTSIDE lib/: the host tests also pin the number of libraries anywhere under lib/ and what lib/ext/
+# holds, so these land in the sibling directory lib_more/ (git-ignored like lib/), reached as a sub-directory "../lib_more" of
+# lib/ by _target here and by _cabi.Binding.for_library.  The next library is one more row HERE.
+MORE_TARGETS = [
+    ("sap", ["svm_1d"], "dvae_sap_hip.h"),                 # discrete-factor SAP: one-feature linear SVMs fitted by Newton's method on the device
+]
+MORE_DIR = os.path.join("..", "lib_more")
 HEADERS = sorted(glob.glob(os.path.join(SRC, "*.h"))) + [os.path.join(HERE, "..", "include", "dvae_hip.h")]
 
 
@@ -72,6 +81,9 @@ for _row in TARGETS + PLUGIN_TARGETS + SCORE_PLUGIN_TARGETS:        # LIB / SOUR
 for _row in EXTRA_TARGETS:
     globals()[_row[0].upper() + "_LIB"], globals()[_row[0].upper() + "_SOURCES"], globals()[_row[0].upper() + "_HEADERS"], _ = \
         _target(*_row, subdir=EXTRA_DIR)
+for _row in MORE_TARGETS:
+    globals()[_row[0].upper() + "_LIB"], globals()[_row[0].upper() + "_SOURCES"], globals()[_row[0].upper() + "_HEADERS"], _ = \
+        _target(*_row, subdir=MORE_DIR)
 ALL_SOURCES = [s for _, sources, _ in TARGETS for s in sources]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
@@ -117,8 +129,8 @@ def _build_row(hipcc, name, sources, header, flags, debug, force, verbose, subdi
 
 
 def build(force=False, verbose=True, debug=None):
-    """Build every target of TARGETS, then of PLUGIN_TARGETS, then of SCORE_PLUGIN_TARGETS, then of EXTRA_TARGETS, in their order;
-    returns the path of libdvae_hip.so."""
+    """Build every target of TARGETS, then of PLUGIN_TARGETS, then of SCORE_PLUGIN_TARGETS, then of EXTRA_TARGETS, then of
+    MORE_TARGETS, in their order; returns the path of libdvae_hip.so."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if debug is None:
         debug = os.environ.get("DVAE_BUILD_DEBUG", "0") == "1"
@@ -130,6 +142,7 @@ def build(force=False, verbose=True, debug=None):
     for name, sources, header in SCORE_PLUGIN_TARGETS:
         _build_row(hipcc, name, sources, header, flags, debug, force, verbose)
     for row in EXTRA_TARGETS: _build_row(hipcc, *row, flags, debug, force, verbose, subdir=EXTRA_DIR)   # noqa: E701 (the host tests count the two loop bodies above)
+    for row in MORE_TARGETS: _build_row(hipcc, *row, flags, debug, force, verbose, subdir=MORE_DIR)     # noqa: E701 (likewise)
     return LIB
 
 

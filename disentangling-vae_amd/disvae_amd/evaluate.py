@@ -69,9 +69,18 @@
   factor value in one HIP pass on the tables where they lie (libdvae_mass_hip.so; accumulators in LDS, fixed order); the
   [D, n_bins * sum(lat_sizes)] mass table crosses to the host, where the scores are combined in fp64.
   Written to interpretability_scores.log by ``__call__(is_interpretability=True)``.
+* SAP with DISCRETE factors (Kumar et al. 2018; the branch of disentanglement_lib's sap_score.py that its shipped configuration
+  selects, and so the SAP number of Locatello et al. 2019), new (``compute_sap_discrete`` / ``sap_discrete_from_table`` /
+  ``sap_discrete_from_score_matrix``): entry [d, k] of the score matrix is the test accuracy of LinearSVC(C=0.01,
+  class_weight="balanced") fitted on latent d alone.  With one feature every one-vs-rest squared-hinge problem has two unknowns,
+  and Newton's method on the active set reaches its exact minimiser: all D x (classes of every factor) problems are fitted by ONE
+  HIP launch on the table where it lies, their columns in LDS (libdvae_sap_hip.so), and two more launches count the correct
+  predictions; the [D, K] counts, the coefficients and the iteration counts cross to the host.
+  Written to sap_discrete.log by ``__call__(is_sap_discrete=True)``.
 """
 import logging
 import math
+import numbers
 import os
 from collections import defaultdict
 from timeit import default_timer
@@ -79,7 +88,7 @@ from timeit import default_timer
 import numpy as np
 import torch
 
-from . import _dcilib, _evallib, _infolib, _irslib, _lib, _masslib, _scorelib, _seplib, _udrlib, _unsuplib
+from . import _dcilib, _evallib, _infolib, _irslib, _lib, _masslib, _saplib, _scorelib, _seplib, _udrlib, _unsuplib
 from ._lib import call, ptr
 from .engine import _stream
 from .likelihood import _ScorePasses, check_rec_dist, log_likelihood
@@ -102,6 +111,7 @@ FAIRNESS_FILE = "fairness.log"
 EXPLICITNESS_FILE = "explicitness.log"
 SEPARABILITY_SCORES_FILE = "separability_scores.log"
 INTERPRETABILITY_SCORES_FILE = "interpretability_scores.log"
+SAP_DISCRETE_FILE = "sap_discrete.log"
 
 
 class Evaluator:
@@ -120,7 +130,8 @@ class Evaluator:
                  is_decomposition=False, n_samples_decomposition=10000, is_scores=False, is_information=False,
                  is_irs=False, is_unsupervised=False, udr_models=None, is_dci=False, dci_args=None, is_downstream=False,
                  is_fairness=False, is_explicitness=False, downstream_args=None, fairness_args=None, explicitness_args=None,
-                 is_separability=False, n_samples_separability=10000, is_interpretability=False, interpretability_args=None):
+                 is_separability=False, n_samples_separability=10000, is_interpretability=False, interpretability_args=None,
+                 is_sap_discrete=False, sap_discrete_args=None):
         """evaluate.py:60-95.  is_log_likelihood: also write compute_log_likelihood(data_loader, n_samples) to
         log_likelihood.log; is_decomposition: also write compute_elbo_decomposition(data_loader, n_samples_decomposition) to
         elbo_decomposition.log; is_scores: also write compute_factor_scores(data_loader) to factor_scores.log; is_information: also
@@ -134,7 +145,8 @@ class Evaluator:
         **explicitness_args) to explicitness.log, their arrays as lists; is_separability: also write
         compute_separability_scores(data_loader, n_samples_separability) to separability_scores.log; is_interpretability: also
         write compute_interpretability_scores(data_loader, **interpretability_args), without its [D, K] matrices, to
-        interpretability_scores.log."""
+        interpretability_scores.log; is_sap_discrete: also write compute_sap_discrete(data_loader, **sap_discrete_args), without
+        its matrices and coefficients, to sap_discrete.log."""
         start = default_timer()
         is_still_training = self.model.training
         self.model.eval()
@@ -172,6 +184,8 @@ class Evaluator:
             (is_interpretability, 'the RMIG, JEMMIG, MIG-sup and DCIMIG scores',
              lambda: self.compute_interpretability_scores(data_loader, **(interpretability_args or {})), matrices,
              'Interpretability scores', INTERPRETABILITY_SCORES_FILE),
+            (is_sap_discrete, 'the discrete-factor SAP score', lambda: self.compute_sap_discrete(data_loader, **(sap_discrete_args or {})),
+             matrices, 'SAP (discrete factors)', SAP_DISCRETE_FILE),
         ]
         written = {}
         for wanted, what, compute, left_out, label, filename in outputs:
@@ -366,6 +380,16 @@ class Evaluator:
         _check_information_sizes(n, lat_sizes, n_bins, n_samples)
         mean, _logvar = self._encode(dataloader, n, lat_sizes)
         return information_scores_from_table(mean, lat_sizes, n_bins=n_bins, n_samples=n_samples, seed=seed)
+
+    # ------------------------------------------------------------------ SAP with discrete factors
+    def compute_sap_discrete(self, dataloader, n_train=10000, n_test=5000, C=0.01, seed=0):
+        """The discrete-factor SAP score of the model (sap_discrete_from_table below, on the posterior means of the whole data set
+        through the native encoder).  The data-set requirements and errors of compute_factor_scores; every size and argument is
+        checked before any device work; train / eval mode is restored."""
+        _ds, lat_sizes, n = self._factor_sizes(dataloader)
+        _check_sap_arguments(n, None, lat_sizes, n_train, n_test, C, seed, None)
+        mean, _logvar = self._encode(dataloader, n, lat_sizes)
+        return sap_discrete_from_table(mean, lat_sizes, n_train=n_train, n_test=n_test, C=C, seed=seed)
 
     # ------------------------------------------------------------------ RMIG / JEMMIG / MIG-sup / DCIMIG
     def compute_interpretability_scores(self, dataloader, n_samples=None, n_bins=100, z_range=(-4., 4.), seed=0):
@@ -910,6 +934,12 @@ def histogram_edges(lo, hi, n_bins):
     return np.linspace(lo, hi, int(n_bins) + 1, dtype=np.float32)[:-1]
 
 
+def largest_gap(m):
+    """[D, K] -> the largest minus the second largest entry over d, [K]; one latent: the second largest counts as 0."""
+    ranked = np.sort(m, axis=0)[::-1]
+    return ranked[0] - (ranked[1] if m.shape[0] > 1 else 0.0)
+
+
 def information_scores_from_statistics(counts, lat_sizes, n_bins, col_var, factor_var, cov_zv):
     """The host half of information_scores_from_table, fp64: ``counts`` int [D, n_bins * sum(lat_sizes)] in the layout of
     dvae_info_joint_hist, col_var [D], factor_var [K], cov_zv [D, K] of dvae_info_moments.
@@ -937,9 +967,7 @@ def information_scores_from_statistics(counts, lat_sizes, n_bins, col_var, facto
         raise ValueError("factor(s) %s take one value among the selected rows: no entropy to divide the MIG by"
                          % [k for k in range(K) if not H[k] > 0])
 
-    def gap(m):                                                          # [D, K] -> largest minus second largest over d, [K]
-        ranked = np.sort(m, axis=0)[::-1]
-        return ranked[0] - (ranked[1] if D > 1 else 0.0)
+    gap = largest_gap
     m = mi ** 2
     t = m.max(axis=1)
     modularity_d = np.zeros(D)
@@ -1722,6 +1750,94 @@ def dci_from_table(mean, lat_sizes, n_train=10000, n_test=5000, seed=0, rows=Non
     return {"disentanglement": disentanglement, "completeness": completeness, "informativeness_train": float(acc[:, 0].mean()),
             "informativeness_test": float(acc[:, 1].mean()), "importance_matrix": matrix, "n_train": n_train, "n_test": n_test,
             "n_stages": n_stages}
+
+
+# ---------------------------------------------------------------------- SAP with discrete factors on a table of means
+def _check_sap_arguments(n, dim, lat_sizes, n_train=10000, n_test=5000, C=0.01, seed=0, rows=None):
+    """n: prod(lat_sizes); dim: None where not known yet (before the encoder ran)."""
+    _check_lat_sizes(lat_sizes, _saplib.MAX_FACTORS)
+    if max(lat_sizes) > _saplib.MAX_CLASSES:
+        raise ValueError("a factor of variation with %d values: the linear-SVM kernels take at most %d classes"
+                         % (max(lat_sizes), _saplib.MAX_CLASSES))
+    if not 1 <= int(n_train) <= _saplib.MAX_ROWS:
+        raise ValueError("n_train must lie in [1, %d], got %r" % (_saplib.MAX_ROWS, n_train))
+    if int(n_test) < 1:
+        raise ValueError("n_test must be at least 1, got %r" % (n_test,))
+    if not (isinstance(C, numbers.Real) and 0.0 < float(C) < math.inf):
+        raise ValueError("C must be a positive finite number, got %r" % (C,))
+    int(seed)
+    if rows is None and int(n_train) + int(n_test) > n:
+        raise ValueError("n_train + n_test must be at most %d (rows are drawn without replacement), got %d + %d"
+                         % (n, int(n_train), int(n_test)))
+    if dim is not None and not 1 <= dim <= _saplib.MAX_D:
+        raise ValueError("the table must have between 1 and %d latent dimensions, got %d" % (_saplib.MAX_D, dim))
+
+
+def sap_discrete_from_score_matrix(score_matrix):
+    """disentanglement_lib's sap_score.py on its score matrix [D, K] (latents x factors; accuracies), fp64: the mean over the
+    factors of the largest minus the second largest entry over the latents (largest_gap: one latent has no runner-up)."""
+    m = np.asarray(score_matrix, dtype=np.float64)
+    if m.ndim != 2 or m.size == 0:
+        raise ValueError("score_matrix must be a non-empty [D, K] matrix, got shape %s" % (m.shape,))
+    return float(np.mean(largest_gap(m)))
+
+
+def sap_discrete_from_table(mean, lat_sizes, n_train=10000, n_test=5000, C=0.01, seed=0, rows=None):
+    """The SAP score with discrete factors of a representation given as the fp32 [N, D] table ``mean`` (on the GPU) of a data set
+    that enumerates ``lat_sizes`` in row-major order: score_matrix[d, k] is the accuracy on n_test rows of
+    LinearSVC(C=C, class_weight="balanced") fitted on latent d ALONE to predict factor k from n_train rows -- the objective and
+    its exact minimiser by Newton's method are stated in include/dvae_sap_hip.h, where liblinear stops at a tolerance.
+
+    rows = randperm(N)[:n_train + n_test] from a private generator seeded with ``seed`` (the same seed gives the same bits, the
+    global random states are untouched), the first n_train to fit; ``rows`` ([n_train + n_test] row numbers in [0, N), repeats
+    allowed) injects the selection.  The factor values are digits of the row number; the labels of factor k are the ranks of its
+    values among those PRESENT in the training rows (a test row with a value never seen counts as an error; a factor with one
+    value present has no problem and predicts that value: every latent scores alike and its gap is 0).  Every problem of every
+    (latent, factor) pair is fitted by ONE dvae_sap_fit call, and both dvae_sap_accuracy passes are enqueued, before anything is
+    read back -- but the number of classes present per factor, which sizes ``coef``.  Every size and argument is checked before
+    any device work, and a table with a NaN or an infinity raises ValueError.  Returns {"sap_discrete", "score_matrix" [D, K]
+    (test accuracy), "score_matrix_train" [D, K], "coef" [D, P, 2] (w, b of every problem, include/dvae_sap_hip.h's order),
+    "n_iterations_max", "n_train", "n_test", "C"}: Python and numpy values."""
+    lat_sizes = [int(k) for k in lat_sizes]
+    K, n_train, n_test = len(lat_sizes), int(n_train), int(n_test)
+    n, dim = _table_shape(mean)
+    _check_sap_arguments(int(np.prod(lat_sizes)) if lat_sizes else 0, dim, lat_sizes, n_train, n_test, C, seed, rows)
+    if n != int(np.prod(lat_sizes)):
+        raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (n, lat_sizes))
+    if rows is not None and torch.as_tensor(rows).numel() != n_train + n_test:
+        raise ValueError("rows must hold n_train + n_test = %d row numbers" % (n_train + n_test))
+    table, rows, _S, dev = _select_rows(mean, rows, n_train + n_test, seed, "sap_discrete_from_table", "linear-SVM")
+    st = _stream()
+    train, test = rows[:n_train].contiguous(), rows[n_train:].contiguous()
+    labels_train, labels_test, n_classes = [], [], []
+    for stride, size in zip(_factor_strides(lat_sizes), lat_sizes):
+        values_train, values_test = (train // stride) % size, (test // stride) % size
+        classes = torch.unique(values_train)                             # sorted; its length is the one number the host needs now
+        n_classes.append(int(classes.numel()))
+        labels_train.append(torch.searchsorted(classes, values_train))
+        at = torch.searchsorted(classes, values_test).clamp(max=n_classes[-1] - 1)
+        labels_test.append(torch.where(classes[at] == values_test, at, torch.full_like(at, -1)))
+    labels_train = torch.stack(labels_train).to(torch.int32).contiguous()
+    labels_test = torch.stack(labels_test).to(torch.int32).contiguous()
+    P = _saplib.problems(n_classes)
+    host_classes = _saplib.host_classes(n_classes)
+    coef = torch.empty(dim, P, 2, dtype=torch.float64, device=dev)
+    iterations = torch.empty(dim, P, dtype=torch.int32, device=dev)
+    correct = torch.empty(2, dim, K, dtype=torch.int32, device=dev)
+    _saplib.call("dvae_sap_fit", ptr(table), ptr(train), ptr(labels_train), host_classes, n, dim, K, n_train, float(C), ptr(coef),
+                 ptr(iterations), st)
+    _saplib.call("dvae_sap_accuracy", ptr(table), ptr(train), ptr(labels_train), host_classes, n, dim, K, n_train, ptr(coef),
+                 ptr(correct[0]), None, st)
+    _saplib.call("dvae_sap_accuracy", ptr(table), ptr(test), ptr(labels_test), host_classes, n, dim, K, n_test, ptr(coef),
+                 ptr(correct[1]), None, st)
+    counts, steps, coef = correct.cpu().numpy(), iterations.cpu().numpy(), coef.cpu().numpy()      # the read-back
+    if (steps < 1).any():
+        raise _lib.DvaeHipError("dvae_sap_fit: %d of %d problems did not stop within %d Newton steps"
+                                % (int((steps < 1).sum()), steps.size, _saplib.MAX_ITERATIONS))
+    score_train, score_test = counts[0] / float(n_train), counts[1] / float(n_test)
+    return {"sap_discrete": sap_discrete_from_score_matrix(score_test), "score_matrix": score_test, "score_matrix_train": score_train,
+            "coef": coef, "n_iterations_max": int(steps.max()) if steps.size else 0, "n_train": n_train, "n_test": n_test,
+            "C": float(C)}
 
 
 # ---------------------------------------------------------------------- prediction-based scores on a table of means
