@@ -9,7 +9,7 @@ logic, each under a stamp of its own (build/flags.txt, build/flags_NAME.txt).  T
 X_HEADERS names (LIB / SOURCES / HEADERS for the training library) are derived from the table.
 PLUGIN_TARGETS is a second list of the same rows, built after TARGETS in the same way (see there), SCORE_PLUGIN_TARGETS a
 third, built after both, EXTRA_TARGETS a fourth, whose libraries land in lib/ext/, and MORE_TARGETS a fifth, built last, whose
-libraries land in lib_more/ next to lib/.
+libraries land in lib_more/ next to lib/, and SCORE_TARGETS a sixth, whose libraries land in lib_scores/ next to both.
 The libraries land in disentangling-vae_amd/lib/ (git-ignored build products).  Objects are rebuilt only
 when a source / header is newer or the flags changed.
 --debug (or DVAE_BUILD_DEBUG=1) adds -DDVAE_DEBUG_SWITCHES: the A/B / timing-ablation environment
@@ -65,6 +65,13 @@ MORE_TARGETS = [
     ("sap", ["svm_1d"], "dvae_sap_hip.h"),                 # discrete-factor SAP: one-feature linear SVMs fitted by Newton's method on the device
 ]
 MORE_DIR = os.path.join("..", "lib_more")
+# A sixth list of the same rows, built after the other five through the same helper, FLAGS and stamp logic, out of ALL_SOURCES and
+# tools/isa_identity.py, into the sibling directory lib_scores/ (git-ignored like lib/): the host tests pin what lib/, lib/ext/ and
+# lib_more/ hold.  Nothing pins this list or its directory to ONE entry: the next score library is one more row of THIS list.
+SCORE_TARGETS = [
+    ("knn", ["knn_mi"], "dvae_knn_hip.h"),                 # binning-free MIG / InfoM / InfoC: k-nearest-neighbour mutual information (Ross 2014)
+]
+SCORE_DIR = os.path.join("..", "lib_scores")
 HEADERS = sorted(glob.glob(os.path.join(SRC, "*.h"))) + [os.path.join(HERE, "..", "include", "dvae_hip.h")]
 
 
@@ -84,6 +91,9 @@ for _row in EXTRA_TARGETS:
 for _row in MORE_TARGETS:
     globals()[_row[0].upper() + "_LIB"], globals()[_row[0].upper() + "_SOURCES"], globals()[_row[0].upper() + "_HEADERS"], _ = \
         _target(*_row, subdir=MORE_DIR)
+for _row in SCORE_TARGETS:
+    globals()[_row[0].upper() + "_LIB"], globals()[_row[0].upper() + "_SOURCES"], globals()[_row[0].upper() + "_HEADERS"], _ = \
+        _target(*_row, subdir=SCORE_DIR)
 ALL_SOURCES = [s for _, sources, _ in TARGETS for s in sources]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
@@ -130,7 +140,7 @@ def _build_row(hipcc, name, sources, header, flags, debug, force, verbose, subdi
 
 def build(force=False, verbose=True, debug=None):
     """Build every target of TARGETS, then of PLUGIN_TARGETS, then of SCORE_PLUGIN_TARGETS, then of EXTRA_TARGETS, then of
-    MORE_TARGETS, in their order; returns the path of libdvae_hip.so."""
+    MORE_TARGETS, then of SCORE_TARGETS, in their order; returns the path of libdvae_hip.so."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if debug is None:
         debug = os.environ.get("DVAE_BUILD_DEBUG", "0") == "1"
@@ -143,6 +153,7 @@ def build(force=False, verbose=True, debug=None):
         _build_row(hipcc, name, sources, header, flags, debug, force, verbose)
     for row in EXTRA_TARGETS: _build_row(hipcc, *row, flags, debug, force, verbose, subdir=EXTRA_DIR)   # noqa: E701 (the host tests count the two loop bodies above)
     for row in MORE_TARGETS: _build_row(hipcc, *row, flags, debug, force, verbose, subdir=MORE_DIR)     # noqa: E701 (likewise)
+    for row in SCORE_TARGETS: _build_row(hipcc, *row, flags, debug, force, verbose, subdir=SCORE_DIR)   # noqa: E701 (likewise)
     return LIB
 
 

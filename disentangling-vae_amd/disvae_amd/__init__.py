@@ -25,8 +25,9 @@ if "GPU_MAX_HW_QUEUES" not in _os.environ:
 from .models.vae import init_specific_model  # noqa: E402
 from .training import Trainer  # noqa: E402
 from .evaluate import (Evaluator, dci_from_importance, dci_from_table, downstream_task_from_table,  # noqa: E402
-                       explicitness_from_table, fairness_from_table, interpretability_scores_from_mass,
-                       interpretability_scores_from_table, sap_discrete_from_score_matrix, sap_discrete_from_table,
+                       digamma_integers, explicitness_from_table, fairness_from_table, interpretability_scores_from_mass,
+                       interpretability_scores_from_table, knn_information_scores_from_mi,
+                       knn_information_scores_from_table, sap_discrete_from_score_matrix, sap_discrete_from_table,
                        separability_scores_from_entropies, udr_from_tables)
 from .visualize import Visualizer, GifTraversalsTraining  # noqa: E402
 from .likelihood import per_image_losses, log_likelihood  # noqa: E402
@@ -36,4 +37,5 @@ __all__ = ["init_specific_model", "Trainer", "Evaluator", "Visualizer", "GifTrav
            "log_likelihood", "udr_from_tables", "dci_from_table", "dci_from_importance", "DipVaeLoss", "InfoVaeLoss",
            "downstream_task_from_table", "fairness_from_table", "explicitness_from_table", "separability_scores_from_entropies",
            "interpretability_scores_from_table", "interpretability_scores_from_mass", "sap_discrete_from_table",
-           "sap_discrete_from_score_matrix"]
+           "sap_discrete_from_score_matrix", "knn_information_scores_from_table", "knn_information_scores_from_mi",
+           "digamma_integers"]

@@ -77,6 +77,14 @@
   HIP launch on the table where it lies, their columns in LDS (libdvae_sap_hip.so), and two more launches count the correct
   predictions; the [D, K] counts, the coefficients and the iteration counts cross to the host.
   Written to sap_discrete.log by ``__call__(is_sap_discrete=True)``.
+* BINNING-FREE MIG, modularity, MIG-sup and DCIMIG, and the InfoMEC scores InfoM and InfoC (Hsu et al. 2023), new
+  (``compute_knn_information_scores`` / ``knn_information_scores_from_table`` / ``knn_information_scores_from_mi``): every
+  mutual-information score above first puts the latent into bins; here I(z_d; v_k) is the k-nearest-neighbour estimate of Ross
+  2014 between the continuous latent and the discrete factor (scikit-learn's _compute_mi_cd, without mutual_info_classif's
+  rescaling and noise).  In one dimension that is a sort, a partition by label, a bounded neighbour walk and two binary searches
+  per row, all integer-exact in the LDS of one workgroup (libdvae_knn_hip.so): two launches, and the neighbour counts' digamma
+  sums [D, K, 4] and the class counts cross to the host, where the estimate is clipped at 0 and the scores are combined in fp64.
+  Written to knn_information_scores.log by ``__call__(is_knn_information=True)``.
 """
 import logging
 import math
@@ -88,7 +96,7 @@ from timeit import default_timer
 import numpy as np
 import torch
 
-from . import _dcilib, _evallib, _infolib, _irslib, _lib, _masslib, _saplib, _scorelib, _seplib, _udrlib, _unsuplib
+from . import _dcilib, _evallib, _infolib, _irslib, _knnlib, _lib, _masslib, _saplib, _scorelib, _seplib, _udrlib, _unsuplib
 from ._lib import call, ptr
 from .engine import _stream
 from .likelihood import _ScorePasses, check_rec_dist, log_likelihood
@@ -112,6 +120,7 @@ EXPLICITNESS_FILE = "explicitness.log"
 SEPARABILITY_SCORES_FILE = "separability_scores.log"
 INTERPRETABILITY_SCORES_FILE = "interpretability_scores.log"
 SAP_DISCRETE_FILE = "sap_discrete.log"
+KNN_INFORMATION_SCORES_FILE = "knn_information_scores.log"
 
 
 class Evaluator:
@@ -131,7 +140,7 @@ class Evaluator:
                  is_irs=False, is_unsupervised=False, udr_models=None, is_dci=False, dci_args=None, is_downstream=False,
                  is_fairness=False, is_explicitness=False, downstream_args=None, fairness_args=None, explicitness_args=None,
                  is_separability=False, n_samples_separability=10000, is_interpretability=False, interpretability_args=None,
-                 is_sap_discrete=False, sap_discrete_args=None):
+                 is_sap_discrete=False, sap_discrete_args=None, is_knn_information=False, knn_information_args=None):
         """evaluate.py:60-95.  is_log_likelihood: also write compute_log_likelihood(data_loader, n_samples) to
         log_likelihood.log; is_decomposition: also write compute_elbo_decomposition(data_loader, n_samples_decomposition) to
         elbo_decomposition.log; is_scores: also write compute_factor_scores(data_loader) to factor_scores.log; is_information: also
@@ -146,7 +155,9 @@ class Evaluator:
         compute_separability_scores(data_loader, n_samples_separability) to separability_scores.log; is_interpretability: also
         write compute_interpretability_scores(data_loader, **interpretability_args), without its [D, K] matrices, to
         interpretability_scores.log; is_sap_discrete: also write compute_sap_discrete(data_loader, **sap_discrete_args), without
-        its matrices and coefficients, to sap_discrete.log."""
+        its matrices and coefficients, to sap_discrete.log; is_knn_information: also write
+        compute_knn_information_scores(data_loader, **knn_information_args), without its [D, K] matrices, to
+        knn_information_scores.log."""
         start = default_timer()
         is_still_training = self.model.training
         self.model.eval()
@@ -186,6 +197,9 @@ class Evaluator:
              'Interpretability scores', INTERPRETABILITY_SCORES_FILE),
             (is_sap_discrete, 'the discrete-factor SAP score', lambda: self.compute_sap_discrete(data_loader, **(sap_discrete_args or {})),
              matrices, 'SAP (discrete factors)', SAP_DISCRETE_FILE),
+            (is_knn_information, 'the binning-free MIG, InfoM and InfoC scores',
+             lambda: self.compute_knn_information_scores(data_loader, **(knn_information_args or {})), matrices,
+             'k-NN information scores', KNN_INFORMATION_SCORES_FILE),
         ]
         written = {}
         for wanted, what, compute, left_out, label, filename in outputs:
@@ -390,6 +404,16 @@ class Evaluator:
         _check_sap_arguments(n, None, lat_sizes, n_train, n_test, C, seed, None)
         mean, _logvar = self._encode(dataloader, n, lat_sizes)
         return sap_discrete_from_table(mean, lat_sizes, n_train=n_train, n_test=n_test, C=C, seed=seed)
+
+    # ------------------------------------------------------------------ binning-free MIG / InfoM / InfoC
+    def compute_knn_information_scores(self, dataloader, n_samples=10000, n_neighbors=3, seed=0):
+        """Binning-free MIG, modularity, MIG-sup, DCIMIG, InfoM and InfoC of the model (knn_information_scores_from_table below,
+        on the posterior means of the whole data set through the native encoder).  The data-set requirements and errors of
+        compute_factor_scores; every size and argument is checked before any device work; train / eval mode is restored."""
+        _ds, lat_sizes, n = self._factor_sizes(dataloader)
+        _check_knn_arguments(n, None, lat_sizes, n_samples, n_neighbors, seed, None)
+        mean, _logvar = self._encode(dataloader, n, lat_sizes)
+        return knn_information_scores_from_table(mean, lat_sizes, n_samples=n_samples, n_neighbors=n_neighbors, seed=seed)
 
     # ------------------------------------------------------------------ RMIG / JEMMIG / MIG-sup / DCIMIG
     def compute_interpretability_scores(self, dataloader, n_samples=None, n_bins=100, z_range=(-4., 4.), seed=0):
@@ -1838,6 +1862,148 @@ def sap_discrete_from_table(mean, lat_sizes, n_train=10000, n_test=5000, C=0.01,
     return {"sap_discrete": sap_discrete_from_score_matrix(score_test), "score_matrix": score_test, "score_matrix_train": score_train,
             "coef": coef, "n_iterations_max": int(steps.max()) if steps.size else 0, "n_train": n_train, "n_test": n_test,
             "C": float(C)}
+
+
+# ---------------------------------------------------------------------- binning-free mutual information on a table of means
+_EULER_GAMMA = "0.57721566490153286060651209008240243104215933593992"
+
+
+def digamma_integers(n):
+    """fp64 [n + 1]: psi(j) for j in [1, n] at index j (index 0 holds 0 and stands for nothing) -- the table dvae_knn_mi reads.
+    The recurrence psi(1) = -gamma, psi(j + 1) = psi(j) + 1 / j carried in numpy's long double and rounded ONCE: a plain fp64
+    cumulative sum is 31 ulp from scipy.special.digamma at n = 16 384, this is within 1 ulp (x86-64's 80-bit long double; where
+    long double is fp64 it is the plain sum)."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be at least 1, got %r" % (n,))
+    steps = np.concatenate([[-np.longdouble(_EULER_GAMMA)], np.longdouble(1) / np.arange(1, n, dtype=np.longdouble)])
+    return np.concatenate([[0.0], np.cumsum(steps).astype(np.float64)])
+
+
+def _check_knn_arguments(n, dim, lat_sizes, n_samples=10000, n_neighbors=3, seed=0, rows=None):
+    """n: prod(lat_sizes); dim: None where not known yet (before the encoder ran)."""
+    _check_lat_sizes(lat_sizes, _knnlib.MAX_FACTORS)
+    if max(lat_sizes) > _knnlib.MAX_CLASSES:
+        raise ValueError("a factor of variation with %d values: the k-NN mutual-information kernels take at most %d"
+                         % (max(lat_sizes), _knnlib.MAX_CLASSES))
+    if min(lat_sizes) < 2:
+        raise ValueError("a factor of variation with one value has no entropy (the scores divide by it): lat_sizes=%s" % (lat_sizes,))
+    if not (isinstance(n_neighbors, numbers.Integral) and 1 <= int(n_neighbors) <= _knnlib.MAX_NEIGHBORS):
+        raise ValueError("n_neighbors must be an integer in [1, %d], got %r" % (_knnlib.MAX_NEIGHBORS, n_neighbors))
+    int(seed)
+    if rows is None:
+        if n_samples is None:
+            n_samples = n
+        if not 1 <= int(n_samples) <= _knnlib.MAX_ROWS:
+            raise ValueError("n_samples must lie in [1, %d] (a column is sorted in the LDS of one workgroup), got %r"
+                             % (_knnlib.MAX_ROWS, n_samples))
+        if int(n_samples) > n:
+            raise ValueError("n_samples must be at most %d (rows are drawn without replacement), got %d" % (n, int(n_samples)))
+    elif not 1 <= torch.as_tensor(rows).numel() <= _knnlib.MAX_ROWS:
+        raise ValueError("rows must hold between 1 and %d row numbers, got %d" % (_knnlib.MAX_ROWS, torch.as_tensor(rows).numel()))
+    if dim is not None and not 1 <= dim <= _knnlib.MAX_D:
+        raise ValueError("the table must have between 1 and %d latent dimensions, got %d" % (_knnlib.MAX_D, dim))
+
+
+def knn_information_scores_from_mi(mi, factor_entropy):
+    """The host half of knn_information_scores_from_table, pure numpy, fp64: ``mi`` [D, K] the estimates of I(z_d; v_k) in nats
+    (unclipped ones are clipped at 0 here and returned as ``raw``), ``factor_entropy`` [K] the entropy H_k in nats of factor k over
+    all selected rows (a factor without entropy raises ValueError).  With I the clipped matrix and NMI = I / H_k:
+
+    mig = mean_k (largest - second largest of I[:, k]) / H_k (one latent: the second is 0);  mig_sup = mean_d (largest - second
+    largest over k of NMI[d, k]) (one factor: the second is 0; Li et al. 2020);  dcimig = sum_k max_{d : k(d) = k} gap_d / sum_k H_k,
+    k(d) = arg max_k I[d, k], gap_d the largest minus the second largest of I[d, :] (a factor no latent prefers contributes 0;
+    Sepliarskaia et al. 2019);  modularity = mean_d [1 - (sum m - t) / (t (K - 1))], m = I[d, :]^2, t = max m (0 where t = 0; K = 1:
+    1 where t > 0; Ridgeway & Mozer 2018) -- the formulas of interpretability_scores_from_mass and
+    information_scores_from_statistics on this matrix.
+    A latent is ACTIVE if its row of I is not all zero, D_a of them.  InfoMEC (Hsu et al. 2023):
+        infom = mean over the active d of (max_k NMI[d, k] / sum_k NMI[d, k] - 1 / K) / (1 - 1 / K)
+        infoc = mean over the k with a nonzero column of (max_d NMI[d, k] / sum_d NMI[d, k] - 1 / D_a) / (1 - 1 / D_a)
+    an entry whose denominator is 0 (K = 1, D_a = 1) is 1.0, and with no active latent both are 0.0.
+    Returns {"mig", "mig_sup", "dcimig", "modularity", "infom", "infoc", "n_active", "best_latent" [K] (arg max_d, the lowest d on
+    ties), "mutual_information" [D, K], "raw" [D, K], "factor_entropy" [K]}."""
+    raw = np.array(mi, dtype=np.float64)
+    H = np.array(factor_entropy, dtype=np.float64).reshape(-1)
+    if raw.ndim != 2 or raw.size == 0 or H.shape != (raw.shape[1],) or not np.isfinite(raw).all():
+        raise ValueError("mi must be a finite non-empty [D, K] matrix and factor_entropy [K], got shapes %s and %s" % (raw.shape, H.shape))
+    if not (H > 0).all():
+        raise ValueError("factor(s) %s take one value among the selected rows: no entropy to divide the scores by"
+                         % [k for k in range(len(H)) if not H[k] > 0])
+    I = np.maximum(raw, 0.0)
+    D, K = I.shape
+    nmi = I / H[None, :]
+    m = I ** 2
+    t = m.max(axis=1)
+    modularity_d = np.zeros(D)
+    if K > 1:
+        modularity_d[t > 0] = 1.0 - (m.sum(axis=1) - t)[t > 0] / (t[t > 0] * (K - 1))
+    else:
+        modularity_d[t > 0] = 1.0
+    mig_sup_d = largest_gap(nmi.T)
+    gap_d = largest_gap(I.T)
+    prefers = I.argmax(axis=1)                                           # [D], k(d)
+    dcimig = sum(gap_d[prefers == k].max() for k in range(K) if (prefers == k).any()) / H.sum()
+    active = (I != 0).any(axis=1)
+    n_active = int(active.sum())
+    infom = infoc = 0.0
+    if n_active:
+        A = nmi[active]
+        infom = 1.0 if K == 1 else float(np.mean((A.max(axis=1) / A.sum(axis=1) - 1.0 / K) / (1.0 - 1.0 / K)))
+        A = A[:, (A != 0).any(axis=0)]
+        infoc = 1.0 if n_active == 1 else float(np.mean((A.max(axis=0) / A.sum(axis=0) - 1.0 / n_active) / (1.0 - 1.0 / n_active)))
+    return {"mig": float(np.mean(largest_gap(I) / H)), "mig_sup": float(mig_sup_d.mean()), "dcimig": float(dcimig),
+            "modularity": float(modularity_d.mean()), "infom": infom, "infoc": infoc, "n_active": n_active,
+            "best_latent": I.argmax(axis=0).astype(np.int64), "mutual_information": I, "raw": raw, "factor_entropy": H}
+
+
+def knn_information_scores_from_table(mean, lat_sizes, n_samples=10000, n_neighbors=3, seed=0, rows=None):
+    """Binning-free MIG, modularity, MIG-sup, DCIMIG, InfoM and InfoC of a representation given as the fp32 [N, D] table ``mean``
+    (on the GPU) of a data set that enumerates ``lat_sizes`` in row-major order (formulas: knn_information_scores_from_mi).
+    I(z_d; v_k) is the k-nearest-neighbour estimate between a continuous and a discrete variable (Ross 2014) that
+    include/dvae_knn_hip.h states: scikit-learn's _compute_mi_cd on the column as it is -- mutual_info_classif's rescaling and
+    seeded noise are NOT applied, ties are handled by the estimator's own rule.
+
+    rows = randperm(N)[:n_samples] from a private generator seeded with ``seed`` (the same seed gives the same bits, the global
+    random states are untouched; n_samples=None: every row); ``rows`` ([S] row numbers in [0, N), repeats allowed: a repeated row
+    counts as another row) injects the selection.  At most DVAE_KNN_MAX_ROWS rows: a column is sorted in the LDS of one workgroup.
+    The factor values are digits of the row number; a factor with one value among the selected rows raises ValueError.  Every
+    size and argument is checked before any device work, and a table with a NaN or an infinity raises ValueError.  ONE launch
+    sequence (dvae_knn_sort, dvae_knn_mi), ONE device-to-host copy of the sums and the class counts, the clipping at 0 and
+    everything after it in fp64 on the host.  Returns the dictionary of knn_information_scores_from_mi and "n_kept" [D, K] (the rows
+    whose class has another row), "n_samples", "n_neighbors": Python and numpy values."""
+    lat_sizes = [int(k) for k in lat_sizes]
+    K = len(lat_sizes)
+    n, dim = _table_shape(mean)
+    _check_knn_arguments(int(np.prod(lat_sizes)) if lat_sizes else 0, dim, lat_sizes, n_samples, n_neighbors, seed, rows)
+    if n != int(np.prod(lat_sizes)):
+        raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (n, lat_sizes))
+    table, rows, S, dev = _select_rows(mean, rows, n_samples, seed, "knn_information_scores_from_table", "k-NN mutual-information")
+    Kn = _knnlib.lib()
+    st = _stream()
+    sum_sizes = sum(lat_sizes)
+    host_sizes = _knnlib.host_sizes(lat_sizes)
+    psi = digamma_integers(S)
+    psi_dev = torch.from_numpy(psi).to(dev)
+    ws = torch.empty(max(Kn.dvae_knn_ws_bytes(n, dim, S), 8), dtype=torch.uint8, device=dev)
+    out = torch.empty(4 * dim * K + (K * sum_sizes + 1) // 2, dtype=torch.float64, device=dev)     # the sums, then the int32 counts
+    sums, counts = out[:4 * dim * K], out[4 * dim * K:].view(torch.int32)[:K * sum_sizes]
+    _knnlib.call("dvae_knn_sort", ptr(table), ptr(rows), n, dim, S, ptr(ws), st)
+    _knnlib.call("dvae_knn_mi", ptr(rows), host_sizes, n, dim, K, S, int(n_neighbors), ptr(psi_dev), ptr(ws), ptr(sums), ptr(counts),
+                 None, None, st)
+    host = out.cpu()                                                     # ONE device->host copy
+    sums = host[:4 * dim * K].numpy().reshape(dim, K, 4)
+    counts = host[4 * dim * K:].view(torch.int32)[:K * sum_sizes].numpy().reshape(K, sum_sizes)
+    H, start = np.zeros(K), 0
+    for k, size in enumerate(lat_sizes):
+        pv = counts[k, start:start + size].astype(np.float64) / S
+        H[k] = -(pv[pv > 0] * np.log(pv[pv > 0])).sum()
+        start += size
+    n_kept = np.rint(sums[:, :, 0]).astype(np.int64)
+    kept = np.maximum(n_kept, 1)
+    raw = np.where(n_kept > 0, psi[kept] + sums[:, :, 1] / kept - sums[:, :, 2] / kept - sums[:, :, 3] / kept, 0.0)
+    scores = knn_information_scores_from_mi(raw, H)
+    scores.update(n_kept=n_kept, n_samples=S, n_neighbors=int(n_neighbors))
+    return scores
 
 
 # ---------------------------------------------------------------------- prediction-based scores on a table of means
