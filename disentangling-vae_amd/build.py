@@ -70,6 +70,7 @@ MORE_DIR = os.path.join("..", "lib_more")
 # lib_more/ hold.  Nothing pins this list or its directory to ONE entry: the next score library is one more row of THIS list.
 SCORE_TARGETS = [
     ("knn", ["knn_mi"], "dvae_knn_hip.h"),                 # binning-free MIG / InfoM / InfoC: k-nearest-neighbour mutual information (Ross 2014)
+    ("lr", ["softmax_fit"], "dvae_lr_hip.h"),              # linear-softmax probes (beta-VAE score, explicitness, InfoE): Newton-CG fits on the device
 ]
 SCORE_DIR = os.path.join("..", "lib_scores")
 HEADERS = sorted(glob.glob(os.path.join(SRC, "*.h"))) + [os.path.join(HERE, "..", "include", "dvae_hip.h")]

@@ -25,7 +25,8 @@ if "GPU_MAX_HW_QUEUES" not in _os.environ:
 from .models.vae import init_specific_model  # noqa: E402
 from .training import Trainer  # noqa: E402
 from .evaluate import (Evaluator, dci_from_importance, dci_from_table, downstream_task_from_table,  # noqa: E402
-                       digamma_integers, explicitness_from_table, fairness_from_table, interpretability_scores_from_mass,
+                       digamma_integers, explicitness_from_table, fairness_from_table, fit_logistic_regression_device,
+                       infoe_from_log_loss, infoe_from_table, interpretability_scores_from_mass,
                        interpretability_scores_from_table, knn_information_scores_from_mi,
                        knn_information_scores_from_table, sap_discrete_from_score_matrix, sap_discrete_from_table,
                        separability_scores_from_entropies, udr_from_tables)
@@ -38,4 +39,4 @@ __all__ = ["init_specific_model", "Trainer", "Evaluator", "Visualizer", "GifTrav
            "downstream_task_from_table", "fairness_from_table", "explicitness_from_table", "separability_scores_from_entropies",
            "interpretability_scores_from_table", "interpretability_scores_from_mass", "sap_discrete_from_table",
            "sap_discrete_from_score_matrix", "knn_information_scores_from_table", "knn_information_scores_from_mi",
-           "digamma_integers"]
+           "digamma_integers", "fit_logistic_regression_device", "infoe_from_table", "infoe_from_log_loss"]

@@ -85,6 +85,14 @@
   per row, all integer-exact in the LDS of one workgroup (libdvae_knn_hip.so): two launches, and the neighbour counts' digamma
   sums [D, K, 4] and the class counts cross to the host, where the estimate is clipped at 0 and the scores are combined in fp64.
   Written to knn_information_scores.log by ``__call__(is_knn_information=True)``.
+* LINEAR-SOFTMAX PROBES FITTED ON THE DEVICE and InfoE, the third score of the InfoMEC triple (Hsu et al. 2023), new
+  (``fit_logistic_regression_device``; ``fit="device"`` of ``explicitness_from_table`` / ``factor_scores_from_table`` and their
+  ``compute_*``; ``compute_infoe`` / ``infoe_from_table`` / ``infoe_from_log_loss``): the multinomial logistic regression of the
+  beta-VAE score and of explicitness -- fit_logistic_regression's objective -- solved by a truncated Newton-CG iteration in fp64
+  inside ONE HIP launch, a persistent workgroup per problem (libdvae_lr_hip.so), its probabilities, log-loss and counts of correct
+  rows by a second launch; the coefficients, the solver's report and [K] sums cross to the host.  InfoE per factor is 1 - the
+  probe's cross-entropy / that of the training rows' class frequencies.  The host fit stays the default of the two older scores.
+  Written to infoe.log by ``__call__(is_infoe=True)``.
 """
 import logging
 import math
@@ -96,7 +104,7 @@ from timeit import default_timer
 import numpy as np
 import torch
 
-from . import _dcilib, _evallib, _infolib, _irslib, _knnlib, _lib, _masslib, _saplib, _scorelib, _seplib, _udrlib, _unsuplib
+from . import _dcilib, _evallib, _infolib, _irslib, _knnlib, _lib, _lrlib, _masslib, _saplib, _scorelib, _seplib, _udrlib, _unsuplib
 from ._lib import call, ptr
 from .engine import _stream
 from .likelihood import _ScorePasses, check_rec_dist, log_likelihood
@@ -121,6 +129,7 @@ SEPARABILITY_SCORES_FILE = "separability_scores.log"
 INTERPRETABILITY_SCORES_FILE = "interpretability_scores.log"
 SAP_DISCRETE_FILE = "sap_discrete.log"
 KNN_INFORMATION_SCORES_FILE = "knn_information_scores.log"
+INFOE_FILE = "infoe.log"
 
 
 class Evaluator:
@@ -140,7 +149,8 @@ class Evaluator:
                  is_irs=False, is_unsupervised=False, udr_models=None, is_dci=False, dci_args=None, is_downstream=False,
                  is_fairness=False, is_explicitness=False, downstream_args=None, fairness_args=None, explicitness_args=None,
                  is_separability=False, n_samples_separability=10000, is_interpretability=False, interpretability_args=None,
-                 is_sap_discrete=False, sap_discrete_args=None, is_knn_information=False, knn_information_args=None):
+                 is_sap_discrete=False, sap_discrete_args=None, is_knn_information=False, knn_information_args=None,
+                 is_infoe=False, infoe_args=None):
         """evaluate.py:60-95.  is_log_likelihood: also write compute_log_likelihood(data_loader, n_samples) to
         log_likelihood.log; is_decomposition: also write compute_elbo_decomposition(data_loader, n_samples_decomposition) to
         elbo_decomposition.log; is_scores: also write compute_factor_scores(data_loader) to factor_scores.log; is_information: also
@@ -157,7 +167,8 @@ class Evaluator:
         interpretability_scores.log; is_sap_discrete: also write compute_sap_discrete(data_loader, **sap_discrete_args), without
         its matrices and coefficients, to sap_discrete.log; is_knn_information: also write
         compute_knn_information_scores(data_loader, **knn_information_args), without its [D, K] matrices, to
-        knn_information_scores.log."""
+        knn_information_scores.log; is_infoe: also write compute_infoe(data_loader, **infoe_args), its arrays as lists and without
+        the solver's [K, 4] report, to infoe.log."""
         start = default_timer()
         is_still_training = self.model.training
         self.model.eval()
@@ -200,6 +211,7 @@ class Evaluator:
             (is_knn_information, 'the binning-free MIG, InfoM and InfoC scores',
              lambda: self.compute_knn_information_scores(data_loader, **(knn_information_args or {})), matrices,
              'k-NN information scores', KNN_INFORMATION_SCORES_FILE),
+            (is_infoe, 'the InfoE score', lambda: self.compute_infoe(data_loader, **(infoe_args or {})), matrices, 'InfoE', INFOE_FILE),
         ]
         written = {}
         for wanted, what, compute, left_out, label, filename in outputs:
@@ -373,17 +385,20 @@ class Evaluator:
 
     # ------------------------------------------------------------------ FactorVAE / beta-VAE scores
     def compute_factor_scores(self, dataloader, n_train=10000, n_eval=5000, batch_size=64, n_variance=10000,
-                              active_threshold=0.05, seed=0, draws=None):
+                              active_threshold=0.05, seed=0, draws=None, fit="host"):
         """FactorVAE score and beta-VAE score of the model (factor_scores_from_table below, on the posterior means of the whole
         data set through the native encoder).  Requirements of compute_metrics: ``dataloader.dataset`` exposes ``lat_sizes`` /
         ``lat_names``, the loader iterates the data set in factor order and the data set enumerates ``lat_sizes``.  Every size
         is checked before any device work; train / eval mode is restored.  Returns {"factor_vae_train", "factor_vae_eval",
-        "beta_vae_train", "beta_vae_eval", "n_active", "n_train", "n_eval", "batch_size"}."""
+        "beta_vae_train", "beta_vae_eval", "n_active", "n_train", "n_eval", "batch_size"}.  fit="device": the beta-VAE score's
+        classifier is fitted by libdvae_lr_hip.so (factor_scores_from_table)."""
         _ds, lat_sizes, n = self._factor_sizes(dataloader)
         _check_score_sizes(n, lat_sizes, n_train, n_eval, batch_size, n_variance)
+        _check_fit(fit, n_train, None, [len(lat_sizes)])
         mean, _logvar = self._encode(dataloader, n, lat_sizes)
         return factor_scores_from_table(mean, lat_sizes, n_train=n_train, n_eval=n_eval, batch_size=batch_size,
-                                        n_variance=n_variance, active_threshold=active_threshold, seed=seed, draws=draws)
+                                        n_variance=n_variance, active_threshold=active_threshold, seed=seed, draws=draws,
+                                        **({} if fit == "host" else {"fit": fit}))      # the default hands on what it always did
 
     # ------------------------------------------------------------------ discretised MIG / modularity / SAP
     def compute_information_scores(self, dataloader, n_samples=None, n_bins=20, seed=0):
@@ -506,14 +521,26 @@ class Evaluator:
         mean, _logvar = self._encode(dataloader, n, lat_sizes)
         return fairness_from_table(mean, lat_sizes, n_train=n_train, n_test_per_value=n_test_per_value, seed=seed, n_stages=n_stages)
 
-    def compute_explicitness(self, dataloader, n_train=10000, n_test=5000, seed=0):
+    def compute_explicitness(self, dataloader, n_train=10000, n_test=5000, seed=0, fit="host"):
         """Explicitness of the model's representation (explicitness_from_table below, on the posterior means of the whole data set
+        through the native encoder).  The data-set requirements and errors of compute_factor_scores; every size and argument is
+        checked before any device work; train / eval mode is restored.  fit="device": the K logistic regressions are fitted by
+        libdvae_lr_hip.so (explicitness_from_table)."""
+        _ds, lat_sizes, n = self._factor_sizes(dataloader)
+        _check_dci_arguments(n, None, lat_sizes, n_train, n_test, seed, None, 1)
+        _check_fit(fit, n_train, None, lat_sizes)
+        mean, _logvar = self._encode(dataloader, n, lat_sizes)
+        return explicitness_from_table(mean, lat_sizes, n_train=n_train, n_test=n_test, seed=seed,
+                                       **({} if fit == "host" else {"fit": fit}))       # the default hands on what it always did
+
+    def compute_infoe(self, dataloader, n_train=10000, n_test=5000, C=1.0, standardize=True, seed=0, rows=None):
+        """InfoE of the model's representation (Hsu et al. 2023; infoe_from_table below, on the posterior means of the whole data set
         through the native encoder).  The data-set requirements and errors of compute_factor_scores; every size and argument is
         checked before any device work; train / eval mode is restored."""
         _ds, lat_sizes, n = self._factor_sizes(dataloader)
-        _check_dci_arguments(n, None, lat_sizes, n_train, n_test, seed, None, 1)
+        _check_infoe_arguments(n, None, lat_sizes, n_train, n_test, C, seed, rows)
         mean, _logvar = self._encode(dataloader, n, lat_sizes)
-        return explicitness_from_table(mean, lat_sizes, n_train=n_train, n_test=n_test, seed=seed)
+        return infoe_from_table(mean, lat_sizes, n_train=n_train, n_test=n_test, C=C, standardize=standardize, seed=seed, rows=rows)
 
     # ------------------------------------------------------------------ MIG / AAM (evaluate.py:119-317)
     def compute_metrics(self, dataloader, sample_idx=None, n_samples=10000):
@@ -767,7 +794,7 @@ def _classifier_accuracy(W, b, classes, features, labels):
 
 
 def factor_scores_from_table(mean, lat_sizes, n_train=10000, n_eval=5000, batch_size=64, n_variance=10000,
-                             active_threshold=0.05, seed=0, draws=None, return_details=False):
+                             active_threshold=0.05, seed=0, draws=None, return_details=False, fit="host"):
     """FactorVAE score and beta-VAE score of a representation given as the fp32 [N, D] table ``mean`` (on the GPU) of a data
     set that enumerates ``lat_sizes`` in row-major order.
 
@@ -786,13 +813,17 @@ def factor_scores_from_table(mean, lat_sizes, n_train=10000, n_eval=5000, batch_
     untouched).  ``draws`` injects them, each key on its own: "variance_rows" ([n] rows), "factor_vae_train" /
     "factor_vae_eval" ((factor, rows)), "beta_vae_train" / "beta_vae_eval" ((factor, rows_a, rows_b)); injected rows and
     factors are range-checked here (the kernels do not).  return_details=True: (scores, details) with the host copies of var,
-    active, the vote matrices, the classifier, the beta-VAE features / labels and (W, b)."""
+    active, the vote matrices, the classifier, the beta-VAE features / labels and (W, b).
+    fit="device": the beta-VAE classifier is fitted where its features lie (dvae_lr_fit of libdvae_lr_hip.so, the same objective
+    to tolerance_grad 1e-8; a fit that does not get there raises DvaeHipError) and its accuracies are dvae_lr_predict's counts
+    of correct rows; n_train <= 16384 and D <= 64 then."""
     lat_sizes = [int(k) for k in lat_sizes]
     K = len(lat_sizes)
     if mean.dim() != 2:
         raise ValueError("mean must be an [N, D] table, got shape %s" % (tuple(mean.shape),))
     n, dim = int(mean.shape[0]), int(mean.shape[1])
     _check_score_sizes(n, lat_sizes, n_train, n_eval, batch_size, n_variance)
+    _check_fit(fit, n_train, dim, [K])
     if n != int(np.prod(lat_sizes)):
         raise ValueError("data set of %d images does not enumerate lat_sizes=%s" % (n, lat_sizes))
     if dim < 1:
@@ -870,6 +901,10 @@ def factor_scores_from_table(mean, lat_sizes, n_train=10000, n_eval=5000, batch_
         out = torch.empty(V, dim, dtype=torch.float32, device=dev)
         _scorelib.call("dvae_score_pair_absdiff", ptr(table), ptr(rows_a), ptr(rows_b), n, dim, V, L, ptr(out), st)
         feats[key], labels[key] = out, factor
+    if fit == "device":
+        return _beta_vae_on_the_device(feats, labels, factor_vae_train, factor_vae_eval, active, n_train, n_eval, L, st, return_details,
+                                       {"var": var, "active": active, "votes_train": votes_train, "votes_eval": votes_eval,
+                                        "classifier": classifier})
     feats = {k: v.cpu().double() for k, v in feats.items()}
     labels = {k: v.cpu().to(torch.int64) for k, v in labels.items()}
     classes = torch.unique(labels["train"])                                            # sorted
@@ -2238,7 +2273,7 @@ def class_probabilities(W, b, features):
     return torch.softmax(torch.as_tensor(features, dtype=torch.float64) @ W.t() + b, dim=1)
 
 
-def explicitness_from_table(mean, lat_sizes, n_train=10000, n_test=5000, seed=0, rows=None, return_details=False):
+def explicitness_from_table(mean, lat_sizes, n_train=10000, n_test=5000, seed=0, rows=None, return_details=False, fit="host"):
     """Explicitness (Ridgeway & Mozer 2018; the second half of disentanglement_lib's modularity_explicitness.py) of a
     representation given as the fp32 [N, D] table ``mean`` (on the GPU) of a data set that enumerates ``lat_sizes`` in row-major
     order: per factor the multinomial logistic regression of the beta-VAE score (fit_logistic_regression, C = 1.0, fp64 on the
@@ -2256,11 +2291,15 @@ def explicitness_from_table(mean, lat_sizes, n_train=10000, n_test=5000, seed=0,
     dci_from_table) and a table with a NaN or an infinity raises ValueError.  Returns {"explicitness_train", "explicitness_test",
     "explicitness_train_per_factor", "explicitness_test_per_factor" [K], "n_train", "n_test"}: Python and numpy values.
     return_details=True: (scores, details) with per factor "classes", "W", "b", the fp32 "probabilities_train" /
-    "probabilities_test" that were ranked, "labels_train" / "labels_test" (-1: a value never seen) and the per-class AUCs."""
+    "probabilities_test" that were ranked, "labels_train" / "labels_test" (-1: a value never seen) and the per-class AUCs.
+    fit="device": the K regressions are fitted by ONE dvae_lr_fit call on the gathered rows where they lie (libdvae_lr_hip.so: the
+    same objective to tolerance_grad 1e-8; a fit that does not get there raises DvaeHipError) and the probabilities come from
+    dvae_lr_predict (formed in fp64, rounded once) without leaving the device; at most 8 factors and 64 latents then."""
     lat_sizes = [int(k) for k in lat_sizes]
     K, n_train, n_test = len(lat_sizes), int(n_train), int(n_test)
     n, dim = _table_shape(mean)
     _check_dci_arguments(int(np.prod(lat_sizes)) if lat_sizes else 0, dim, lat_sizes, n_train, n_test, seed, rows, 1)
+    _check_fit(fit, n_train, dim, lat_sizes)
     _check_table_enumerates(n, lat_sizes)
     if rows is not None and torch.as_tensor(rows).numel() != n_train + n_test:
         raise ValueError("rows must hold n_train + n_test = %d row numbers" % (n_train + n_test))
@@ -2268,9 +2307,13 @@ def explicitness_from_table(mean, lat_sizes, n_train=10000, n_test=5000, seed=0,
     L = _udrlib.lib()
     st = _stream()
     strides = _factor_strides(lat_sizes)
-    features = table.index_select(0, rows).cpu().double()                          # [n_train + n_test, D]: the fit is the host's
-    rows_host = rows.cpu()
     sets = (("train", slice(0, n_train)), ("test", slice(n_train, n_train + n_test)))
+    if fit == "device":
+        probes = _DeviceProbes(table, rows, n_train, lat_sizes, 1.0, LR_TOLERANCE_GRAD, False, st, with_prob=True)
+        on_device = probes.per_factor("explicitness_from_table")         # the read-back of the coefficients and of the solver's report
+    else:
+        features = table.index_select(0, rows).cpu().double()                      # [n_train + n_test, D]: the fit is the host's
+    rows_host = rows.cpu()
     enqueued, details = [], []
     for k in range(K):
         values = (rows_host // strides[k]) % lat_sizes[k]
@@ -2278,14 +2321,19 @@ def explicitness_from_table(mean, lat_sizes, n_train=10000, n_test=5000, seed=0,
         C = int(classes.numel())
         at = torch.searchsorted(classes, values).clamp(max=C - 1)
         labels = torch.where(classes[at] == values, at, torch.full_like(at, -1))   # -1: a value never seen in training
-        if C > 1:
+        if fit == "device":
+            W, b = on_device[k]["W"], on_device[k]["b"]
+        elif C > 1:
             W, b = fit_logistic_regression(features[:n_train], labels[:n_train], C, C=1.0)
         else:                                                            # one class: nothing to fit
             W, b = torch.zeros(1, dim, dtype=torch.float64), torch.zeros(1, dtype=torch.float64)
         detail = {"classes": classes, "W": W, "b": b}
         for name, part in sets:
             S = part.stop - part.start
-            prob = class_probabilities(W, b, features[part]).to(torch.float32).to(dev)                   # [S, C], rounded to fp32
+            if fit == "device":
+                prob = on_device[k]["prob_" + name]                      # [S, C] fp32, where dvae_lr_predict wrote it
+            else:
+                prob = class_probabilities(W, b, features[part]).to(torch.float32).to(dev)               # [S, C], rounded to fp32
             lab = labels[part].to(dev)
             rank_sum = torch.empty(C, dtype=torch.float64, device=dev)
             for lo in range(0, C, _udrlib.MAX_D):
@@ -2311,3 +2359,287 @@ def explicitness_from_table(mean, lat_sizes, n_train=10000, n_test=5000, seed=0,
     for d in details:
         d["probabilities_train"], d["probabilities_test"] = d["probabilities_train"].cpu(), d["probabilities_test"].cpu()
     return scores, details
+
+
+# ---------------------------------------------------------------------- linear-softmax probes fitted on the device
+LR_TOLERANCE_GRAD = 1e-8                                                 # fit_logistic_regression's own
+
+
+def _check_lr_sizes(n_rows, dim, n_classes):
+    """The limits of libdvae_lr_hip.so, before any device work.  dim: None where not known yet."""
+    n_classes = [int(c) for c in n_classes]
+    if not 1 <= len(n_classes) <= _lrlib.MAX_PROBLEMS:
+        raise ValueError("%d problems of one call: the softmax-regression kernels take between 1 and %d" % (len(n_classes), _lrlib.MAX_PROBLEMS))
+    if not all(1 <= c <= _lrlib.MAX_CLASSES for c in n_classes):
+        raise ValueError("a problem with %d classes: the softmax-regression kernels take between 1 and %d"
+                         % (max(n_classes) if min(n_classes) >= 1 else min(n_classes), _lrlib.MAX_CLASSES))
+    if not 1 <= int(n_rows) <= _lrlib.MAX_ROWS:
+        raise ValueError("the softmax-regression kernels fit between 1 and %d rows, got %r" % (_lrlib.MAX_ROWS, n_rows))
+    if dim is not None and not 1 <= int(dim) <= _lrlib.MAX_D:
+        raise ValueError("the softmax-regression kernels take between 1 and %d features, got %d" % (_lrlib.MAX_D, dim))
+
+
+def _check_lr_numbers(C, tolerance_grad):
+    if not (isinstance(C, numbers.Real) and 0.0 < float(C) < math.inf):
+        raise ValueError("C must be a positive finite number, got %r" % (C,))
+    if not (isinstance(tolerance_grad, numbers.Real) and 0.0 <= float(tolerance_grad) < math.inf):
+        raise ValueError("tolerance_grad must be a finite number >= 0, got %r" % (tolerance_grad,))
+
+
+def _check_fit(fit, n_train, dim, lat_sizes):
+    """fit = "host" | "device" of the scores that fit a logistic regression; "device" is held to libdvae_lr_hip.so's limits."""
+    if fit not in ("host", "device"):
+        raise ValueError('fit must be "host" or "device", got %r' % (fit,))
+    if fit == "device":
+        _check_lr_sizes(n_train, dim, lat_sizes)
+
+
+def _standardizer_on_the_device(features, st):
+    """(shift, scale) fp64 [D] on the device of the fp32 [S, D] features: the column mean and 1 / population std from
+    dvae_unsup_moments (fp64 throughout); a constant column -- its largest element is its smallest -- gets scale 0."""
+    S, D = int(features.shape[0]), int(features.shape[1])
+    dev = features.device
+    ws = torch.empty(max(_unsuplib.lib().dvae_unsup_moments_ws_floats(S, D, S), 1), dtype=torch.float32, device=dev)
+    out = torch.empty(D * D + 2 * D, dtype=torch.float64, device=dev)     # cov, mean, then min and max: 2 D floats in D doubles
+    minmax = out[D * D + D:].view(torch.float32)
+    _unsuplib.call("dvae_unsup_moments", ptr(features), None, S, D, S, ptr(ws), ptr(minmax[:D]), ptr(minmax[D:]), ptr(out[D * D:D * D + D]),
+                   ptr(out[:D * D]), st)
+    var = out[:D * D].view(D, D).diagonal() * ((S - 1.0) / S)             # ddof = 1 -> the population variance
+    live = (minmax[D:] > minmax[:D]) & (var > 0)
+    scale = torch.where(live, torch.rsqrt(torch.where(live, var, torch.ones_like(var))), torch.zeros_like(var))
+    return out[D * D:D * D + D].contiguous(), scale.contiguous()
+
+
+def _lr_fit(features, labels, n_classes, C, tolerance_grad, shift, scale, st):
+    """dvae_lr_fit enqueued: features fp32 [S, D], labels int32 [Q, S], both contiguous on the device -> (coef fp64 flat, report
+    fp64 [Q, 4]) on the device.  Nothing is read back."""
+    S, D, Q = int(features.shape[0]), int(features.shape[1]), len(n_classes)
+    dev = features.device
+    host = _lrlib.host_classes(n_classes)
+    n_bytes = _lrlib.lib().dvae_lr_ws_bytes(S, D, host, Q)
+    if n_bytes < 0:
+        raise ValueError("dvae_lr_ws_bytes refuses S = %d, D = %d, classes %s" % (S, D, list(n_classes)))
+    ws = torch.empty(max(n_bytes // 8, 1), dtype=torch.float64, device=dev)
+    coef = torch.empty(sum(_lrlib.coef_sizes(n_classes, D)), dtype=torch.float64, device=dev)
+    report = torch.empty(Q, 4, dtype=torch.float64, device=dev)
+    _lrlib.call("dvae_lr_fit", ptr(features), ptr(shift), ptr(scale), ptr(labels), host, S, D, Q, float(C), float(tolerance_grad), ptr(ws),
+                ptr(coef), ptr(report), st)
+    return coef, report
+
+
+def _lr_predict(features, labels, n_classes, coef, shift, scale, st, with_prob):
+    """dvae_lr_predict enqueued -> {"prob": fp32 flat or None, "log_loss" fp64 [Q], "correct", "counted" int32 [Q]} on the device."""
+    T, D, Q = int(features.shape[0]), int(features.shape[1]), len(n_classes)
+    dev = features.device
+    out = {"prob": torch.empty(T * sum(n_classes), dtype=torch.float32, device=dev) if with_prob else None,
+           "log_loss": torch.empty(Q, dtype=torch.float64, device=dev), "correct": torch.empty(Q, dtype=torch.int32, device=dev),
+           "counted": torch.empty(Q, dtype=torch.int32, device=dev)}
+    _lrlib.call("dvae_lr_predict", ptr(features), ptr(shift), ptr(scale), ptr(labels), _lrlib.host_classes(n_classes), T, D, Q, ptr(coef),
+                ptr(out["prob"]), ptr(out["log_loss"]), ptr(out["correct"]), ptr(out["counted"]), st)
+    return out
+
+
+def _lr_converged(report, caller):
+    """The host copy of the solver's report [Q, 4]; DvaeHipError naming the first problem that stopped short of tolerance_grad."""
+    report = report.cpu().numpy()
+    short = np.flatnonzero(report[:, 2] < 0)
+    if short.size:
+        q = int(short[0])
+        raise _lib.DvaeHipError("%s: dvae_lr_fit: problem %d (of %d; %d in all) did not meet tolerance_grad within %d Newton steps: max |gradient| "
+                                "%.3e after %d function evaluations" % (caller, q, report.shape[0], short.size, _lrlib.MAX_ITERATIONS,
+                                                                        report[q, 1], int(report[q, 3])))
+    return report
+
+
+def _split_coef(coef, n_classes, dim):
+    """The flat host coefficients -> [(W [C, D], b [C])] fp64 tensors, one per problem."""
+    out, at = [], 0
+    for C in n_classes:
+        out.append((coef[at:at + C * dim].view(C, dim).clone(), coef[at + C * dim:at + C * (dim + 1)].clone()))
+        at += C * (dim + 1)
+    return out
+
+
+def fit_logistic_regression_device(features, labels, n_classes, C=1.0, tolerance_grad=LR_TOLERANCE_GRAD, standardize=False,
+                                   return_report=False):
+    """fit_logistic_regression's problem -- minimise mean cross-entropy + ||W||^2 / (2 C n) with an unpenalised bias, from zero --
+    solved ON THE DEVICE by dvae_lr_fit (libdvae_lr_hip.so: truncated Newton-CG in fp64, one launch) until the largest absolute
+    gradient entry is at most ``tolerance_grad``.  features [n, D] (n <= 16384, D <= 64) on the GPU, rounded to fp32 if they are not;
+    labels [n] in [0, n_classes), n_classes <= 256.  Returns (W [n_classes, D], b [n_classes]) as fp64 CPU tensors like the host
+    function, b on sum b = 0; unlike it, a fit that stops short of the tolerance raises DvaeHipError naming the problem.
+    standardize=True fits on (x - column mean) / population std (a constant column: on 0) and returns the coefficients folded back to
+    the raw features (W scale, b - W scale . shift).  return_report=True: (W, b, report) with the solver's (objective, max |gradient|,
+    Newton steps, function evaluations)."""
+    features = torch.as_tensor(features)
+    if features.dim() != 2:
+        raise ValueError("features must be an [n, D] matrix, got shape %s" % (tuple(features.shape),))
+    n, dim = int(features.shape[0]), int(features.shape[1])
+    _check_lr_sizes(n, dim, [n_classes])
+    _check_lr_numbers(C, tolerance_grad)
+    labels = torch.as_tensor(labels).reshape(-1)
+    if labels.numel() != n or not (0 <= int(labels.min()) and int(labels.max()) < int(n_classes)):
+        raise ValueError("labels must hold %d classes in [0, %d)" % (n, int(n_classes)))
+    if not bool(torch.isfinite(features).all()):
+        raise ValueError("the features hold a NaN or an infinity")
+    if not features.is_cuda:
+        raise _lib.DvaeHipError("fit_logistic_regression_device needs the features on the GPU (there is no CPU / PyTorch fallback for the "
+                                "softmax-regression kernels)")
+    dev = features.device
+    x = features.detach().to(torch.float32).contiguous()
+    y = labels.to(dev, torch.int32).view(1, n).contiguous()
+    st = _stream()
+    shift, scale = _standardizer_on_the_device(x, st) if standardize else (None, None)
+    coef, report = _lr_fit(x, y, [int(n_classes)], C, tolerance_grad, shift, scale, st)
+    report = _lr_converged(report, "fit_logistic_regression_device")
+    W, b = _split_coef(coef.cpu(), [int(n_classes)], dim)[0]
+    if standardize:
+        shift, scale = shift.cpu(), scale.cpu()
+        W = W * scale
+        b = b - W @ shift
+    return (W, b, report[0]) if return_report else (W, b)
+
+
+class _DeviceProbes:
+    """The linear-softmax probes of every factor of variation, fitted and evaluated on the device: what explicitness_from_table
+    (fit="device") and infoe_from_table share.  rows int64 [n_train + n_test] on the device, the first n_train to fit; the labels of
+    factor k are the ranks of its values among those PRESENT in the training rows (-1 for a test row whose value is not).  ONE
+    dvae_lr_fit call fits all K problems on the gathered rows and two dvae_lr_predict calls evaluate them; nothing is read back here
+    but the number of classes present per factor, which sizes the coefficients."""
+
+    def __init__(self, table, rows, n_train, lat_sizes, C, tolerance_grad, standardize, st, with_prob):
+        self.dim, self.n_train, self.n_test = int(table.shape[1]), int(n_train), int(rows.numel()) - int(n_train)
+        gathered = table.index_select(0, rows)                           # the torch gather is plumbing
+        self.x = {"train": gathered[:n_train].contiguous(), "test": gathered[n_train:].contiguous()}
+        train, test = rows[:n_train], rows[n_train:]
+        labels_train, labels_test, self.n_classes, self.classes = [], [], [], []
+        for stride, size in zip(_factor_strides(lat_sizes), lat_sizes):
+            values_train, values_test = (train // stride) % size, (test // stride) % size
+            classes = torch.unique(values_train)                         # sorted; its length is the one number the host needs now
+            self.n_classes.append(int(classes.numel()))
+            self.classes.append(classes)
+            labels_train.append(torch.searchsorted(classes, values_train))
+            at = torch.searchsorted(classes, values_test).clamp(max=self.n_classes[-1] - 1)
+            labels_test.append(torch.where(classes[at] == values_test, at, torch.full_like(at, -1)))
+        self.labels = {"train": torch.stack(labels_train).to(torch.int32).contiguous(),
+                       "test": torch.stack(labels_test).to(torch.int32).contiguous()}
+        self.shift, self.scale = _standardizer_on_the_device(self.x["train"], st) if standardize else (None, None)
+        self.coef, self.report = _lr_fit(self.x["train"], self.labels["train"], self.n_classes, C, tolerance_grad, self.shift, self.scale, st)
+        self.out = {name: _lr_predict(self.x[name], self.labels[name], self.n_classes, self.coef, self.shift, self.scale, st, with_prob)
+                    for name in ("train", "test") if self.x[name].shape[0] > 0}
+
+    def per_factor(self, caller):
+        """The read-back of the report (raises where a fit stopped short) and of the coefficients -> per factor {"W", "b" (fp64, CPU),
+        "prob_train", "prob_test" (fp32 [rows, C] views on the device, where the probabilities were asked for)}."""
+        self.report_host = _lr_converged(self.report, caller)
+        out = [{"W": W, "b": b} for W, b in _split_coef(self.coef.cpu(), self.n_classes, self.dim)]
+        for name, got in self.out.items():
+            at, rows = 0, int(self.x[name].shape[0])
+            for k, C in enumerate(self.n_classes):
+                if got["prob"] is not None:
+                    out[k]["prob_" + name] = got["prob"][at:at + rows * C].view(rows, C)
+                at += rows * C
+        return out
+
+
+def _beta_vae_on_the_device(feats, labels, factor_vae_train, factor_vae_eval, active, n_train, n_eval, L, st, return_details, details):
+    """The beta-VAE half of factor_scores_from_table with fit="device": feats fp32 [V, D] and labels int32 [V] of the train and the
+    eval set where dvae_score_pair_absdiff left them; the classes are the factors that occur in the train set."""
+    dim = int(feats["train"].shape[1])
+    factor = {k: v.to(torch.int64) for k, v in labels.items()}
+    classes = torch.unique(factor["train"])                              # sorted; its length sizes the coefficients
+    C = int(classes.numel())
+    ranks = {}
+    for key in ("train", "eval"):
+        at = torch.searchsorted(classes, factor[key]).clamp(max=C - 1)
+        ranks[key] = torch.where(classes[at] == factor[key], at, torch.full_like(at, -1)).to(torch.int32).view(1, -1).contiguous()
+    coef, report = _lr_fit(feats["train"], ranks["train"], [C], 1.0, LR_TOLERANCE_GRAD, None, None, st)
+    counts = {key: _lr_predict(feats[key], ranks[key], [C], coef, None, None, st, False)["correct"] for key in ("train", "eval")}
+    _lr_converged(report, "factor_scores_from_table")
+    scores = {"factor_vae_train": factor_vae_train, "factor_vae_eval": factor_vae_eval,
+              "beta_vae_train": int(counts["train"].item()) / float(n_train), "beta_vae_eval": int(counts["eval"].item()) / float(n_eval),
+              "n_active": int(active.sum()), "n_train": n_train, "n_eval": n_eval, "batch_size": L}
+    if not return_details:
+        return scores
+    W, b = _split_coef(coef.cpu(), [C], dim)[0]
+    details.update(features_train=feats["train"].cpu().double(), features_eval=feats["eval"].cpu().double(),
+                   labels_train=factor["train"].cpu(), labels_eval=factor["eval"].cpu(), classes=classes.cpu(), W=W, b=b)
+    return scores, details
+
+
+# ---------------------------------------------------------------------- InfoE on a table of means
+def _check_infoe_arguments(n, dim, lat_sizes, n_train=10000, n_test=5000, C=1.0, seed=0, rows=None):
+    """n: prod(lat_sizes); dim: None where not known yet.  The rows and checks of explicitness_from_table / dci_from_table, then the
+    limits of libdvae_lr_hip.so."""
+    _check_dci_arguments(n, dim, lat_sizes, n_train, n_test, seed, rows, 1)
+    _check_lr_sizes(n_train, dim, lat_sizes)
+    _check_lr_numbers(C, 0.0)
+
+
+def infoe_from_log_loss(ce_model, ce_null):
+    """The InfoE of Hsu et al. 2023 (the normalised predictive V-information of a factor given the latents, V = linear-softmax
+    probes) from two cross-entropies per factor, pure numpy: ce_model [K], the mean negative log-likelihood of the probe, and
+    ce_null [K], that of the best constant prediction (the class frequencies of the training rows: their entropy on those rows).
+    -> (per_factor [K] = 1 - ce_model / ce_null, UNCLIPPED, NaN where ce_null is not positive -- a factor with one class present --
+    or a cross-entropy is not finite; the mean over the other factors of max(0, .), NaN when there is none)."""
+    ce_model, ce_null = np.asarray(ce_model, dtype=np.float64), np.asarray(ce_null, dtype=np.float64)
+    if ce_model.shape != ce_null.shape or ce_model.ndim != 1:
+        raise ValueError("ce_model and ce_null must be two [K] vectors, got shapes %s and %s" % (ce_model.shape, ce_null.shape))
+    ok = np.isfinite(ce_model) & np.isfinite(ce_null)
+    ok[ok] = ce_null[ok] > 0
+    per_factor = np.full(ce_model.shape, np.nan)
+    per_factor[ok] = 1.0 - ce_model[ok] / ce_null[ok]
+    return per_factor, (float(np.maximum(per_factor[ok], 0.0).mean()) if ok.any() else float("nan"))
+
+
+def infoe_from_table(mean, lat_sizes, n_train=10000, n_test=5000, C=1.0, standardize=True, seed=0, rows=None):
+    """InfoE -- explicitness in the InfoMEC triple of Hsu et al. 2023, next to InfoM and InfoC of knn_information_scores_from_table --
+    of a representation given as the fp32 [N, D] table ``mean`` (on the GPU) of a data set that enumerates ``lat_sizes`` in row-major
+    order: per factor k the multinomial logistic regression of include/dvae_lr_hip.h (fit_logistic_regression's objective with this
+    ``C``) predicts the factor from all latents of n_train rows; with ce_model = its mean negative log-likelihood and ce_null = the
+    cross-entropy of the class frequencies OF THE TRAINING ROWS (on them: the empirical entropy H(s_k)),
+    infoe_per_factor = 1 - ce_model / ce_null (infoe_from_log_loss), on the training rows and on n_test others.  theta = (0, log
+    frequencies) is feasible at no penalty, so the training value is >= 0 up to the solver's tolerance.
+
+    Rows and checks as in explicitness_from_table / dci_from_table: randperm(N)[:n_train + n_test] from a private generator seeded
+    with ``seed`` (the same seed gives the same bits, the global random states are untouched), the first n_train to fit; ``rows``
+    injects the selection.  Labels are the ranks of the values PRESENT in the training rows; a test row whose value was never seen
+    is left out of ce_model_test and ce_null_test (n_unseen counts them) and is an error in accuracy_test.  standardize=True fits on
+    (x - shift) scale with shift = the column mean and scale = 1 / population std of the training rows (dvae_unsup_moments, fp64; a
+    constant column gets scale 0 and weights exactly 0).  All K factors are fitted by ONE dvae_lr_fit call and evaluated by two
+    dvae_lr_predict calls before anything is read back but the number of classes present per factor; a fit that stops short of
+    tolerance_grad = 1e-8 raises DvaeHipError.  At most 8 factors, 256 values a factor, 64 latents, 10 240 training rows.
+    Returns {"infoe_train", "infoe_test" (the means over the factors with two classes or more of max(0, .)),
+    "infoe_train_per_factor", "infoe_test_per_factor" [K] (unclipped; NaN for a one-class factor), "ce_model_train", "ce_model_test",
+    "ce_null_train", "ce_null_test", "accuracy_train", "accuracy_test" [K], "n_unseen" [K], "report" [K, 4] (the solver's objective,
+    max |gradient|, Newton steps, function evaluations), "n_train", "n_test", "C", "standardize"}: Python and numpy values."""
+    lat_sizes = [int(k) for k in lat_sizes]
+    K, n_train, n_test = len(lat_sizes), int(n_train), int(n_test)
+    n, dim = _table_shape(mean)
+    _check_infoe_arguments(int(np.prod(lat_sizes)) if lat_sizes else 0, dim, lat_sizes, n_train, n_test, C, seed, rows)
+    _check_table_enumerates(n, lat_sizes)
+    if rows is not None and torch.as_tensor(rows).numel() != n_train + n_test:
+        raise ValueError("rows must hold n_train + n_test = %d row numbers" % (n_train + n_test))
+    table, rows, _S, dev = _select_rows(mean, rows, n_train + n_test, seed, "infoe_from_table", "softmax-regression")
+    st = _stream()
+    probes = _DeviceProbes(table, rows, n_train, lat_sizes, float(C), LR_TOLERANCE_GRAD, bool(standardize), st, with_prob=False)
+    width = max(probes.n_classes)
+    counts = torch.stack([torch.stack([torch.bincount(probes.labels[name][k] + 1, minlength=width + 1)[1:] for k in range(K)])
+                          for name in ("train", "test")])                # [2, K, width] rows per class (the unseen ones left out)
+    # ---- the read-back, after everything was enqueued
+    report = _lr_converged(probes.report, "infoe_from_table")
+    counts = counts.cpu().numpy().astype(np.float64)
+    got = {name: {k: v.cpu().numpy() for k, v in out.items() if v is not None} for name, out in probes.out.items()}
+    result = {}
+    for i, (name, total) in enumerate((("train", n_train), ("test", n_test))):
+        counted = got[name]["counted"].astype(np.float64)
+        freq = counts[0] / float(n_train)                                # the class frequencies of the TRAINING rows
+        with np.errstate(divide="ignore", invalid="ignore"):
+            log_freq = np.where(counts[0] > 0, np.log(np.where(counts[0] > 0, freq, 1.0)), 0.0)
+            ce_null = -(counts[i] * log_freq).sum(axis=1) / counted
+            ce_model = got[name]["log_loss"] / counted
+        per_factor, score = infoe_from_log_loss(ce_model, ce_null)
+        result.update({"infoe_" + name: score, "infoe_%s_per_factor" % name: per_factor, "ce_model_" + name: ce_model,
+                       "ce_null_" + name: ce_null, "accuracy_" + name: got[name]["correct"] / float(total)})
+    result.update(n_unseen=(n_test - got["test"]["counted"]).astype(np.int64), report=report, n_train=n_train, n_test=n_test, C=float(C),
+                  standardize=bool(standardize))
+    return result
