@@ -122,3 +122,85 @@ class DeviceImageLoader:
                 batch = self.images.index_select(0, order_dev[lo:lo + per])   # gather on the device: uint8, B x C x H x W bytes
                 lab = 0 if self.labels is None else self.labels[order[lo:lo + per]]
             yield batch, lab
+
+
+def draw_pair_partners(rows, lat_sizes, k, generator):
+    """Partners for the weakly-supervised pair losses (Locatello et al. 2020; models.losses.WeakVaeLoss): for every row of a data
+    set that enumerates ``lat_sizes`` in row-major order (a row is sum_j value_j * stride_j, as evaluate.draw_fixed_factor_rows
+    has it) the row of an image that differs from it in a few factors of variation and shares the others.
+
+    Only factors with two values or more are eligible (e of them).  k = 1 changes exactly one of them, k >= 2 exactly
+    min(k, e), k = -1 a number drawn uniformly from 1 .. max(1, e - 1) per row (at least one eligible factor stays shared when
+    there are two).  The changed factors are drawn without replacement, and the new value of a changed factor uniformly among
+    its OTHER values: it really changes.  All draws come from ``generator`` (a CPU torch.Generator) in a fixed order -- the
+    counts (k = -1 only), one uniform score per (row, eligible factor), one offset per eligible factor in factor order -- so the
+    same seed gives the same pairs.
+
+    rows: int64 [n] (any order, repeats allowed) -> (partner_rows int64 [n], changed int64 [n]: bit j set when factor j differs)."""
+    sizes = [int(s) for s in lat_sizes]
+    K = len(sizes)
+    if K > 63:
+        raise ValueError("at most 63 factors of variation (the changed-factor mask is one int64), got %d" % K)
+    k = int(k)
+    if k == 0 or k < -1:
+        raise ValueError("k must be -1 (a random number of changed factors) or >= 1, got %d" % k)
+    eligible = [j for j, s in enumerate(sizes) if s >= 2]
+    e = len(eligible)
+    if e == 0:
+        raise ValueError("no factor of variation takes two values or more: lat_sizes=%s" % (sizes,))
+    rows = torch.as_tensor(rows, dtype=torch.int64, device="cpu").reshape(-1)
+    n = rows.numel()
+    strides = [int(np.prod(sizes[j + 1:], dtype=np.int64)) for j in range(K)]
+    if k == -1:
+        count = torch.randint(1, max(1, e - 1) + 1, (n,), generator=generator)
+    else:
+        count = torch.full((n,), min(k, e), dtype=torch.int64)
+    # without replacement: the `count` eligible factors with the smallest scores
+    rank = torch.rand(n, e, generator=generator).argsort(dim=1).argsort(dim=1)
+    pick = rank < count.view(n, 1)                                        # [n, e]
+    partner = rows.clone()
+    changed = torch.zeros(n, dtype=torch.int64)
+    for col, j in enumerate(eligible):
+        value = (rows // strides[j]) % sizes[j]
+        offset = torch.randint(1, sizes[j], (n,), generator=generator)    # 1 .. size - 1: uniform over the other values
+        new = (value + offset) % sizes[j]
+        on = pick[:, col].to(torch.int64)
+        partner += on * (new - value) * strides[j]
+        changed |= on << j
+    return partner, changed
+
+
+class PairedFactorLoader(DeviceImageLoader):
+    """Batches of image PAIRS for WeakVaeLoss out of a device-resident data set that enumerates its factors of variation by row
+    number (dSprites, 3D shapes, ...: prod(lat_sizes) images in row-major order of the factor values).
+
+    ``batch_size`` counts PAIRS: an item is ``(batch, changed)`` with ``batch`` uint8 [2 P, C, H, W] -- rows [0, P) the first
+    members, rows [P, 2 P) their partners, the layout WeakVaeLoss.fused_step takes -- and ``changed`` int64 [P] on the host, bit j
+    set when factor j differs within the pair (a label for diagnostics: the loss does not read it).  ``len()`` is
+    ceil(N / batch_size); the last batch may be smaller.
+
+    Per epoch the first members follow ``DeviceImageLoader.epoch_order(N)`` (the reference loader's consumption of the global CPU
+    generator), then ONE more ``random_()`` draw of that generator seeds a private generator from which ``draw_pair_partners``
+    draws a partner for each of the N images, on the host.  The row numbers of all batches go to the device in one copy; a
+    batch is one ``index_select`` of 2 P rows.  ``k``: how many factors a partner changes (draw_pair_partners)."""
+
+    def __init__(self, images, lat_sizes, batch_size=64, k=1, device="cuda"):
+        super().__init__(images, batch_size=batch_size, shuffle=True, device=device)
+        self.lat_sizes = tuple(int(s) for s in lat_sizes)
+        if int(np.prod(self.lat_sizes, dtype=np.int64)) != self.n_images:
+            raise ValueError("lat_sizes %s enumerate %d images, the data set has %d"
+                             % (self.lat_sizes, int(np.prod(self.lat_sizes, dtype=np.int64)), self.n_images))
+        self.k = int(k)
+        draw_pair_partners(torch.zeros(0, dtype=torch.int64), self.lat_sizes, self.k, None)     # refuses a bad k / lat_sizes now
+
+    def __iter__(self):
+        n = self.n_images
+        order = self.epoch_order(n)
+        g = torch.Generator()
+        g.manual_seed(int(torch.empty((), dtype=torch.int64).random_().item()))
+        partner, changed = draw_pair_partners(order, self.lat_sizes, self.k, g)
+        spans = self._global_batches()
+        index = torch.cat([torch.cat((order[i:i + per], partner[i:i + per])) for i, per in spans])
+        index_dev = index.to(self.images.device)           # ONE host-to-device copy per epoch
+        for i, per in spans:
+            yield self.images.index_select(0, index_dev[2 * i:2 * (i + per)]), changed[i:i + per]

@@ -539,8 +539,12 @@ class VAEEngine:
             d.update(convT_w=I(dec, "up"), convT_b=ptr(P(dec + ".bias")), convT_out=ptr(buf.dec_act[0]))
         return d
 
-    def _fc_layers_fwd(self, buf, eps, kl_dim, n_enc, n_kl, n_dec, coef):
-        """fc_chain_fwd for any latent dimension: dvae_linear_fwd x 3, dvae_reparam_kl_fwd (its run-time-D form), x 3."""
+    def _fc_layers_fwd(self, buf, eps, kl_dim, n_enc, n_kl, n_dec, coef, latent_op=None):
+        """fc_chain_fwd for any latent dimension: dvae_linear_fwd x 3, dvae_reparam_kl_fwd (its run-time-D form), x 3.
+        latent_op (None: the launches and their order are what they were): an operator on the posterior parameters between
+        mu_logvar_gen and the reparameterisation (the pair losses: models/losses.py) -- latent_op.fwd(buf.ml, n_enc) enqueues its
+        forward launch and returns the interleaved [n_enc, 2D] tensor that dvae_reparam_kl_fwd reads INSTEAD of buf.ml, so
+        buf.mu / buf.logvar / buf.z are those of the operator's output; _fc_layers_bwd(latent_op=...) is its counterpart."""
         s = _stream()
         ws = ptr(self._ws)
         D = self.latent_dim
@@ -555,11 +559,12 @@ class VAEEngine:
         # KL over the rows < n_kl only (FactorVAE: the first half batch, losses.py:255-259): two row ranges
         with_kl = kl_dim is not None and n_kl > 0
         n0 = n_kl if with_kl else n_enc
-        call("dvae_reparam_kl_fwd", ptr(buf.ml), ptr(eps), ptr(buf.mu), ptr(buf.logvar), ptr(buf.z),
+        ml = buf.ml if latent_op is None else latent_op.fwd(buf.ml, n_enc)
+        call("dvae_reparam_kl_fwd", ptr(ml), ptr(eps), ptr(buf.mu), ptr(buf.logvar), ptr(buf.z),
              ptr(kl_dim) if with_kl else None, ptr(coef) if with_kl else None, n0, D, s)
         if n0 < n_enc:
             o = n0 * D * 4
-            call("dvae_reparam_kl_fwd", ptr(buf.ml) + 2 * o, None if eps is None else ptr(eps) + o, ptr(buf.mu) + o,
+            call("dvae_reparam_kl_fwd", ptr(ml) + 2 * o, None if eps is None else ptr(eps) + o, ptr(buf.mu) + o,
                  ptr(buf.logvar) + o, ptr(buf.z) + o, None, None, n_enc - n0, D, s)
         if n_dec > 0:
             for x, name, y, K, N in ((buf.z, "decoder.lin1", buf.d1, D, HIDDEN_DIM),
@@ -568,12 +573,17 @@ class VAEEngine:
                 call("dvae_linear_fwd", ptr(x), ptr(P(name + ".weight")), ptr(P(name + ".bias")), ptr(y), n_dec, K, N,
                      ACT_RELU, ws, s)
 
-    def _fc_layers_bwd(self, buf, eps, dz2, dz3, dmu_x, dlv_x, scal, coef, n):
+    def _fc_layers_bwd(self, buf, eps, dz2, dz3, dmu_x, dlv_x, scal, coef, n, latent_op=None):
         """fc_chain_bwd for any latent dimension: dvae_linear_dgrad x 3, dvae_reparam_kl_bwd, x 3 (the launches of the
-        autograd-compatible path: decode_backward / encode_backward without fc_chain)."""
+        autograd-compatible path: decode_backward / encode_backward without fc_chain).
+        latent_op: the operator of _fc_layers_fwd -- buf.mu / buf.logvar are its output, so dvae_reparam_kl_bwd leaves the gradient
+        with respect to that output in buf.dml, and latent_op.bwd(buf.ml, buf.dml, n) enqueues the launch that turns it, in place,
+        into the gradient with respect to buf.ml."""
         self._dec_fc_dgrads(buf, n)
         call("dvae_reparam_kl_bwd", ptr(buf.dz), ptr(dz2), ptr(dz3), ptr(dmu_x), ptr(dlv_x), ptr(buf.mu), ptr(buf.logvar),
              ptr(eps), ptr(scal), ptr(coef), ptr(buf.dml), n, self.latent_dim, _stream())
+        if latent_op is not None:
+            latent_op.bwd(buf.ml, buf.dml, n)
         self._enc_fc_dgrads(buf, n)
 
     def fc_chain_bwd(self, buf, eps, dz2, dz3, dmu_x, dlv_x, scal, coef, n):

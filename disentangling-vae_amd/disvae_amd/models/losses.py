@@ -1,6 +1,7 @@
 """Loss plugins with the API of disvae/models/losses.py (get_loss_f, BaseLoss, BetaHLoss,
 BetaBLoss, FactorKLoss, BtcvaeLoss, LOSSES, RECON_DIST) on the HIP kernels, plus DipVaeLoss / DIP_LOSSES
-(DIP-VAE-I / II) and InfoVaeLoss / INFO_LOSSES (InfoVAE / MMD-VAE), which the reference does not have.
+(DIP-VAE-I / II), InfoVaeLoss / INFO_LOSSES (InfoVAE / MMD-VAE) and WeakVaeLoss / WEAK_LOSSES (Ada-GVAE / Ada-ML-VAE on image
+pairs), which the reference does not have.
 
 Two ways in:
   * ``loss(data, recon, latent_dist, is_train, storer, latent_sample=...)`` -- the reference
@@ -19,6 +20,7 @@ import torch
 
 from .. import _diplib
 from .. import _mmdlib
+from .. import _weaklib
 from .. import _lib
 from .. import optim
 from .._lib import call, ptr, record_py
@@ -33,6 +35,7 @@ LOSSES = ["VAE", "betaH", "betaB", "factor", "btcvae"]  # losses.py:17
 RECON_DIST = ["bernoulli", "laplace", "gaussian"]        # losses.py:18
 DIP_LOSSES = ["dipI", "dipII"]                           # DIP-VAE-I / II (Kumar et al. 2018): not in the reference, so not in LOSSES
 INFO_LOSSES = ["infovae"]                                # InfoVAE / MMD-VAE (Zhao et al. 2019): not in the reference either
+WEAK_LOSSES = ["adagvae", "adamlvae"]                    # Ada-GVAE / Ada-ML-VAE on image pairs (Locatello et al. 2020): nor these
 
 
 def get_loss_f(loss_name, **kwargs_parse):
@@ -58,6 +61,9 @@ def get_loss_f(loss_name, **kwargs_parse):
     elif loss_name in INFO_LOSSES:
         return InfoVaeLoss(alpha=kwargs_parse.get("info_alpha", 0.), lam=kwargs_parse.get("info_lambda", 1000.),
                            kernel=kwargs_parse.get("mmd_kernel", "imq"), bandwidth=kwargs_parse.get("mmd_bandwidth"), **kwargs_all)
+    elif loss_name in WEAK_LOSSES:
+        return WeakVaeLoss(aggregation="gvae" if loss_name == "adagvae" else "mlvae", beta=kwargs_parse.get("weak_beta", 1),
+                           **kwargs_all)
     else:
         assert loss_name not in LOSSES
         raise ValueError("Uknown loss : {}".format(loss_name))
@@ -477,6 +483,87 @@ class _MmdFn(torch.autograd.Function):
         return dz * gout, None, None, None, None
 
 
+class _PairAggregate:
+    """The latent operator of the pair losses as VAEEngine._fc_layers_fwd / _fc_layers_bwd take it: the two launches of
+    libdvae_weak_hip.so (include/dvae_weak_hip.h) around the reparameterisation, on the interleaved [rows, 2 D] layout; rows i and
+    rows / 2 + i are a pair.  Through record_py: a recorded plan re-issues them with these arguments, a hipGraph captures them."""
+
+    def __init__(self, kind, D, ml_agg, shared, delta, stream):
+        self.kind, self.D, self.ml_agg, self.shared, self.delta, self.stream = kind, D, ml_agg, shared, delta, stream
+
+    def fwd(self, ml, rows):
+        record_py(_weaklib.call, "dvae_weak_aggregate_fwd", ptr(ml), rows // 2, self.D, self.kind, ptr(self.ml_agg),
+                  ptr(self.shared), ptr(self.delta), self.stream)
+        return self.ml_agg
+
+    def bwd(self, ml, dml, rows):
+        record_py(_weaklib.call, "dvae_weak_aggregate_bwd", ptr(ml), ptr(self.shared), rows // 2, self.D, self.kind, ptr(dml),
+                  self.stream)
+
+
+def _check_pairs(rows, D):
+    """What a batch of pairs has to satisfy, before any device work."""
+    if rows < 2 or rows % 2:
+        raise ValueError("a batch of pairs has an even number of rows (rows i and rows / 2 + i are a pair), got {}".format(rows))
+    if not 1 <= D <= _weaklib.MAX_D:
+        raise ValueError("the pair losses take 1 <= latent_dim <= {} (the mask of a pair is one 64-bit word), got {}".format(
+            _weaklib.MAX_D, D))
+
+
+def _interleave(a, b):
+    """[B, D] x 2 -> the interleaved [B, 2 D] layout of mu_logvar_gen, contiguous and owned."""
+    return torch.stack((a, b), dim=-1).reshape(a.shape[0], 2 * a.shape[1]).contiguous()
+
+
+class _AdaptiveGroupFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mu, logvar, kind):
+        B, D = mu.shape
+        ml = _interleave(mu.float(), logvar.float())
+        ml_agg = torch.empty_like(ml)
+        shared = torch.empty(B // 2, dtype=torch.int64, device=mu.device)
+        op = _PairAggregate(kind, D, ml_agg, shared, None, _stream())
+        op.fwd(ml, B)
+        ctx.save_for_backward(ml, shared)
+        ctx.kind = kind
+        ctx.mark_non_differentiable(shared)
+        return ml_agg[:, 0::2].contiguous(), ml_agg[:, 1::2].contiguous(), shared
+
+    @staticmethod
+    def backward(ctx, gmu, glv, _gshared):
+        ml, shared = ctx.saved_tensors
+        B, D = ml.shape[0], ml.shape[1] // 2
+        zero = lambda g: torch.zeros(B, D, dtype=torch.float32, device=ml.device) if g is None else g.float()
+        dml = _interleave(zero(gmu), zero(glv))
+        _PairAggregate(ctx.kind, D, None, shared, None, _stream()).bwd(ml, dml, B)
+        return dml[:, 0::2], dml[:, 1::2], None
+
+
+def adaptive_group_posterior(mu, logvar, aggregation="gvae"):
+    """The adaptive group posterior of Ada-GVAE ("gvae") / Ada-ML-VAE ("mlvae") (Locatello et al. 2020) of a batch of pairs:
+    mu, logvar fp32 [2 P, D] device tensors, rows i and P + i a pair -> (mu~, logvar~, shared): the aggregated posterior
+    parameters [2 P, D] (a dimension that the pair shares -- delta < tau, include/dvae_weak_hip.h -- holds the same bits in both
+    rows, every other element is its input) and the mask, int64 [P] with bit d set where dimension d is shared.  Differentiable
+    with respect to mu and logvar through the library's backward launch; the mask is a constant.  For models that are not the
+    engine's: WeakVaeLoss.fused_step runs the same two launches inside the native step."""
+    if aggregation not in _weaklib.KINDS:
+        raise ValueError("aggregation must be one of {}, got {!r}".format(sorted(_weaklib.KINDS), aggregation))
+    if mu.dim() != 2 or mu.shape != logvar.shape:
+        raise ValueError("mu and logvar must be [2 P, D] tensors of one shape, got {} and {}".format(tuple(mu.shape),
+                                                                                                     tuple(logvar.shape)))
+    _check_pairs(mu.shape[0], mu.shape[1])
+    return _AdaptiveGroupFn.apply(mu, logvar, _weaklib.KINDS[aggregation])
+
+
+def popcount64(words):
+    """Set bits of each element of an int64 tensor (the pair masks), on the host -> int64 [n]."""
+    w = words.detach().cpu().contiguous().view(-1)
+    n = torch.zeros_like(w)
+    for k in range(64):
+        n += (w >> k) & 1
+    return n
+
+
 def u8_to_f32(x):
     """ToTensor's arithmetic on a uint8 device tensor: float(v) / 255 (dvae_u8_to_f32)."""
     x = x.contiguous()
@@ -845,6 +932,109 @@ class InfoVaeLoss(_SingleOptimizerLoss):
             storer['mmd_loss'].append(mmd_loss.item())
             storer['loss'].append(loss.item())
         return loss
+
+
+class WeakVaeLoss(_SingleOptimizerLoss):
+    """Ada-GVAE / Ada-ML-VAE (Locatello et al. 2020, "Weakly-Supervised Disentanglement Without Compromises";
+    disentanglement_lib's weak_vae.py -- the reference has no counterpart) on a batch of image PAIRS: 2 P rows, rows i and P + i
+    a pair that shares all but a few factors of variation (data.PairedFactorLoader, or any batch whose halves pair up).
+
+        loss = rec + anneal * beta * KL(q~ || N(0, I)),        both terms means over the 2 P rows
+
+    q~ is the adaptive group posterior (include/dvae_weak_hip.h): per pair and dimension delta = 2 KL(q_a || q_b), the
+    threshold tau half way between the pair's largest and smallest delta, and on every dimension with delta < tau both rows
+    receive one posterior -- the mean of means and variances (aggregation "gvae") or the product of experts ("mlvae").  The mask
+    is a constant for the gradient.  z = m~ + exp(lv~ / 2) eps with eps [2 P, D] under the noise contract of the other losses
+    (one normal_, or injected); in evaluation z = m~.  After a step the engine's buf.mu / buf.logvar hold q~.
+
+    The operator sits between mu_logvar_gen and the reparameterisation, inside what the fused FC chain does in one launch:
+    the step runs the FC core one launch per layer around it (the path of latent dimensions above 16) and the 4x4 conv ends as
+    launches of their own, for every latent dimension.  `shared_dims` logs the mean number of shared dimensions per pair.
+    Data-parallel steps are not built (fused_step raises under a communicator of more than one rank)."""
+    KIND = _lib.LOSS_BETAH
+    STORED = (('recon_loss', _lib.S_REC), ('kl_loss', _lib.S_KL), ('shared_dims', None), ('loss', _lib.S_LOSS))
+
+    def __init__(self, aggregation="gvae", beta=1, **kwargs):
+        super().__init__(**kwargs)
+        if aggregation not in _weaklib.KINDS:
+            raise ValueError("aggregation must be one of {}, got {!r}".format(sorted(_weaklib.KINDS), aggregation))
+        self.aggregation = aggregation
+        self.beta = beta
+        self._weak = {}
+        self._shared = None          # the mask of the last step: what `shared_dims` is counted from
+
+    _coefs = BetaHLoss._coefs
+
+    def _begin_step(self, model, data):
+        """The step's policy without the fused 4x4 conv ends: there is no chain launch to carry them."""
+        pol = super()._begin_step(model, data)._replace(fuse_ends=False)
+        model.engine.begin_step(pol)
+        return pol
+
+    def _pair_bufs(self, device, P, D):
+        """(ml_agg fp32 [2 P, 2 D], shared int64 [P], delta fp32 [P, D]) of the two launches, allocated once per shape."""
+        t = self._weak.get((device, P, D))
+        if t is None:
+            _lib.note_alloc()
+            t = self._weak[(device, P, D)] = (torch.empty(2 * P, 2 * D, dtype=torch.float32, device=device),
+                                              torch.empty(P, dtype=torch.int64, device=device),
+                                              torch.empty(P, D, dtype=torch.float32, device=device))
+        return t
+
+    def _replay_key(self, model, data, injected, pol):
+        return super()._replay_key(model, data, injected, pol) + (self.aggregation,)
+
+    def _store(self, storer, sc, D, keys=None):
+        if storer is None:
+            return
+        vals = sc.scal.tolist()
+        shared = popcount64(self._shared).double().mean().item()     # one more small copy, on logging steps only
+        for key, slot in self.STORED:
+            if key == 'kl_loss':
+                self._store_kl(storer, vals, D)
+            else:
+                storer[key].append(shared if key == 'shared_dims' else vals[slot])
+
+    def fused_step(self, data, model, optimizer, storer, eps=None):
+        _check_pairs(data.shape[0], model.latent_dim)
+        if self._world()[0] > 1:
+            raise NotImplementedError(
+                "Ada-GVAE / Ada-ML-VAE under data parallelism is not built: both members of a pair have to lie on one rank, "
+                "which the sharding of a batch by rows does not give")
+        # here, not in _device_step: a replayed step does not run that, and `shared_dims` is counted from THIS step's mask
+        self._shared = self._pair_bufs(data.device, data.shape[0] // 2, model.latent_dim)[1]
+        return super().fused_step(data, model, optimizer, storer, eps=eps)
+
+    def _device_step(self, data, model, sc, eps, is_train):
+        """Forward + loss + backward as one stream of launches: the FC core layer by layer around the pair operator."""
+        eng = model.engine
+        B, D = data.shape[0], model.latent_dim
+        buf = eng.buffers(B)
+        s = _stream()
+        data = eng.input(data, buf)
+        if is_train and eps is None:
+            eps = sc.latent("eps", B, D)
+            record_py(eps.normal_)
+        if not is_train:
+            eps = None
+        op = _PairAggregate(_weaklib.KINDS[self.aggregation], D, *self._pair_bufs(data.device, B // 2, D), s)
+        eng.encode_convs(data, buf, chain=False)
+        # kl_dim receives the D final values (coef is passed): nothing is left for the epilogue to finish
+        eng._fc_layers_fwd(buf, eps, sc.kl_dim, B, B, B, sc.coef, latent_op=op)
+        eng.decode_convs(buf, B, fuse_loss=(data, self._rec_code(), sc.coef, sc.partials), ends=False)
+        self._finish_loss(sc, 0, D, None, B, None, B, s)
+        if not is_train:
+            return
+
+        def fc_chain():
+            eng._fc_layers_bwd(buf, eps, None, None, None, None, sc.scal, sc.coef, B, latent_op=op)
+        self._backward(eng, model, data, buf, B, fc_chain)
+
+    def __call__(self, data, recon_data, latent_dist, is_train, storer, **kwargs):
+        raise NotImplementedError(
+            "WeakVaeLoss has no loss(data, recon, latent_dist, ...) form: the pairs are aggregated BEFORE z is sampled, so a "
+            "reconstruction made from the un-aggregated posterior cannot carry the loss.  Train with fused_step (the native "
+            "Trainer does), or build the loss of a model of your own on adaptive_group_posterior(mu, logvar, aggregation)")
 
 
 class BetaBLoss(_SingleOptimizerLoss):
