@@ -14,10 +14,21 @@ bool use_generic_only() {
 
 static int check_layout(int l) { return l == DVAE_NCHW || l == DVAE_NHWC; }
 
+// The alignment contract of the conv family (include/dvae_hip.h): any 4-byte-aligned fp32 pointer is accepted.  The 32 <-> 32
+// channel kernels move operands, masks and results in 16-byte accesses and LDS-DMA, so they take a call only when EVERY pointer
+// of it is 16-byte aligned (NULL counts as aligned).  The thin-end kernels: k_down_thin's accesses are all 4 bytes wide (its
+// wave-specialised form tests its own pointers, conv_thin_ws.hip); launch_up_thin and the thin weight-gradient branch test the
+// pointers their kernels vectorise.  Every other call goes to the shape-generic kernels of conv_generic.hip, whose accesses are
+// 4 bytes wide (their 16-byte branches, k_*_thin_px, test the pointers they vectorise).
+static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr,
+                      const void* e = nullptr) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e) & 15) == 0;
+}
+
 // big[N,Cb,2Hs,2Ws] -> small[N,Cs,Hs,Ws]
 static int run_down(const ConvArgs& a, hipStream_t s) {
   if (!use_generic_only()) {
-    int r = launch_down_mfma32(a, s);
+    int r = aligned16(a.big, a.w, a.bias, a.mask, a.out) ? launch_down_mfma32(a, s) : 1;
     if (r <= 0) return r;
     r = launch_down_thin(a, s);
     if (r <= 0) return r;
@@ -28,12 +39,14 @@ static int run_up(const ConvArgs& a, hipStream_t s) {
   if (!use_generic_only()) {
     int r = 1;
     static const bool no_ws = env_off("DVAE_UP_WS");        // debug builds: DVAE_UP_WS=0 -> k_up32 for every geometry (A/B)
-    if (!no_ws) {
-      r = launch_up_mfma32_ws(a, s);
+    if (aligned16(a.small, a.w, a.bias, a.mask, a.out)) {
+      if (!no_ws) {
+        r = launch_up_mfma32_ws(a, s);
+        if (r <= 0) return r;
+      }
+      r = launch_up_mfma32(a, s);
       if (r <= 0) return r;
     }
-    r = launch_up_mfma32(a, s);
-    if (r <= 0) return r;
     r = launch_up_thin(a, s);
     if (r <= 0) return r;
   }
@@ -41,14 +54,17 @@ static int run_up(const ConvArgs& a, hipStream_t s) {
 }
 static int run_wgrad(const float* big, int big_layout, const float* small, int small_layout, float* dw, float* db,
                      int bias_from_big, int N, int Cb, int Cs, int Hs, int Ws, float* ws, hipStream_t s) {
+  const bool tuned = !use_generic_only() && ws != nullptr;
+  const bool al32 = aligned16(big, small, dw, db, ws);      // k_wgrad32 / k_wgrad32ws and their reduction
   // the small side of the 4x4 end of the conv stack may be NCHW (= the FC stack's (c,h,w) order)
-  if (!use_generic_only() && ws != nullptr && Hs == Ws && Cs == 32 && Cb == 32 && big_layout == DVAE_NHWC && Hs == 4 &&
+  if (tuned && al32 && Hs == Ws && Cs == 32 && Cb == 32 && big_layout == DVAE_NHWC && Hs == 4 &&
       small_layout == DVAE_NCHW)
     return launch_wgrad_mfma32(big, small, dw, db, bias_from_big, N, Hs, ws, s, 1);
-  if (!use_generic_only() && ws != nullptr && Hs == Ws && Cs == 32 && small_layout == DVAE_NHWC) {
-    if (Cb == 32 && big_layout == DVAE_NHWC && (Hs == 4 || Hs == 8 || Hs == 16))
+  if (tuned && Hs == Ws && Cs == 32 && small_layout == DVAE_NHWC) {
+    if (al32 && Cb == 32 && big_layout == DVAE_NHWC && (Hs == 4 || Hs == 8 || Hs == 16))
       return launch_wgrad_mfma32(big, small, dw, db, bias_from_big, N, Hs, ws, s, 0);
-    if ((Cb == 1 || Cb == 3) && Hs == 32 && big_layout == DVAE_NCHW)
+    // k_wgrad_thin: 16-byte loads of the 32-channel side, 16-byte reads of the partial sums; the image, dw and db by 4 bytes
+    if ((Cb == 1 || Cb == 3) && Hs == 32 && big_layout == DVAE_NCHW && aligned16(small, ws))
       return launch_wgrad_thin(big, small, dw, db, bias_from_big, N, Cb, Hs, ws, s);
   }
   return launch_wgrad_generic(big, big_layout, small, small_layout, dw, db, bias_from_big, N, Cb, Cs, Hs, Ws, ws,
@@ -74,7 +90,7 @@ int dvae_conv4s2_fwd(const float* x, int x_layout, const float* w, const float* 
 
 int dvae_conv4s2_dgrad(const float* dy, int dy_layout, const float* w, const float* x_act, float* dx, int dx_layout,
                        int N, int Cin, int H, int W, int Cout, void* stream) {
-  DVAE_CHECK_ARG(dy && w && dx && N > 0 && Cin > 0 && Cout > 0 && (H % 2 == 0) && (W % 2 == 0));
+  DVAE_CHECK_ARG(dy && w && dx && N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && (H % 2 == 0) && (W % 2 == 0));
   DVAE_CHECK_ARG(check_layout(dy_layout) && check_layout(dx_layout));
   // conv weight w[Cout,Cin,4,4] = w[cs][cb]: small = dy (Cout channels), big = dx (Cin channels)
   ConvArgs a{nullptr, 0, dy, dy_layout, w, nullptr, x_act, dx, dx_layout, N, Cin, Cout, H / 2, W / 2, DVAE_ACT_NONE};
@@ -83,7 +99,8 @@ int dvae_conv4s2_dgrad(const float* dy, int dy_layout, const float* w, const flo
 
 int dvae_conv4s2_wgrad(const float* x, int x_layout, const float* dy, int dy_layout, float* dw, float* db, int N,
                        int Cin, int H, int W, int Cout, float* ws, void* stream) {
-  DVAE_CHECK_ARG(x && dy && dw && N > 0 && (H % 2 == 0) && (W % 2 == 0));
+  DVAE_CHECK_ARG(x && dy && dw && N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && (H % 2 == 0) && (W % 2 == 0));
+  DVAE_CHECK_ARG(check_layout(x_layout) && check_layout(dy_layout));
   const int rc = run_wgrad(x, x_layout, dy, dy_layout, dw, db, /*bias_from_big=*/0, N, Cin, Cout, H / 2, W / 2, ws,
                    (hipStream_t)stream);
   return rc;
@@ -108,7 +125,8 @@ int dvae_convT4s2_dgrad(const float* dy, int dy_layout, const float* w, const fl
 
 int dvae_convT4s2_wgrad(const float* x, int x_layout, const float* dy, int dy_layout, float* dw, float* db, int N,
                         int Cin, int H, int W, int Cout, float* ws, void* stream) {
-  DVAE_CHECK_ARG(x && dy && dw && N > 0);
+  DVAE_CHECK_ARG(x && dy && dw && N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0);
+  DVAE_CHECK_ARG(check_layout(x_layout) && check_layout(dy_layout));
   const int rc = run_wgrad(dy, dy_layout, x, x_layout, dw, db, /*bias_from_big=*/1, N, Cout, Cin, H, W, ws,
                    (hipStream_t)stream);
   return rc;
@@ -120,9 +138,11 @@ int dvae_convT4s2_sigmoid_recon_fwd(const float* x, int x_layout, const float* w
   DVAE_CHECK_ARG(x && w && target && recon && g && coef && partials && N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0);
   DVAE_CHECK_ARG(check_layout(x_layout));
   DVAE_CHECK_ARG(dist == DVAE_REC_BERNOULLI || dist == DVAE_REC_GAUSSIAN || dist == DVAE_REC_LAPLACE);
+  // the likelihood pass of the two-pass form (k_recon_loss) and the fused kernel both move these three in 16-byte accesses
+  DVAE_CHECK_ARG(aligned16(target, recon, g));
   ConvArgs a{nullptr, 0, x, x_layout, w, b, nullptr, recon, DVAE_NCHW, N, Cout, Cin, H, W, DVAE_ACT_SIGMOID};
   static const bool two_pass = env_on("DVAE_RECON_TWO_PASS");   // A/B switch (debug builds)
-  if (!use_generic_only() && !two_pass) {
+  if (!use_generic_only() && !two_pass && aligned16(x, w, b)) {
     int r = launch_up_thin_recon(a, target, g, dist, coef, partials, (hipStream_t)stream);
     if (r <= 0) return r;
   }

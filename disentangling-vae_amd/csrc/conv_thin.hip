@@ -691,9 +691,9 @@ int launch_down_thin(const ConvArgs& a, hipStream_t s) {
 }
 
 int launch_up_thin(const ConvArgs& a, hipStream_t s) {
-  if (!thin_applicable(a) || a.small_layout != DVAE_NHWC || a.out_layout != DVAE_NCHW || a.mask) return 1;
-  const int n_units = a.N * 8;
-  const int grid = n_units;          // one unit per workgroup: the hardware dispatcher balances the load
+  if (!thin_applicable(a) || a.small_layout != DVAE_NHWC || a.out_layout != DVAE_NCHW || a.mask || a.act == DVAE_ACT_LEAKY02) return 1;
+  if ((((uintptr_t)a.small | (uintptr_t)a.w) & 15) != 0 || ((uintptr_t)a.out & 7) != 0) return 1;   // 16-byte tile loads, 8-byte stores
+  const int grid = a.N * 8, n_units = grid;   // one unit per workgroup: the hardware dispatcher balances the load
   if (a.Cb == 1) hipLaunchKernelGGL((k_up_thin<1, false>), dim3(grid), dim3(128), 0, s, a.small, a.w, a.bias, a.out, a.N, a.act, n_units, (const float*)nullptr, (float*)nullptr, 0, (const float*)nullptr, (float*)nullptr);
   else hipLaunchKernelGGL((k_up_thin<3, false>), dim3(grid), dim3(128), 0, s, a.small, a.w, a.bias, a.out, a.N, a.act, n_units, (const float*)nullptr, (float*)nullptr, 0, (const float*)nullptr, (float*)nullptr);
   DVAE_CHECK_LAUNCH();

@@ -626,9 +626,9 @@ int launch_linear_fwd(const float* x, const float* w, const float* b, float* y, 
     DVAE_CHECK_LAUNCH();
     return 0;
   }
-  if (use_small(M, N, K, K % 4 == 0)) {
-    // A = x (k contiguous), B(k,j) = w[j*K + k] (k contiguous)
-    if (K % 4 == 0)
+  const bool vec = K % 4 == 0 && (((uintptr_t)x | (uintptr_t)w) & 15) == 0;   // 16-byte loads along the rows of x and w
+  if (use_small(M, N, K, vec)) {
+    if (vec)
       hipLaunchKernelGGL((k_gemm32<true, true>), grid32(M, N), dim3(256), 0, s, x, (long)K, 1L, w, 1L, (long)K, y,
                          (long)N, M, N, K, b, act, (const float*)nullptr, 0, (float*)nullptr);
     else
@@ -667,7 +667,7 @@ int launch_linear_dgrad(const float* dy, const float* w, const float* x_act, int
   }
   if (use_small(M, K, N, false)) {
     // A = dy (contraction index n contiguous), B(k=n, j) = w[n*K + j] (j contiguous -> lanes)
-    if (N % 4 == 0)
+    if (N % 4 == 0 && ((uintptr_t)dy & 15) == 0)
       hipLaunchKernelGGL((k_gemm32<true, false>), grid32(M, K), dim3(256), 0, s, dy, (long)N, 1L, w, (long)K, 1L, dx,
                          (long)K, M, K, N, (const float*)nullptr, 0, x_act, x_act ? act : 0, (float*)nullptr);
     else

@@ -75,8 +75,19 @@ enum {
 int dvae_version(void);
 const char* dvae_last_error(void);
 
-/* ---- Conv2d(k=4,s=2,p=1): encoders.py:54-60,73-77 (nn.Conv2d + torch.relu) -------------
- * x[N,Cin,H,W] -> y[N,Cout,H/2,W/2], w[Cout,Cin,4,4], y = act(conv(x,w)+b).               */
+/* ---- Alignment contract of the conv (dvae_conv4s2_*, dvae_convT4s2_*) and linear (dvae_linear_*) entry points --------
+ * Every fp32 pointer needs 4-byte alignment only, and any N, channel count, even H / W (any H / W for the transposed
+ * family), layout pair and optional-pointer combination documented below is accepted.  The tuned gfx950 kernels are taken
+ * only when the pointers THEY read or write with 8- / 16-byte accesses or LDS-DMA are 16-byte aligned (NULL counts as
+ * aligned; rows must also be a multiple of 16 bytes where a kernel vectorises along them); any other call falls through to
+ * a kernel whose accesses to that pointer are 4 bytes wide (the shape-generic conv kernels, k_gemm / the scalar-staging
+ * forms of k_fc32 / k_gdma's scalar epilogue).  Results agree to rounding, not bit for bit, between the two.  One exception
+ * is refused instead: target, recon and g of dvae_convT4s2_sigmoid_recon_fwd must be 16-byte aligned.
+ *
+ * ---- Conv2d(k=4,s=2,p=1): encoders.py:54-60,73-77 (nn.Conv2d + torch.relu) -------------
+ * x[N,Cin,H,W] -> y[N,Cout,H/2,W/2], w[Cout,Cin,4,4], y = act(conv(x,w)+b); b may be NULL; act: any DVAE_ACT_*.
+ * Pointers: 4-byte aligned (the contract above).  N, Cin, Cout, H, W > 0, H and W even, both layouts NCHW or NHWC --
+ * the same holds for _dgrad and _wgrad, which refuse anything else (DVAE_CHECK_ARG) as the forward does.          */
 int dvae_conv4s2_fwd(const float* x, int x_layout, const float* w, const float* b, float* y,
                      int y_layout, int N, int Cin, int H, int W, int Cout, int act, void* stream);
 /* autograd of the above (training.py:157 loss.backward): dy is the gradient w.r.t. the
@@ -85,12 +96,15 @@ int dvae_conv4s2_fwd(const float* x, int x_layout, const float* w, const float* 
 int dvae_conv4s2_dgrad(const float* dy, int dy_layout, const float* w, const float* x_act, float* dx,
                        int dx_layout, int N, int Cin, int H, int W, int Cout, void* stream);
 /* dw[Cout,Cin,4,4] = sum x (*) dy ; db[Cout] = sum dy (db may be NULL).
- * ws: workspace of at least dvae_conv_wgrad_ws_floats() floats.                             */
+ * ws: workspace of at least dvae_conv_wgrad_ws_floats() floats, or NULL (then, or with a pointer off the 16-byte
+ * grid, the shape-generic weight-gradient kernels run).                                       */
 int dvae_conv4s2_wgrad(const float* x, int x_layout, const float* dy, int dy_layout, float* dw,
                        float* db, int N, int Cin, int H, int W, int Cout, float* ws, void* stream);
 
 /* ---- ConvTranspose2d(k=4,s=2,p=1): decoders.py:57-65,77-82 ------------------------------
- * x[N,Cin,H,W] -> y[N,Cout,2H,2W], w[Cin,Cout,4,4]; act in {none, relu, sigmoid}.          */
+ * x[N,Cin,H,W] -> y[N,Cout,2H,2W], w[Cin,Cout,4,4]; act: any DVAE_ACT_* (leaky 0.2 runs on the shape-generic
+ * kernels at every geometry); b may be NULL.  Pointers: 4-byte aligned (the alignment contract above); _wgrad
+ * refuses empty shapes and unknown layout codes as the forward does; ws as for dvae_conv4s2_wgrad.               */
 int dvae_convT4s2_fwd(const float* x, int x_layout, const float* w, const float* b, float* y,
                       int y_layout, int N, int Cin, int H, int W, int Cout, int act, void* stream);
 /* dx[N,Cin,H,W] from dy[N,Cout,2H,2W] (pre-activation grad), fused ReLU mask like above.   */
@@ -198,7 +212,9 @@ int dvae_convT4s2_sigmoid_recon_fwd_u8(const float* x /* NHWC */, const float* w
 int dvae_relayout(const float* src, int src_layout, float* dst, int N, int C, int H, int W, void* stream);
 
 /* ---- nn.Linear: encoders.py:63-67,81-86; decoders.py:53-55,71-73; discriminator.py:51-68 --
- * y[M,N] = act(x[M,K] w[N,K]^T + b[N]);  act in {none, relu, leaky 0.2}.
+ * y[M,N] = act(x[M,K] w[N,K]^T + b[N]);  act in {none, relu, leaky 0.2}; b may be NULL.
+ * Pointers (all three entry points): 4-byte aligned, any M, K, N > 0 (the alignment contract above: 16-byte loads
+ * only from 16-byte-aligned bases with K resp. N a multiple of 4, 4-byte accesses otherwise).
  * ws (all three, may be NULL): the dvae_conv_wgrad_ws_floats() workspace; enables the
  * split-contraction schedule for layers with few output tiles (fixed-order, deterministic). */
 int dvae_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int K, int N,
@@ -327,7 +343,9 @@ int dvae_sigmoid_bwd(const float* grad_y, const float* y, float* out, long n, vo
 /* Final decoder layer fused with the likelihood: recon = sigmoid(convT(x,w)+b) (decoders.py:82),
  * partials[DVAE_REC_NPART] = per-workgroup sums of the loss vs `target`, g = coef[INV_B] *
  * dLoss/d(pre-sigmoid logit).  x[N,Cin,H,W]; target, recon, g: [N,Cout,2H,2W] NCHW.  One pass over
- * the reconstruction instead of three (convT3 store, loss read, gradient write).              */
+ * the reconstruction instead of three (convT3 store, loss read, gradient write) at Cout in {1, 3}, Cin = 32 NHWC,
+ * 32x32 -> 64x64 with x, w, b 16-byte aligned; every other shape, layout or alignment of x, w, b: two passes, same
+ * results to rounding.  target, recon and g must be 16-byte aligned (refused otherwise); b may be NULL.        */
 int dvae_convT4s2_sigmoid_recon_fwd(const float* x, int x_layout, const float* w, const float* b,
                                     const float* target, float* recon, float* g, int dist,
                                     const float* coef, float* partials, int N, int Cin, int H, int W,

@@ -81,17 +81,17 @@ VARIANTS = [
     _v("k_down32<4, false>", "dvae_conv4s2_fwd, dvae_conv32_down", "Hs == 4, no mask (output NHWC or NCHW)", "conv_mfma.hip:396", V + "test_conv32_at_the_persistent_grid_switch[1024-4]"),
     _v("k_down32<4, true>", "dvae_convT4s2_dgrad, dvae_conv32_down", "Hs == 4, mask", "conv_mfma.hip:395", V + "test_conv32_at_the_persistent_grid_switch[1025-4]"),
     _v("k_wgrad32<16>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "Hs == 16 with the small side NCHW or DVAE_WGRAD_WS=0", "conv_mfma.hip:433", None,
-       "run_wgrad (capi.hip:45) passes small_nchw = 1 for Hs == 4 only, and " + _DEBUG_ONLY % "DVAE_WGRAD_WS"),
+       "run_wgrad (capi.hip:60) passes small_nchw = 1 for Hs == 4 only, and " + _DEBUG_ONLY % "DVAE_WGRAD_WS"),
     _v("k_wgrad32<8>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "Hs == 8 with the small side NCHW or DVAE_WGRAD_WS=0", "conv_mfma.hip:433", None,
-       "run_wgrad (capi.hip:45) passes small_nchw = 1 for Hs == 4 only, and " + _DEBUG_ONLY % "DVAE_WGRAD_WS"),
+       "run_wgrad (capi.hip:60) passes small_nchw = 1 for Hs == 4 only, and " + _DEBUG_ONLY % "DVAE_WGRAD_WS"),
     _v("k_wgrad32<4>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "Hs == 4 (small side NHWC or NCHW)", "conv_mfma.hip:433", V + "test_wgrad32_at_the_reduction_form_switch[767-4-True-False]"),
     _v("k_wgrad32_reduce<false>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "32 <-> 32 channels, N < WGR_LEAN_MIN_IMAGES = 768", "conv_mfma.hip:375", V + "test_wgrad32_at_the_reduction_form_switch[767-8-False-False]"),
     _v("k_wgrad32_reduce<true>", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad", "32 <-> 32 channels, N >= 768", "conv_mfma.hip:373", V + "test_wgrad32_at_the_reduction_form_switch[768-8-False-False]"),
     # ---- conv_thin.hip (C = 1 / 3 <-> 32 channels, 64x64 <-> 32x32)
-    _v("k_up_thin<1, false, float>", "dvae_convT4s2_fwd", "Cb == 1, NHWC -> NCHW, no mask", "conv_thin.hip:697", K + "test_convT_fwd_dgrad_wgrad[3-32-1-0-3-False]"),
+    _v("k_up_thin<1, false, float>", "dvae_convT4s2_fwd", "Cb == 1, NHWC -> NCHW, no mask, act not leaky, aligned", "conv_thin.hip:697", K + "test_convT_fwd_dgrad_wgrad[3-32-1-0-3-False]"),
     _v("k_up_thin<1, true, float>", "dvae_convT4s2_sigmoid_recon_fwd", "Cb == 1", "conv_thin.hip:709", K + "test_convT_sigmoid_recon_fused[3-1-32-gaussian-False]"),
     _v("k_up_thin<1, true, unsigned char>", "dvae_convT4s2_sigmoid_recon_fwd_u8", "Cb == 1", "conv_thin.hip:734", U8 + "test_u8_kernels_equal_fp32_kernels_bitwise[3-1]"),
-    _v("k_up_thin<3, false, float>", "dvae_convT4s2_fwd", "Cb == 3, NHWC -> NCHW, no mask", "conv_thin.hip:698", K + "test_convT_fwd_dgrad_wgrad[5-32-3-0-3-False]"),
+    _v("k_up_thin<3, false, float>", "dvae_convT4s2_fwd", "Cb == 3, NHWC -> NCHW, no mask, act not leaky, aligned", "conv_thin.hip:698", K + "test_convT_fwd_dgrad_wgrad[5-32-3-0-3-False]"),
     _v("k_up_thin<3, true, float>", "dvae_convT4s2_sigmoid_recon_fwd", "Cb == 3", "conv_thin.hip:710", K + "test_convT_sigmoid_recon_fused[5-3-32-bernoulli-False]"),
     _v("k_up_thin<3, true, unsigned char>", "dvae_convT4s2_sigmoid_recon_fwd_u8", "Cb == 3", "conv_thin.hip:735", U8 + "test_u8_kernels_equal_fp32_kernels_bitwise[5-3]"),
     _v("k_down_thin<1, 0, float>", "dvae_conv4s2_fwd", "Cb == 1, N < 192, no mask", "conv_thin.hip:684", V + "test_thin_ends_at_the_wave_specialised_switch[191-1]"),
@@ -454,3 +454,256 @@ TRIP_CLASSES = [
         ("u5", 240, _WWS + "[240]"), ("u6", 288, _WWS + "[288]"), ("m2", 129, _CAP + "[129-16]")]),
 ]
 
+
+
+# ---- PREDICATES: the non-numeric terms of the conv / linear launcher conditions ------------------------------------------------
+# A conv case is the geometry both directions of the k4/s2/p1 family run at: big[N,Cb,H,W] <-> small[N,Cs,H/2,W/2], the layouts
+# of the two sides and the forward activation; `null` names a pointer role passed as NULL (b, db, mask, ws), `off` a role and a
+# byte offset into a larger 16-byte-aligned buffer (roles: big, small, w, b, mask, dw, db, ws).  A linear case is (M, K, N), the
+# forward activation and `off` (roles: x, w, b, y, dy, x_act, dx, dw, db).  tests/test_gpu_dispatch_predicates.py runs every
+# entry point of the family at each case; the id functions below spell the pytest ids.
+CONV_BASE = dict(N=3, Cb=32, Cs=32, H=32, W=32, bl="NHWC", sl="NHWC", act="relu", null=None, off=None)
+THIN_BASE = dict(N=3, Cb=3, Cs=32, H=64, W=64, bl="NCHW", sl="NHWC", act="relu", null=None, off=None)
+LIN_BASE = dict(M=8, K=512, N=256, act="relu", off=None)
+
+
+def conv_case(_base=None, **kw):
+    d = dict(_base or CONV_BASE)
+    assert set(kw) <= set(d), kw
+    d.update(kw)
+    return d
+
+
+def thin_case(**kw):
+    return conv_case(THIN_BASE, **kw)
+
+
+def lin_case(**kw):
+    d = dict(LIN_BASE)
+    assert set(kw) <= set(d), kw
+    d.update(kw)
+    return d
+
+
+def conv_id(d):
+    s = "N%d-Cb%d-Cs%d-%dx%d-b%s-s%s-%s" % (d["N"], d["Cb"], d["Cs"], d["H"], d["W"], d["bl"], d["sl"], d["act"])
+    if d["null"]:
+        s += "-null_" + d["null"]
+    if d["off"]:
+        s += "-%s_plus%d" % d["off"]
+    return s
+
+
+def lin_id(d):
+    s = "M%d-K%d-N%d-%s" % (d["M"], d["K"], d["N"], d["act"])
+    if d["off"]:
+        s += "-%s_plus%d" % d["off"]
+    return s
+
+
+Predicate = namedtuple("Predicate", "launcher term where family entry base arg neighbour kernel base_test test reason")
+
+P = "tests/test_gpu_dispatch_predicates.py::"
+_FAMILY_TEST = {"conv": ("test_conv_family", conv_id), "fused": ("test_fused_likelihood", conv_id), "linear": ("test_linear_family", lin_id)}
+
+
+def _p(launcher, where, term, family, entry, base, arg, value, kernel, base_test=None, test=None):
+    """One term of a launcher condition: `base` satisfies the whole conjunction the term stands in, the neighbour is `base`
+    with the argument(s) `arg` set to `value` -- the term negated alone -- and `kernel` is what then takes the call of `entry`
+    (read from the launchers, as VARIANTS is).  arg "H,W" is the one argument `image size` of a square image."""
+    keys = arg.split(",")
+    neighbour = dict(base, **dict(zip(keys, value if len(keys) > 1 else (value,))))
+    if family in _FAMILY_TEST:
+        fn, ident = _FAMILY_TEST[family]
+        base_test, test = P + "%s[%s]" % (fn, ident(base)), P + "%s[%s]" % (fn, ident(neighbour))
+    return Predicate(launcher, term, where, family, entry, base, arg, neighbour, kernel, base_test, test, None)
+
+
+def _unreachable(launcher, where, term, reason):
+    return Predicate(launcher, term, where, None, None, None, None, None, None, None, None, reason)
+
+
+_C, _T, _T1 = conv_case(), thin_case(), thin_case(Cb=1)
+_C16, _C8 = conv_case(H=16, W=16), conv_case(H=8, W=8)               # Hs = 8, Hs = 4
+_C4N = conv_case(H=8, W=8, sl="NCHW")                                # the 4x4 end with its NCHW small side
+_CSIG, _TSIG = conv_case(act="sigmoid"), thin_case(act="sigmoid")    # declined for the activation alone
+_PX, _PX1 = thin_case(H=32, W=32), thin_case(Cb=1, H=32, W=32)       # the thin ends at the 32x32 image: k_*_thin_px
+_DN, _UP, _WG = "dvae_conv4s2_fwd, dvae_convT4s2_dgrad", "dvae_convT4s2_fwd, dvae_conv4s2_dgrad", "dvae_conv4s2_wgrad, dvae_convT4s2_wgrad"
+_GD, _GU, _GW = "k_down_generic", "k_up_generic", "k_wgrad_generic + k_chansum"
+_L, _LD, _LN, _LS = lin_case(), lin_case(M=64, K=1000, N=1000), lin_case(M=100, K=1000, N=2), lin_case(K=1000, N=36)
+_L12 = lin_case(K=12)
+_FW, _DG, _WGL = "dvae_linear_fwd", "dvae_linear_dgrad", "dvae_linear_wgrad"
+_GRP = dict(K=512, N=256, x_off=0, dy_off=0)
+_GRP_BASE, _GRP_TEST = K + "test_linear_wgrad_grouped[64]", P + "test_linear_wgrad_grouped_flag_bits[8]"
+_REFUSED = P + "test_fused_likelihood_refuses_an_unaligned_target_recon_or_gradient[4-target]"
+_CALLER = "%s tests the same term before the call (no other caller in the shipped library), so it is always true here"
+
+PREDICATES = [
+    # ---- capi.hip: run_down, run_up, run_wgrad, dvae_convT4s2_sigmoid_recon_fwd
+    _p("run_down", "capi.hip:31", "aligned16(a.big, a.w, a.bias, a.mask, a.out)", "conv", _DN, _C, "off", ("big", 4), _GD),
+    _p("run_up", "capi.hip:42", "aligned16(a.small, a.w, a.bias, a.mask, a.out)", "conv", _UP, _C, "off", ("small", 4), _GU),
+    _p("run_wgrad", "capi.hip:57", "ws != nullptr", "conv", _WG, _C, "null", "ws", _GW),
+    _p("run_wgrad", "capi.hip:58", "aligned16(big, small, dw, db, ws)", "conv", _WG, _C, "off", ("dw", 4), _GW),
+    _p("run_wgrad (4x4 end, NCHW)", "capi.hip:60", "Hs == Ws", "conv", _WG, _C4N, "W", 4, _GW),
+    _p("run_wgrad (4x4 end, NCHW)", "capi.hip:60", "Cs == 32", "conv", _WG, _C4N, "Cs", 16, _GW),
+    _p("run_wgrad (4x4 end, NCHW)", "capi.hip:60", "Cb == 32", "conv", _WG, _C4N, "Cb", 16, _GW),
+    _p("run_wgrad (4x4 end, NCHW)", "capi.hip:60", "big_layout == DVAE_NHWC", "conv", _WG, _C4N, "bl", "NCHW", _GW),
+    _p("run_wgrad (4x4 end, NCHW)", "capi.hip:60", "Hs == 4", "conv", _WG, _C4N, "H,W", (16, 16), _GW),
+    _p("run_wgrad (4x4 end, NCHW)", "capi.hip:61", "small_layout == DVAE_NCHW", "conv", _WG, _C4N, "sl", "NHWC", "k_wgrad32<4> (capi.hip:64)"),
+    _p("run_wgrad", "capi.hip:63", "Hs == Ws", "conv", _WG, _C, "W", 16, _GW),
+    _p("run_wgrad", "capi.hip:63", "Cs == 32", "conv", _WG, _C, "Cs", 16, _GW),
+    _p("run_wgrad", "capi.hip:63", "small_layout == DVAE_NHWC", "conv", _WG, _C, "sl", "NCHW", _GW),
+    _p("run_wgrad", "capi.hip:64", "Cb == 32", "conv", _WG, _C, "Cb", 16, _GW),
+    _p("run_wgrad", "capi.hip:64", "big_layout == DVAE_NHWC", "conv", _WG, _C, "bl", "NCHW", _GW),
+    _p("run_wgrad", "capi.hip:64", "Hs == 4", "conv", _WG, _C8, "H,W", (4, 4), _GW),
+    _p("run_wgrad", "capi.hip:64", "Hs == 8", "conv", _WG, _C16, "H,W", (12, 12), _GW),
+    _p("run_wgrad", "capi.hip:64", "Hs == 16", "conv", _WG, _C, "H,W", (64, 64), "k_wgrad_generic_part + k_wgrad_generic_fin"),
+    _p("run_wgrad (thin)", "capi.hip:67", "Cb == 1", "conv", _WG, _T1, "Cb", 2, "k_wgrad_generic_part + k_wgrad_generic_fin"),
+    _p("run_wgrad (thin)", "capi.hip:67", "Cb == 3", "conv", _WG, _T, "Cb", 4, "k_wgrad_generic_part + k_wgrad_generic_fin"),
+    _p("run_wgrad (thin)", "capi.hip:67", "Hs == 32", "conv", _WG, _T, "H,W", (32, 32), _GW),
+    _p("run_wgrad (thin)", "capi.hip:67", "big_layout == DVAE_NCHW", "conv", _WG, _T, "bl", "NHWC", "k_wgrad_generic_part + k_wgrad_generic_fin"),
+    _p("run_wgrad (thin)", "capi.hip:67", "aligned16(small, ws)", "conv", _WG, _T, "off", ("small", 4), "k_wgrad_generic_part + k_wgrad_generic_fin"),
+    _p("dvae_convT4s2_sigmoid_recon_fwd", "capi.hip:142", "aligned16(target, recon, g)", "refusal", "dvae_convT4s2_sigmoid_recon_fwd",
+       dict(target_off=0), "target_off", 4, "none: refused by DVAE_CHECK_ARG", P + "test_fused_likelihood[%s]" % conv_id(_T), _REFUSED),
+    _p("dvae_convT4s2_sigmoid_recon_fwd", "capi.hip:145", "aligned16(x, w, b)", "fused", "dvae_convT4s2_sigmoid_recon_fwd", _T, "off",
+       ("small", 4), "k_up_generic + k_recon_loss"),
+    # ---- conv_mfma.hip: mfma32_applicable (l0, l1 = big, small layouts in launch_down_mfma32; small, big in launch_up_mfma32)
+    _p("mfma32_applicable", "conv_mfma.hip:439", "Cb == 32", "conv", _DN + ", " + _UP, _C, "Cb", 16, _GD + " / " + _GU),
+    _p("mfma32_applicable", "conv_mfma.hip:439", "Cs == 32", "conv", _DN + ", " + _UP, _C, "Cs", 16, _GD + " / " + _GU),
+    _p("mfma32_applicable", "conv_mfma.hip:439", "Hs == Ws", "conv", _DN + ", " + _UP, _C, "H", 16, _GD + " / " + _GU),
+    _p("mfma32_applicable", "conv_mfma.hip:439", "Hs == 4", "conv", _DN + ", " + _UP, _C8, "H,W", (4, 4), _GD + " / " + _GU),
+    _p("mfma32_applicable", "conv_mfma.hip:439", "Hs == 8", "conv", _DN + ", " + _UP, _C16, "H,W", (12, 12), _GD + " / " + _GU),
+    _p("mfma32_applicable", "conv_mfma.hip:439", "Hs == 16", "conv", _DN + ", " + _UP, _C, "H,W", (64, 64), _GD + " / " + _GU),
+    _p("mfma32_applicable", "conv_mfma.hip:439", "l0 == DVAE_NHWC", "conv", _DN, _C, "bl", "NCHW", _GD),
+    _p("mfma32_applicable", "conv_mfma.hip:440", "l1 == DVAE_NHWC", "conv", _DN, _C, "sl", "NCHW", _GD),
+    _unreachable("mfma32_applicable", "conv_mfma.hip:440", "l2 == DVAE_NHWC", "both call sites (conv_mfma.hip:446, 456) pass the literal DVAE_NHWC"),
+    _p("launch_down_mfma32", "conv_mfma.hip:445", "a.Hs == 4", "conv", _DN, _C4N, "H,W", (16, 16), _GD),
+    _p("launch_down_mfma32", "conv_mfma.hip:445", "a.out_layout == DVAE_NCHW", "conv", _DN, _C4N, "sl", "NHWC", "k_down32<4, *> (still)"),
+    _p("launch_down_mfma32", "conv_mfma.hip:447", "a.act != DVAE_ACT_NONE", "conv", "dvae_conv4s2_fwd", _CSIG, "act", "none", "k_down32dma<16, false>"),
+    _p("launch_down_mfma32", "conv_mfma.hip:447", "a.act != DVAE_ACT_RELU", "conv", "dvae_conv4s2_fwd", _CSIG, "act", "relu", "k_down32dma<16, false>"),
+    _p("launch_down_mfma32", "conv_mfma.hip:449", "a.Hs == 16", "conv", _DN, _C, "H,W", (16, 16), "k_down32dma<8, *> (still)"),
+    _p("launch_down_mfma32", "conv_mfma.hip:449", "a.Hs == 8", "conv", _DN, _C16, "H,W", (8, 8), "k_down32<4, *>"),
+    _p("launch_up_mfma32", "conv_mfma.hip:455", "a.Hs == 4", "conv", _UP, _C4N, "H,W", (16, 16), _GU),
+    _p("launch_up_mfma32", "conv_mfma.hip:455", "a.small_layout == DVAE_NCHW", "conv", _UP, _C4N, "sl", "NHWC", "k_up32<4, *> (still)"),
+    _p("launch_up_mfma32", "conv_mfma.hip:457", "a.act != DVAE_ACT_NONE", "conv", "dvae_convT4s2_fwd", conv_case(H=8, W=8, act="sigmoid"), "act", "none", "k_up32<4, false>"),
+    _p("launch_up_mfma32", "conv_mfma.hip:457", "a.act != DVAE_ACT_RELU", "conv", "dvae_convT4s2_fwd", conv_case(H=8, W=8, act="sigmoid"), "act", "relu", "k_up32<4, false>"),
+    _p("launch_wgrad_mfma32", "conv_mfma.hip:468", "Hs == 16", "conv", _WG, _C, "H,W", (16, 16), "k_wgrad32ws<8> (still)"),
+    _p("launch_wgrad_mfma32", "conv_mfma.hip:468", "Hs == 8", "conv", _WG, _C16, "H,W", (8, 8), "k_wgrad32<4>"),
+    # ---- conv_up_ws.hip: launch_up_mfma32_ws
+    _p("launch_up_mfma32_ws", "conv_up_ws.hip:382", "a.Cb == 32", "conv", _UP, _C, "Cb", 16, _GU),
+    _p("launch_up_mfma32_ws", "conv_up_ws.hip:382", "a.Cs == 32", "conv", _UP, _C, "Cs", 16, _GU),
+    _p("launch_up_mfma32_ws", "conv_up_ws.hip:382", "a.Hs == a.Ws", "conv", _UP, _C, "W", 16, _GU),
+    _p("launch_up_mfma32_ws", "conv_up_ws.hip:382", "a.Hs == 8", "conv", _UP, _C16, "H,W", (8, 8), "k_up32<4, *> (launch_up_mfma32)"),
+    _p("launch_up_mfma32_ws", "conv_up_ws.hip:382", "a.Hs == 16", "conv", _UP, _C, "H,W", (64, 64), _GU),
+    _p("launch_up_mfma32_ws", "conv_up_ws.hip:382", "a.small_layout == DVAE_NHWC", "conv", _UP, _C, "sl", "NCHW", _GU),
+    _p("launch_up_mfma32_ws", "conv_up_ws.hip:383", "a.out_layout == DVAE_NHWC", "conv", _UP, _C, "bl", "NCHW", _GU),
+    _p("launch_up_mfma32_ws", "conv_up_ws.hip:385", "a.act != DVAE_ACT_NONE", "conv", "dvae_convT4s2_fwd", _CSIG, "act", "none", "k_up32ws<16, 0, false>"),
+    _p("launch_up_mfma32_ws", "conv_up_ws.hip:385", "a.act != DVAE_ACT_RELU", "conv", "dvae_convT4s2_fwd", _CSIG, "act", "relu", "k_up32ws<16, 0, false>"),
+    # ---- conv_thin.hip: thin_applicable and the layout / activation / alignment terms beside it
+    _p("thin_applicable", "conv_thin.hip:671", "a.Cb == 1", "conv", _DN + ", " + _UP, _T1, "Cb", 2, _GD + " / " + _GU),
+    _p("thin_applicable", "conv_thin.hip:671", "a.Cb == 3", "conv", _DN + ", " + _UP, _T, "Cb", 4, _GD + " / " + _GU),
+    _p("thin_applicable", "conv_thin.hip:671", "a.Cs == 32", "conv", _DN + ", " + _UP, _T, "Cs", 16, _GD + " / " + _GU),
+    _p("thin_applicable", "conv_thin.hip:671", "a.Hs == 32", "conv", _DN + ", " + _UP, _T, "H", 32, "k_down_thin_px<3> / k_up_thin_px<3>"),
+    _p("thin_applicable", "conv_thin.hip:671", "a.Ws == 32", "conv", _DN + ", " + _UP, _T, "W", 32, "k_down_thin_px<3> / k_up_thin_px<3>"),
+    _p("launch_down_thin", "conv_thin.hip:675", "a.big_layout != DVAE_NCHW", "conv", _DN, _T, "bl", "NHWC", _GD),
+    _p("launch_down_thin", "conv_thin.hip:675", "a.out_layout != DVAE_NHWC", "conv", _DN, _T, "sl", "NCHW", _GD),
+    _p("launch_down_thin", "conv_thin.hip:676", "a.act != DVAE_ACT_NONE", "conv", "dvae_conv4s2_fwd", _TSIG, "act", "none", "k_down_thin<3, 0, float>"),
+    _p("launch_down_thin", "conv_thin.hip:676", "a.act != DVAE_ACT_RELU", "conv", "dvae_conv4s2_fwd", _TSIG, "act", "relu", "k_down_thin<3, 0, float>"),
+    _p("launch_up_thin", "conv_thin.hip:694", "a.small_layout != DVAE_NHWC", "conv", "dvae_convT4s2_fwd", _T, "sl", "NCHW", _GU),
+    _p("launch_up_thin", "conv_thin.hip:694", "a.out_layout != DVAE_NCHW", "conv", "dvae_convT4s2_fwd", _T, "bl", "NHWC", "k_up_thin_px<3>"),
+    _p("launch_up_thin", "conv_thin.hip:694", "a.act == DVAE_ACT_LEAKY02", "conv", "dvae_convT4s2_fwd", _T, "act", "leaky", "k_up_thin_px<3>"),
+    _p("launch_up_thin", "conv_thin.hip:695", "(((uintptr_t)a.small | (uintptr_t)a.w) & 15) != 0", "conv", "dvae_convT4s2_fwd", _T, "off", ("small", 4), _GU),
+    _p("launch_up_thin", "conv_thin.hip:695", "((uintptr_t)a.out & 7) != 0", "conv", "dvae_convT4s2_fwd", _T, "off", ("big", 4), "k_up_thin_px<3>"),
+    _p("launch_up_thin_recon", "conv_thin.hip:705", "a.small_layout != DVAE_NHWC", "fused", "dvae_convT4s2_sigmoid_recon_fwd", _T, "sl", "NCHW",
+       "k_up_generic + k_recon_loss"),
+    _unreachable("launch_up_thin_recon", "conv_thin.hip:705", "a.out_layout != DVAE_NCHW",
+                 "dvae_convT4s2_sigmoid_recon_fwd (capi.hip:143) builds the arguments with the literal DVAE_NCHW: recon is NCHW by contract"),
+    _unreachable("launch_wgrad_thin", "conv_thin.hip:765", "Cb == 1", _CALLER % "run_wgrad (capi.hip:67)"),
+    _unreachable("launch_wgrad_thin", "conv_thin.hip:765", "Cb == 3", _CALLER % "run_wgrad (capi.hip:67)"),
+    _unreachable("launch_wgrad_thin", "conv_thin.hip:765", "Hs != 32", _CALLER % "run_wgrad (capi.hip:67)"),
+    # ---- conv_thin_ws.hip (N >= 192: the pairs are the tests of the wave-specialised switch, which run 193 images)
+    _unreachable("launch_down_thin_ws", "conv_thin_ws.hip:326", "a.act != DVAE_ACT_NONE",
+                 "mask_bits comes from dvae_convT3_dgrad_bits alone, which passes DVAE_ACT_NONE, no bias and no out_bits (capi.hip:443)"),
+    _unreachable("launch_down_thin_ws", "conv_thin_ws.hip:327", "a.act != DVAE_ACT_RELU",
+                 "out_bits comes from dvae_conv1_fwd_bits alone, which passes DVAE_ACT_RELU (capi.hip:420)"),
+    _p("launch_down_thin_ws", "conv_thin_ws.hip:328", "& 15", "thin_ws", "dvae_conv4s2_fwd", dict(N=193, C=3, off=0), "off", 4, "k_down_thin<3, 0, float>",
+       _PAST + "[193-3]", V + "test_thin_ends_past_the_cap_on_buffers_the_wave_specialised_kernels_decline"),
+    _p("launch_down_thin_ws", "conv_thin_ws.hip:330", "& 15", "thin_ws", "dvae_conv1_fwd_bits, dvae_convT3_dgrad_bits", dict(N=193, C=3, off=0), "off", 4,
+       "k_down_thin<3, 3, float> / k_down_thin<3, 2, float>", _PAST + "[193-3]",
+       V + "test_thin_ends_past_the_cap_on_buffers_the_wave_specialised_kernels_decline"),
+    _unreachable("launch_wgrad_thin_ws", "conv_thin_ws.hip:625", "Cb != 1", _CALLER % "launch_wgrad_thin (conv_thin.hip:765)"),
+    _unreachable("launch_wgrad_thin_ws", "conv_thin_ws.hip:625", "Cb != 3", _CALLER % "launch_wgrad_thin (conv_thin.hip:765)"),
+    _p("launch_wgrad_thin_ws", "conv_thin_ws.hip:626", "& 15", "thin_ws", _WG, dict(N=193, C=3, off=0), "off", 4, "k_wgrad_thin<3, float>",
+       _PAST + "[193-3]", V + "test_thin_ends_past_the_cap_on_buffers_the_wave_specialised_kernels_decline"),
+    # ---- conv_generic.hip: the k_*_thin_px branches
+    _p("launch_down_generic", "conv_generic.hip:342", "a.Cs == 32", "conv", _DN, _PX, "Cs", 16, _GD),
+    _p("launch_down_generic", "conv_generic.hip:342", "a.Cb == 1", "conv", _DN, _PX1, "Cb", 2, _GD),
+    _p("launch_down_generic", "conv_generic.hip:342", "a.Cb == 3", "conv", _DN, _PX, "Cb", 4, _GD),
+    _p("launch_down_generic", "conv_generic.hip:342", "a.big_layout == DVAE_NCHW", "conv", _DN, _PX, "bl", "NHWC", _GD),
+    _p("launch_down_generic", "conv_generic.hip:342", "a.out_layout == DVAE_NHWC", "conv", _DN, _PX, "sl", "NCHW", _GD),
+    _p("launch_down_generic", "conv_generic.hip:343", "& 15", "conv", _DN, _PX, "off", ("small", 4), _GD),
+    _p("launch_up_generic", "conv_generic.hip:362", "a.Cs == 32", "conv", _UP, _PX, "Cs", 16, _GU),
+    _p("launch_up_generic", "conv_generic.hip:362", "a.Cb == 1", "conv", _UP, _PX1, "Cb", 2, _GU),
+    _p("launch_up_generic", "conv_generic.hip:362", "a.Cb == 3", "conv", _UP, _PX, "Cb", 4, _GU),
+    _p("launch_up_generic", "conv_generic.hip:362", "a.small_layout == DVAE_NHWC", "conv", _UP, _PX, "sl", "NCHW", _GU),
+    _p("launch_up_generic", "conv_generic.hip:362", "& 15", "conv", _UP, _PX, "off", ("small", 8), _GU),
+    # ---- linear.hip (through the C-ABI lda = ldb = K forward, lda = N and ldb = K for the input gradient: one argument moves both)
+    _p("try_fc32", "linear.hip:414", "& 15", "linear", _FW, _L, "off", ("x", 4), "k_gemm<true, false>"),
+    _p("try_fc32<false>", "linear.hip:415", "Kc % 4", "linear", _FW, _L12, "K", 10, "k_fc32<32, false, 1>"),
+    _p("try_fc32<false>", "linear.hip:415", "lda % 4", "linear", _FW, _L12, "K", 10, "k_fc32<32, false, 1>"),
+    _p("try_fc32<false>", "linear.hip:415", "ldb % 4", "linear", _FW, _L12, "K", 10, "k_fc32<32, false, 1>"),
+    _p("try_fc32", "linear.hip:419", "Kc % 4", "linear", _FW, _L, "K", 510, "k_gemm<true, false>"),
+    _p("try_fc32<true>", "linear.hip:419", "lda % 4", "linear", _DG, _L, "N", 255, "k_gemm<true, true>"),
+    _p("try_fc32<true>", "linear.hip:420", "N % 4", "linear", _DG, _L12, "K", 10, "k_fc32<256, true, 2>"),
+    _p("try_fc32<true>", "linear.hip:420", "ldb % 4", "linear", _DG, _L12, "K", 10, "k_fc32<256, true, 2>"),
+    _unreachable("try_fc32<false>", "linear.hip:421", "ldb % 4", "the forward passes ldb = K = Kc, and linear.hip:419 has already returned for Kc % 4 != 0"),
+    _p("try_fcw32", "linear.hip:534", "N % 4", "linear", _WGL, _L, "N", 255, "k_gemm<false, true>"),
+    _p("try_fcw32", "linear.hip:534", "K % 4", "linear", _WGL, _L, "K", 510, "k_gemm<false, true>"),
+    _p("try_fcw32", "linear.hip:535", "& 15", "linear", _WGL, _L, "off", ("dy", 8), "k_gemm<false, true>"),
+    _p("launch_linear_fwd", "linear.hip:629", "K % 4 == 0", "linear", _FW, _LS, "K", 1001, "k_gemm<true, false> + k_splitk_epilogue"),
+    _p("launch_linear_fwd", "linear.hip:629", "& 15", "linear", _FW, _LS, "off", ("w", 4), "k_gemm<true, false> + k_splitk_epilogue"),
+    _unreachable("launch_linear_dgrad", "linear.hip:670", "N % 4 == 0", _SMALL_ONLY),
+    _unreachable("launch_linear_dgrad", "linear.hip:670", "& 15", _SMALL_ONLY),
+    # ---- gemm_dma.hip
+    _p("launch_gdma_t (vec_ok)", "gemm_dma.hip:473", "N % 4 == 0", "linear", _FW, _LD, "N", 1002, "k_gdma<32, 32, 64, 3, 4, false, 0> (scalar epilogue)"),
+    _p("launch_gdma_t (vec_ok)", "gemm_dma.hip:473", "ldc % 4 == 0", "linear", _FW, _LD, "N", 1002, "k_gdma<32, 32, 64, 3, 4, false, 0> (scalar epilogue)"),
+    _p("launch_gdma_t (vec_ok)", "gemm_dma.hip:473", "& 15", "linear", _FW, _LD, "off", ("y", 4), "k_gdma<32, 32, 64, 3, 4, false, 0> (scalar epilogue)"),
+    _p("try_gdma", "gemm_dma.hip:482", "Kc % 4", "linear", _FW, _LD, "K", 1001, "k_gemm<true, false>"),
+    _p("try_gdma", "gemm_dma.hip:482", "lda % 4", "linear", _DG, _LD, "N", 1001, "k_gemm<true, true>"),
+    _p("try_gdma", "gemm_dma.hip:482", "ldb % 4", "linear", _FW, _LD, "K", 1001, "k_gemm<true, false>"),
+    _p("try_gdma", "gemm_dma.hip:482", "N % 4", "linear", _DG, _LD, "K", 1001, "k_gemm<true, true>"),
+    _p("try_gdma", "gemm_dma.hip:483", "& 15", "linear", _FW, _LD, "off", ("w", 4), "k_gemm<true, false>"),
+    _p("try_gdma_wgrad", "gemm_dma.hip:517", "N % 4", "linear", _WGL, _LD, "N", 1002, "k_gemm<false, true>"),
+    _p("try_gdma_wgrad", "gemm_dma.hip:517", "K % 4", "linear", _WGL, _LD, "K", 1001, "k_gemm<false, true>"),
+    _p("try_gdma_wgrad", "gemm_dma.hip:519", "& 15", "linear", _WGL, _LD, "off", ("dw", 8), "k_fcw32<64>"),
+    # ---- linear_narrow.hip
+    _p("try_narrow_fwd", "linear_narrow.hip:88", "K % 4", "linear", _FW, _LN, "K", 1001, "k_gemm<true, false>"),
+    _p("try_narrow_fwd", "linear_narrow.hip:88", "aligned16(x, w)", "linear", _FW, _LN, "off", ("x", 4), "k_gemm<true, false>"),
+    _p("try_narrow_dgrad", "linear_narrow.hip:99", "K % 4", "linear", _DG, _LN, "K", 1001, "k_gemm<true, true>"),
+    _p("try_narrow_dgrad", "linear_narrow.hip:99", "aligned16(w, x_act, dx)", "linear", _DG, _LN, "off", ("dx", 4), "k_gemm<true, true>"),
+    # ---- linear_grouped.hip: the two flag bits of a problem (each problem of one launch of test_linear_wgrad_grouped_flag_bits)
+    _p("launch_linear_wgrad_grouped", "linear_grouped.hip:161", "p.N % 4 == 0", "grouped", "dvae_linear_wgrad_grouped", dict(_GRP, K=256), "N", 18,
+       "k_fcw_grouped<64>, 4-byte loads of dy", _GRP_BASE, _GRP_TEST),
+    _p("launch_linear_wgrad_grouped", "linear_grouped.hip:161", "((uintptr_t)p.dy & 15) == 0", "grouped", "dvae_linear_wgrad_grouped", dict(_GRP, K=256, N=20),
+       "dy_off", 4, "k_fcw_grouped<64>, 4-byte loads of dy", _GRP_BASE, _GRP_TEST),
+    _p("launch_linear_wgrad_grouped", "linear_grouped.hip:161", "p.K % 4 == 0", "grouped", "dvae_linear_wgrad_grouped", dict(_GRP, K=12), "K", 10,
+       "k_fcw_grouped<64>, 4-byte loads of x", _GRP_BASE, _GRP_TEST),
+    _p("launch_linear_wgrad_grouped", "linear_grouped.hip:161", "((uintptr_t)p.x & 15) == 0", "grouped", "dvae_linear_wgrad_grouped", dict(_GRP, K=256, N=20),
+       "x_off", 8, "k_fcw_grouped<64>, 4-byte loads of x", _GRP_BASE, _GRP_TEST),
+]
+
+# The launcher-condition lines the host test scans for ==, !=, % and alignment comparisons: every comparison found on them must
+# be the `term` of a row above with that `where` -- a term added to one of these conditions later fails the host test until it
+# has its pair.  (file, lines)
+PREDICATE_LINES = [
+    ("capi.hip", (31, 42, 57, 58, 60, 61, 63, 64, 67, 142, 145)),
+    ("conv_mfma.hip", (439, 440, 445, 447, 449, 455, 457, 468)),
+    ("conv_up_ws.hip", (382, 383, 385)),
+    ("conv_thin.hip", (671, 675, 676, 694, 695, 705, 765)),
+    ("conv_thin_ws.hip", (326, 327, 328, 330, 625, 626)),
+    ("conv_generic.hip", (342, 343, 362)),
+    ("linear.hip", (414, 415, 419, 420, 421, 534, 535, 629, 670)),
+    ("gemm_dma.hip", (473, 482, 483, 517, 519)),
+    ("linear_narrow.hip", (88, 99)),
+    ("linear_grouped.hip", (161,)),
+]

@@ -7,6 +7,9 @@
   test), OPEN_SWITCHES is empty, and pytest collects every id named;
 * TRIP_CLASSES: the launch arithmetic, evaluated at the image count of each named test, gives the trip-count class the table
   claims for it, and every required class of every persistent kernel family has a test;
+* PREDICATES: every row cites a source line that holds its term, its neighbour is its base with the one named argument changed,
+  it names two different tests (or the reason no call negates the term), and every ==, !=, % or alignment comparison on the
+  launcher-condition lines of the conv and linear files is the term of some row;
 * tools/kernel_trace_names.py reduces a kernel trace to the same spelling of the names."""
 import os
 import re
@@ -167,7 +170,8 @@ def test_trip_class_table_claims_what_the_launch_arithmetic_gives():
 
 def test_every_named_test_is_collected():
     ids = ({v.test for v in KV.VARIANTS if v.test} | {t for s in KV.SWITCHES for t in (s.below_test, s.above_test) if t}
-           | {c[2] for f in KV.TRIP_CLASSES for c in f.cases})
+           | {c[2] for f in KV.TRIP_CLASSES for c in f.cases}
+           | {t for r in KV.PREDICATES for t in (r.base_test, r.test) if t})
     assert all(i.startswith("tests/test_gpu_") for i in ids)
     files = sorted({i.split("::")[0] for i in ids})
     r = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + files, cwd=ROOT,
@@ -176,6 +180,74 @@ def test_every_named_test_is_collected():
     assert collected, r.stdout[-2000:] + r.stderr[-2000:]
     missing = sorted(ids - collected)
     assert not missing, "test ids named in tests/kernel_variants.py that pytest does not collect: %s" % missing
+
+
+def _csrc_lines(f, cache={}):
+    if f not in cache:
+        with open(os.path.join(ROOT, "disentangling-vae_amd", "csrc", f)) as fh:
+            cache[f] = fh.read().split("\n")
+    return cache[f]
+
+
+def test_every_predicate_row_cites_its_term_and_pairs_a_base_with_one_changed_argument():
+    assert len(KV.PREDICATES) > 100
+    for r in KV.PREDICATES:
+        f, _, ln = r.where.partition(":")
+        lines = _csrc_lines(f)
+        assert 0 < int(ln) <= len(lines) and r.term in lines[int(ln) - 1], (r.where, r.term)
+        assert r.launcher and r.term, r
+        if r.reason is not None:                                    # no C-ABI call negates the term: the argument, no half-filled pair
+            assert r.base is r.neighbour is r.arg is r.kernel is r.base_test is r.test is None and len(r.reason) > 40, r
+            continue
+        assert r.entry and r.kernel and r.family, r
+        keys = set(r.arg.split(","))
+        assert set(r.base) == set(r.neighbour), r
+        assert {k for k in r.base if r.base[k] != r.neighbour[k]} == keys, (r.where, r.term, "the neighbour differs from the base in", r.arg)
+        assert r.base_test and r.test and r.base_test != r.test, (r.where, r.term)
+        if r.family in KV._FAMILY_TEST:                             # the ids are the ids of the two argument sets
+            fn, ident = KV._FAMILY_TEST[r.family]
+            assert r.base_test.endswith("::%s[%s]" % (fn, ident(r.base))) and r.test.endswith("::%s[%s]" % (fn, ident(r.neighbour))), r
+    assert len({(r.where, r.term, r.launcher) for r in KV.PREDICATES}) == len(KV.PREDICATES), "a term is listed twice"
+
+
+_CMP = re.compile(r"[A-Za-z_][\w.]*(?:\s*%\s*\d+)?\s*(?:==|!=)\s*[A-Za-z_0-9][\w.:]*")
+_MOD = re.compile(r"[A-Za-z_][\w.]*\s*%\s*\d+")
+_ALIGN = re.compile(r"&\s*(?:15|7)\b|aligned16\([^()]*\)")
+
+
+def predicate_terms(line):
+    """the ==, !=, % and alignment comparisons of one source line (comments dropped), as the source spells them."""
+    line = line.split("//")[0]
+    out = _CMP.findall(line)
+    rest = _CMP.sub(" ", line)
+    return out + _MOD.findall(rest) + _ALIGN.findall(rest)
+
+
+def test_predicate_term_scanner():
+    assert predicate_terms("  if (!(a.Cb == 32 && a.Hs == a.Ws && (a.Hs == 8 || a.Hs == 16) && a.l != DVAE_NHWC)) return 1;  // x == y") == [
+        "a.Cb == 32", "a.Hs == a.Ws", "a.Hs == 8", "a.Hs == 16", "a.l != DVAE_NHWC"]
+    assert predicate_terms("if (off || Kc < 256 || Kc % 4 || (b && N % 4)) return false;") == ["Kc % 4", "N % 4"]
+    assert predicate_terms("const int v = N % 4 == 0 && (((uintptr_t)c | (uintptr_t)b) & 15) == 0;") == ["N % 4 == 0", "& 15"]
+    assert predicate_terms("if (tuned && ws != nullptr && aligned16(small, ws)) x;") == ["ws != nullptr", "aligned16(small, ws)"]
+
+
+def test_every_comparison_of_a_launcher_condition_has_a_predicate_row():
+    """A term added to one of the scanned launcher conditions (KV.PREDICATE_LINES) has no row, and fails here until it gets its
+    base / neighbour pair; a condition that moves takes its rows' `where` along (the first test above holds them to the text)."""
+    rows = {}
+    for r in KV.PREDICATES:
+        rows.setdefault(r.where, []).append(r.term)
+    scanned = set()
+    for f, lns in KV.PREDICATE_LINES:
+        lines = _csrc_lines(f)
+        for ln in lns:
+            where = "%s:%d" % (f, ln)
+            scanned.add(where)
+            found = predicate_terms(lines[ln - 1])
+            assert found, (where, "no comparison on this line: PREDICATE_LINES is stale")
+            for t in found:
+                assert any(t in term for term in rows.get(where, ())), "%s: `%s` has no row in KV.PREDICATES" % (where, t)
+    assert not sorted(set(rows) - scanned), "rows on lines that PREDICATE_LINES does not scan"
 
 
 TRACE_SAMPLE = '''"Kind","Agent_Id","Queue_Id","Kernel_Id","Kernel_Name","Correlation_Id","Start_Timestamp","End_Timestamp"
