@@ -72,6 +72,7 @@ SCORE_TARGETS = [
     ("knn", ["knn_mi"], "dvae_knn_hip.h"),                 # binning-free MIG / InfoM / InfoC: k-nearest-neighbour mutual information (Ross 2014)
     ("lr", ["softmax_fit"], "dvae_lr_hip.h"),              # linear-softmax probes (beta-VAE score, explicitness, InfoE): Newton-CG fits on the device
     ("weak", ["weak_pairs"], "dvae_weak_hip.h"),           # Ada-GVAE / Ada-ML-VAE: the adaptive group posterior of image pairs and its backward pass (a TRAINING plugin, not a score)
+    ("semi", ["label_reg"], "dvae_semi_hip.h"),            # S2-beta-VAE: the supervised regulariser on the labelled rows of a batch and its gradient (a TRAINING plugin, not a score)
 ]
 SCORE_DIR = os.path.join("..", "lib_scores")
 HEADERS = sorted(glob.glob(os.path.join(SRC, "*.h"))) + [os.path.join(HERE, "..", "include", "dvae_hip.h")]

@@ -32,8 +32,8 @@ from .evaluate import (Evaluator, dci_from_importance, dci_from_table, downstrea
                        separability_scores_from_entropies, udr_from_tables)
 from .visualize import Visualizer, GifTraversalsTraining  # noqa: E402
 from .likelihood import per_image_losses, log_likelihood  # noqa: E402
-from .models.losses import DipVaeLoss, InfoVaeLoss, WeakVaeLoss, adaptive_group_posterior  # noqa: E402
-from .data import PairedFactorLoader, draw_pair_partners  # noqa: E402
+from .models.losses import DipVaeLoss, InfoVaeLoss, SemiSupervisedVaeLoss, WeakVaeLoss, adaptive_group_posterior  # noqa: E402
+from .data import LabelledFactorLoader, PairedFactorLoader, draw_pair_partners  # noqa: E402
 
 __all__ = ["init_specific_model", "Trainer", "Evaluator", "Visualizer", "GifTraversalsTraining", "per_image_losses",
            "log_likelihood", "udr_from_tables", "dci_from_table", "dci_from_importance", "DipVaeLoss", "InfoVaeLoss",
@@ -41,4 +41,4 @@ __all__ = ["init_specific_model", "Trainer", "Evaluator", "Visualizer", "GifTrav
            "interpretability_scores_from_table", "interpretability_scores_from_mass", "sap_discrete_from_table",
            "sap_discrete_from_score_matrix", "knn_information_scores_from_table", "knn_information_scores_from_mi",
            "digamma_integers", "fit_logistic_regression_device", "infoe_from_table", "infoe_from_log_loss", "WeakVaeLoss",
-           "adaptive_group_posterior", "PairedFactorLoader", "draw_pair_partners"]
+           "adaptive_group_posterior", "PairedFactorLoader", "draw_pair_partners", "SemiSupervisedVaeLoss", "LabelledFactorLoader"]

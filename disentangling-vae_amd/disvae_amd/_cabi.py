@@ -1,6 +1,6 @@
 """The one ctypes loader behind the bindings of every library but the training library's (_evallib.py, _scorelib.py, _infolib.py,
 _irslib.py, _unsuplib.py, _udrlib.py, _dcilib.py, _diplib.py, _mmdlib.py, _seplib.py, _masslib.py, _saplib.py, _knnlib.py,
-_lrlib.py, _weaklib.py).
+_lrlib.py, _weaklib.py, _semilib.py).
 
 Each of those modules states what is its own -- its short name, mirrored constants, SIGNATURES, _RESTYPE -- and keeps a
 module-level LIB_PATH and lib() / call() pair in front of one Binding.for_library(name, ...), which derives the rest from the

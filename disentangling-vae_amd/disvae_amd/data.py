@@ -204,3 +204,49 @@ class PairedFactorLoader(DeviceImageLoader):
         index_dev = index.to(self.images.device)           # ONE host-to-device copy per epoch
         for i, per in spans:
             yield self.images.index_select(0, index_dev[2 * i:2 * (i + per)]), changed[i:i + per]
+
+
+class LabelledFactorLoader(DeviceImageLoader):
+    """Batches for SemiSupervisedVaeLoss out of a device-resident data set that enumerates its factors of variation by row number
+    (dSprites, 3D shapes, ...: prod(lat_sizes) images in row-major order of the factor values): half of every batch is the
+    unlabelled data set, the other half comes from a small labelled subset.
+
+    ``batch_size`` counts the images of ONE half (P): an item is ``(batch, rows)`` with ``batch`` uint8 [2 P, C, H, W] and
+    ``rows`` int64 [2 P] on the device -- what SemiSupervisedVaeLoss.fused_step takes as ``labels``.  Rows [0, P) of a batch
+    follow ``DeviceImageLoader.epoch_order(N)`` and carry -1 (unlabelled); rows [P, 2 P) cycle through a per-epoch permutation of
+    the labelled subset and carry their row numbers, from which the kernels derive the factor values.  ``len()`` is
+    ceil(N / batch_size); the last batch may be smaller (both halves shrink alike).
+
+    The labelled subset -- ``n_labelled`` distinct rows -- is drawn ONCE, at construction, from a private generator seeded with
+    ``seed``: the same seed gives the same subset whatever the global generator holds.  Per epoch the first halves consume the
+    global CPU generator as the reference loader does, then ONE more ``random_()`` draw of it seeds a private generator for the
+    subset's permutation (as PairedFactorLoader does for its partners).  The row numbers of all batches go to the device in one
+    copy; a batch is one ``index_select`` of 2 P rows."""
+
+    def __init__(self, images, lat_sizes, batch_size=64, n_labelled=1000, seed=0, device="cuda"):
+        super().__init__(images, batch_size=batch_size, shuffle=True, device=device)
+        self.lat_sizes = tuple(int(s) for s in lat_sizes)
+        if int(np.prod(self.lat_sizes, dtype=np.int64)) != self.n_images:
+            raise ValueError("lat_sizes %s enumerate %d images, the data set has %d"
+                             % (self.lat_sizes, int(np.prod(self.lat_sizes, dtype=np.int64)), self.n_images))
+        self.n_labelled = int(n_labelled)
+        if not 1 <= self.n_labelled <= self.n_images:
+            raise ValueError("n_labelled must lie in 1 .. %d (the images of the data set), got %d" % (self.n_images, self.n_labelled))
+        g = torch.Generator()
+        g.manual_seed(int(seed))
+        self.labelled_rows = torch.randperm(self.n_images, generator=g)[:self.n_labelled].clone()      # int64 [n_labelled], host
+
+    def __iter__(self):
+        n = self.n_images
+        order = self.epoch_order(n)
+        g = torch.Generator()
+        g.manual_seed(int(torch.empty((), dtype=torch.int64).random_().item()))
+        perm = torch.randperm(self.n_labelled, generator=g)
+        labelled = self.labelled_rows[perm][torch.arange(n) % self.n_labelled]     # position j of the epoch: the cycle's j-th row
+        spans = self._global_batches()
+        index = torch.cat([torch.cat((order[i:i + per], labelled[i:i + per])) for i, per in spans])
+        index_dev = index.to(self.images.device)           # ONE host-to-device copy per epoch
+        unlabelled = torch.full((self.batch_size,), -1, dtype=torch.int64, device=self.images.device)
+        for i, per in spans:
+            sel = index_dev[2 * i:2 * (i + per)]
+            yield self.images.index_select(0, sel), torch.cat((unlabelled[:per], sel[per:]))

@@ -234,10 +234,14 @@ class Evaluator:
         """evaluate.py:97-117."""
         storer = defaultdict(list)
         n = len(dataloader)
-        for data, _ in dataloader:
+        takes_labels = getattr(self.loss_f, "takes_labels", False)
+        for data, labels in dataloader:
             data = data.to(self.device)
             if isinstance(self.loss_f, FactorKLoss):
                 self.loss_f.call_optimize(data, self.model, None, storer)     # evaluate.py:112-114
+            elif takes_labels:                                                # SemiSupervisedVaeLoss: the batch's row numbers, if any
+                self.loss_f.fused_step(data, self.model, None, storer,
+                                       labels=labels.to(self.device) if torch.is_tensor(labels) else None)
             else:
                 self.loss_f.fused_step(data, self.model, None, storer)
             if self.reference_early_return:

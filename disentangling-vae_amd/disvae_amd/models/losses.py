@@ -1,7 +1,7 @@
 """Loss plugins with the API of disvae/models/losses.py (get_loss_f, BaseLoss, BetaHLoss,
 BetaBLoss, FactorKLoss, BtcvaeLoss, LOSSES, RECON_DIST) on the HIP kernels, plus DipVaeLoss / DIP_LOSSES
 (DIP-VAE-I / II), InfoVaeLoss / INFO_LOSSES (InfoVAE / MMD-VAE) and WeakVaeLoss / WEAK_LOSSES (Ada-GVAE / Ada-ML-VAE on image
-pairs), which the reference does not have.
+pairs) and SemiSupervisedVaeLoss / SEMI_LOSSES (S2-beta-VAE on a few labelled images), which the reference does not have.
 
 Two ways in:
   * ``loss(data, recon, latent_dist, is_train, storer, latent_sample=...)`` -- the reference
@@ -15,12 +15,14 @@ Host-side state (n_train_steps, annealing, storer cadence) follows losses.py:71-
 """
 import abc
 import contextlib
+import ctypes
 
 import torch
 
 from .. import _diplib
 from .. import _mmdlib
 from .. import _weaklib
+from .. import _semilib
 from .. import _lib
 from .. import optim
 from .._lib import call, ptr, record_py
@@ -36,6 +38,7 @@ RECON_DIST = ["bernoulli", "laplace", "gaussian"]        # losses.py:18
 DIP_LOSSES = ["dipI", "dipII"]                           # DIP-VAE-I / II (Kumar et al. 2018): not in the reference, so not in LOSSES
 INFO_LOSSES = ["infovae"]                                # InfoVAE / MMD-VAE (Zhao et al. 2019): not in the reference either
 WEAK_LOSSES = ["adagvae", "adamlvae"]                    # Ada-GVAE / Ada-ML-VAE on image pairs (Locatello et al. 2020): nor these
+SEMI_LOSSES = ["s2vae"]                                  # S2-beta-VAE on a few labelled images (Locatello et al. 2020, "Few Labels"): nor this
 
 
 def get_loss_f(loss_name, **kwargs_parse):
@@ -64,6 +67,14 @@ def get_loss_f(loss_name, **kwargs_parse):
     elif loss_name in WEAK_LOSSES:
         return WeakVaeLoss(aggregation="gvae" if loss_name == "adagvae" else "mlvae", beta=kwargs_parse.get("weak_beta", 1),
                            **kwargs_all)
+    elif loss_name in SEMI_LOSSES:
+        return SemiSupervisedVaeLoss(lat_sizes=kwargs_parse["lat_sizes"], sup_loss=kwargs_parse.get("sup_loss", "xent"),
+                                     gamma_sup=kwargs_parse.get("gamma_sup", 1.), beta=kwargs_parse.get("s2_beta", 4),
+                                     sup_reduction=kwargs_parse.get("sup_reduction", "sum"),
+                                     sup_anneal=kwargs_parse.get("sup_anneal", "fixed"),
+                                     sup_anneal_steps=kwargs_parse.get("sup_anneal_steps", 0),
+                                     sup_factors=kwargs_parse.get("sup_factors"), latent_dim=kwargs_parse.get("latent_dim"),
+                                     n_data=kwargs_parse.get("n_data"), **kwargs_all)
     else:
         assert loss_name not in LOSSES
         raise ValueError("Uknown loss : {}".format(loss_name))
@@ -481,6 +492,40 @@ class _MmdFn(torch.autograd.Function):
     def backward(ctx, gout):
         (dz,) = ctx.saved_tensors
         return dz * gout, None, None, None, None
+
+
+def _semi_launches(mu, rows, K, table, kind, reduction, w_ptr, ws, dmu, out, loss_io, stream):
+    """The two launches of libdvae_semi_hip.so (include/dvae_semi_hip.h) on a split [n, D] batch of posterior means and its row
+    numbers (negative: unlabelled); table: the (sizes, strides) ctypes arrays of _semilib.factor_table, whose host addresses the
+    calls take; w_ptr: the DEVICE address of the term's weight; dmu None: the value only.  Through record_py: a recorded plan
+    re-issues them with these arguments, a hipGraph captures them."""
+    n, D = mu.shape
+    sizes, strides = ctypes.addressof(table[0]), ctypes.addressof(table[1])
+    record_py(_semilib.call, "dvae_semi_partials", ptr(mu), 0, ptr(rows), n, D, K, sizes, strides, kind, ptr(ws), stream)
+    record_py(_semilib.call, "dvae_semi_grad", ptr(mu), 0, ptr(rows), n, D, K, sizes, strides, kind, reduction, w_ptr, ptr(ws),
+              ptr(dmu), ptr(out), loss_io, stream)
+
+
+class _SemiFn(torch.autograd.Function):
+    """The supervised regulariser R_sup(mu, rows) of SemiSupervisedVaeLoss (weight 1) -> 0-d tensor; the value and the gradient
+    come from the same two launches as in the fused step, so backward only scales what forward saved."""
+
+    @staticmethod
+    def forward(ctx, mu, rows, K, table, kind, reduction):
+        mu, rows = mu.contiguous(), rows.contiguous()
+        n, D = mu.shape
+        f64 = lambda m: torch.empty(m, dtype=torch.float64, device=mu.device)
+        ws, out = f64(_semilib.ws_doubles(n, D, K)), f64(_semilib.out_doubles(D, K))
+        one = torch.ones(1, dtype=torch.float32, device=mu.device)
+        dmu = torch.empty_like(mu)
+        _semi_launches(mu, rows, K, table, kind, reduction, ptr(one), ws, dmu, out, None, _stream())
+        ctx.save_for_backward(dmu)
+        return out[0].float()
+
+    @staticmethod
+    def backward(ctx, gout):
+        (dmu,) = ctx.saved_tensors
+        return dmu * gout, None, None, None, None, None
 
 
 class _PairAggregate:
@@ -1035,6 +1080,184 @@ class WeakVaeLoss(_SingleOptimizerLoss):
             "WeakVaeLoss has no loss(data, recon, latent_dist, ...) form: the pairs are aggregated BEFORE z is sampled, so a "
             "reconstruction made from the un-aggregated posterior cannot carry the loss.  Train with fused_step (the native "
             "Trainer does), or build the loss of a model of your own on adaptive_group_posterior(mu, logvar, aggregation)")
+
+
+class SemiSupervisedVaeLoss(_SingleOptimizerLoss):
+    """S2-beta-VAE (Locatello et al. 2020, "Disentangling Factors of Variation Using Few Labels"; disentanglement_lib's
+    semi_supervised_vae.py -- the reference has no counterpart): beta-VAE on the whole batch plus a supervised regulariser on
+    the few rows of the batch whose factors of variation are known.
+
+        loss = rec + anneal * beta * KL + w_t * R_sup(mu[labelled], labels)
+
+    rec and KL are BetaHLoss's, means over ALL rows of the batch, and steps_anneal acts on the KL term as there.  R_sup runs
+    over the labelled rows only and reads the posterior MEANS.  The data set enumerates its factors ``lat_sizes`` by row number
+    in row-major order (dSprites, 3D shapes, Cars3D, ...): ``labels`` is int64 [B] on the device, the row number of every image
+    of the batch, NEGATIVE for an unlabelled one, and the value index of factor j of row r is (r // stride_j) % size_j -- a
+    label tensor never exists.  Factor ``sup_factors[k]`` is tied to latent k, K = len(sup_factors) <= latent_dim and K <= 8;
+    the default is every factor with two values or more, in the order of lat_sizes.  With y_ik = value_ik / size_k:
+
+      sup_loss "xent"  sum_i sum_{k<K} BCE-with-logits(mu_ik, y_ik), in the stable form max(x, 0) - x y + log1p(exp(-|x|)); the
+                       gradient is sigmoid(mu_ik) - y_ik;
+      sup_loss "l2"    sum_i sum_{k<K} (mu_ik - y_ik)^2;
+      sup_loss "cov"   sum_{(d, k), d != k} C_dk^2 with C [D, K] the biased cross-covariance of mu and the factor value INDICES
+                       (not normalised, as in disentanglement_lib) over the labelled rows; the entries d = k are left out; the
+                       gradient is (2 / n_lab) sum_{k != d} C_dk (v_ik - mean v_k), so every one of the D latents receives one.
+
+    sup_reduction "sum" (disentanglement_lib's default) or "mean": xent and l2 divided by the number of labelled rows, on the
+    device (cov is a function of means already and is the same under both).  w_t is gamma_sup (sup_anneal "fixed"), or
+    linear_annealing(0, gamma_sup, step, sup_anneal_steps) in training (sup_anneal "anneal"; evaluation: gamma_sup); the kernels
+    read it from the step's staged coefficient buffer, so a replayed plan or hipGraph sees this step's value.  With no labelled
+    row in the batch R_sup = 0 and every gradient of it is an exact zero; with ``labels=None`` the two launches are skipped
+    and the step is BetaHLoss's.  `sup_loss` logs R_sup (after the reduction, without w_t), `n_labelled` the labelled rows.
+
+    NOT built: disentanglement_lib's "embed" regulariser, the learnt scale of its l2 form, its "fine_tune" annealer, S2 on top
+    of the FactorVAE / beta-TCVAE / DIP terms, and binned or noisy labels (labels are the exact factor values).  The labelled
+    rows couple the batch: data-parallel steps are not built (fused_step raises under a communicator of more than one rank)."""
+    KIND = _lib.LOSS_BETAH
+    STORED = (('recon_loss', _lib.S_REC), ('kl_loss', _lib.S_KL), ('sup_loss', None), ('n_labelled', None), ('loss', _lib.S_LOSS))
+    takes_labels = True           # Trainer / Evaluator pass the second item of a batch as fused_step(..., labels=)
+
+    def __init__(self, lat_sizes, sup_loss="xent", gamma_sup=1., beta=4, sup_reduction="sum", sup_anneal="fixed",
+                 sup_anneal_steps=0, sup_factors=None, latent_dim=None, n_data=None, **kwargs):
+        super().__init__(**kwargs)
+        if sup_loss not in _semilib.KINDS:
+            raise ValueError("sup_loss must be one of {}, got {!r}".format(sorted(_semilib.KINDS), sup_loss))
+        if sup_reduction not in _semilib.REDUCTIONS:
+            raise ValueError("sup_reduction must be one of {}, got {!r}".format(sorted(_semilib.REDUCTIONS), sup_reduction))
+        if sup_anneal not in ("fixed", "anneal"):
+            raise ValueError("sup_anneal must be 'fixed' or 'anneal', got {!r}".format(sup_anneal))
+        self.lat_sizes = tuple(int(s) for s in lat_sizes)
+        if not self.lat_sizes or min(self.lat_sizes) < 1:
+            raise ValueError("lat_sizes must be positive factor sizes, got {!r}".format(lat_sizes))
+        n_rows = 1
+        for s in self.lat_sizes:
+            n_rows *= s
+        if n_data is not None and n_rows != int(n_data):
+            raise ValueError("lat_sizes {} enumerate {} images, the data set has {}".format(self.lat_sizes, n_rows, int(n_data)))
+        if sup_factors is None:
+            sup_factors = [j for j, s in enumerate(self.lat_sizes) if s >= 2]
+        self.factors = tuple(int(j) for j in sup_factors)
+        if not self.factors or len(set(self.factors)) != len(self.factors) or \
+                not all(0 <= j < len(self.lat_sizes) for j in self.factors):
+            raise ValueError("sup_factors must be distinct indices into lat_sizes {} (at least one), got {!r}".format(
+                self.lat_sizes, sup_factors))
+        if len(self.factors) > _semilib.MAX_K:
+            raise ValueError("at most {} supervised factors, got {}".format(_semilib.MAX_K, len(self.factors)))
+        self.sup_loss, self.sup_reduction, self.sup_anneal = sup_loss, sup_reduction, sup_anneal
+        self.gamma_sup, self.sup_anneal_steps, self.beta = float(gamma_sup), int(sup_anneal_steps), beta
+        self._table = _semilib.factor_table(self.lat_sizes, self.factors)      # host arrays: recorded launches hold their addresses
+        self._semi = {}
+        self._labelled_now = False     # whether the step under way has a rows tensor: its launches exist, `out` is this step's
+        if latent_dim is not None:
+            self._check_dims(1, int(latent_dim))
+
+    @property
+    def n_factors(self):
+        return len(self.factors)
+
+    def _check_dims(self, rows, D):
+        """What a batch has to satisfy, before any device work."""
+        if self.n_factors > D:
+            raise ValueError("{} supervised factors need latent_dim >= {} (factor k is tied to latent k), got {}".format(
+                self.n_factors, self.n_factors, D))
+        if D > _semilib.MAX_D:
+            raise ValueError("the semi-supervised loss takes latent_dim <= {}, got {}".format(_semilib.MAX_D, D))
+        if not 1 <= rows <= _semilib.MAX_ROWS:
+            raise ValueError("the semi-supervised loss takes batches of 1 to {} rows, got {}".format(_semilib.MAX_ROWS, rows))
+
+    @staticmethod
+    def _check_labels(labels, rows, device):
+        if not (torch.is_tensor(labels) and labels.dtype == torch.int64 and tuple(labels.shape) == (rows,)):
+            raise ValueError("labels must be an int64 tensor of {} row numbers (negative: unlabelled), got {!r}".format(
+                rows, (getattr(labels, "dtype", None), tuple(getattr(labels, "shape", ()))) if torch.is_tensor(labels) else labels))
+        if labels.device != device:
+            raise ValueError("labels must lie on the batch's device {}, got {}".format(device, labels.device))
+
+    def sup_weight(self, is_train):
+        """w_t of the step under way."""
+        if self.sup_anneal == "fixed" or not is_train:
+            return self.gamma_sup
+        return linear_annealing(0, self.gamma_sup, self.n_train_steps, self.sup_anneal_steps)
+
+    def _coefs(self, is_train):
+        # w_t rides in the GAMMA slot of the staged coefficients: the BETAH epilogue and FC chain do not read it (loss.hip:
+        # loss_finalize_body; latent_math.h: load_tc_coef is the beta-TCVAE estimator's)
+        anneal = linear_annealing(0, 1, self.n_train_steps, self.steps_anneal) if is_train else 1
+        return dict(ANNEAL=anneal, BETA=self.beta, GAMMA=self.sup_weight(is_train))
+
+    def _semi_buf(self, device, name, n):
+        """fp64 buffers of the two launches, allocated once: ("ws", B, D) the workspace, ("out", D) value, count and C."""
+        t = self._semi.get((device,) + name)
+        if t is None:
+            _lib.note_alloc()
+            t = self._semi[(device,) + name] = torch.zeros(n, dtype=torch.float64, device=device)
+        return t
+
+    def _regulariser(self, buf, sc, B, D, is_train, stream, rows=None):
+        """w_t R_sup on top of the epilogue's rec + anneal * beta * KL in sc.scal[S_LOSS] (dvae_semi_grad's loss_io: no third
+        launch) -> the gradient for the FC chain; evaluation: the value only; no rows: nothing."""
+        if rows is None:
+            return None
+        K = self.n_factors
+        ws = self._semi_buf(sc.device, ("ws", B, D), _semilib.ws_doubles(B, D, K))
+        out = self._semi_buf(sc.device, ("out", D), _semilib.out_doubles(D, K))
+        dmu = sc.latent("semi_dmu", B, D) if is_train else None
+        _semi_launches(buf.mu, rows, K, self._table, _semilib.KINDS[self.sup_loss], _semilib.REDUCTIONS[self.sup_reduction],
+                       ptr(sc.coef) + 4 * _lib.C_GAMMA, ws, dmu, out, ptr(sc.scal) + 4 * _lib.S_LOSS, stream)
+        return dmu, None
+
+    def _replay_key(self, model, data, injected, pol):
+        return super()._replay_key(model, data, injected, pol) + (
+            self.sup_loss, self.sup_reduction, self.sup_anneal, self.sup_anneal_steps, self.gamma_sup, self.lat_sizes,
+            self.factors, self._labelled_now)
+
+    def _store(self, storer, sc, D, keys=None):
+        if storer is None:
+            return
+        vals = sc.scal.tolist()
+        sup, n_lab = 0.0, 0.0
+        if self._labelled_now:
+            sup, n_lab = self._semi[(sc.device, "out", D)][:2].tolist()     # fp64 [R, n_lab, C]: a second small copy, on logging steps only
+        for key, slot in self.STORED:
+            if key == 'kl_loss':
+                self._store_kl(storer, vals, D)
+            else:
+                storer[key].append({'sup_loss': sup, 'n_labelled': n_lab}[key] if slot is None else vals[slot])
+
+    def fused_step(self, data, model, optimizer, storer, eps=None, labels=None):
+        """labels: int64 [B] on the batch's device (row numbers, negative: unlabelled), or None: all unlabelled, and the
+        regulariser's launches are skipped.  The rows go through _run_step's static buffers as eps does: a recorded plan reads
+        them from a buffer that is refreshed every step."""
+        if self._world()[0] > 1:
+            raise NotImplementedError(
+                "S2-VAE under data parallelism is not built: the labelled rows of the GLOBAL batch share one count (and, for "
+                "cov, one covariance), so a sharded step has to gather the means and rows of every rank first")
+        self._check_dims(data.shape[0], model.latent_dim)
+        if labels is not None:
+            self._check_labels(labels, data.shape[0], data.device)
+        self._labelled_now = labels is not None
+        return super().fused_step(data, model, optimizer, storer, eps=eps, extra_noise=[("s2_rows", labels)])
+
+    def __call__(self, data, recon_data, latent_dist, is_train, storer, labels=None, **kwargs):
+        storer = self._pre_call(is_train, storer)
+        sc = self.scratch(recon_data.device)
+        rec_loss = _reconstruction_loss(data, recon_data, storer=storer, distribution=self.rec_dist, scratch=sc)
+        kl_loss = _kl_normal_loss(*latent_dist, storer, scratch=sc)
+        mu = latent_dist[0]
+        self._check_dims(mu.shape[0], mu.shape[1])
+        anneal_reg = linear_annealing(0, 1, self.n_train_steps, self.steps_anneal) if is_train else 1
+        loss = rec_loss + anneal_reg * (self.beta * kl_loss)
+        sup_loss = None
+        if labels is not None:
+            self._check_labels(labels, mu.shape[0], mu.device)
+            sup_loss = _SemiFn.apply(mu, labels, self.n_factors, self._table, _semilib.KINDS[self.sup_loss],
+                                     _semilib.REDUCTIONS[self.sup_reduction])
+            loss = loss + self.sup_weight(is_train) * sup_loss
+        if storer is not None:
+            storer['sup_loss'].append(0.0 if sup_loss is None else sup_loss.item())
+            storer['n_labelled'].append(0.0 if labels is None else float((labels >= 0).sum().item()))
+            storer['loss'].append(loss.item())
+        return loss
 
 
 class BetaBLoss(_SingleOptimizerLoss):

@@ -76,11 +76,14 @@ class Trainer():
         pending, total = [], 0.0
         bar = tqdm(total=n_iter, desc="Epoch {}".format(epoch + 1), leave=False, disable=not self.is_progress_bar)
         try:
-            for batch, _labels in data_loader:
+            takes_labels = getattr(self.loss_f, "takes_labels", False)
+            for batch, labels in data_loader:
+                # a loss that takes labels (SemiSupervisedVaeLoss) receives the batch's second item; every other loss is called as before
+                extra = dict(labels=labels) if takes_labels else {}
                 if on_device:
-                    pending.append(self._train_iteration_async(batch, storer).clone())
+                    pending.append(self._train_iteration_async(batch, storer, **extra).clone())
                 else:
-                    value = self._train_iteration(batch, storer)
+                    value = self._train_iteration(batch, storer, **extra)
                     total += value
                     bar.set_postfix(loss=value)
                 bar.update()
@@ -95,26 +98,34 @@ class Trainer():
         return (isinstance(self.model, VAE) and isinstance(self.loss_f, BaseLoss)
                 and next(self.model.parameters()).device.type == "cuda")
 
-    def _train_iteration_async(self, data, storer):
+    def _labels_kw(self, labels):
+        """fused_step's / the loss call's `labels=` for a loss that takes labels: the batch's second item on the device (anything
+        that is not a tensor -- the 0 of an unlabelled loader -- means "all unlabelled")."""
+        if not getattr(self.loss_f, "takes_labels", False):
+            return {}
+        return dict(labels=labels.to(self.device, non_blocking=True) if torch.is_tensor(labels) else None)
+
+    def _train_iteration_async(self, data, storer, labels=None):
         """One native training iteration; returns the loss as a 0-d DEVICE tensor (no sync)."""
         data = data.to(self.device, non_blocking=True)
         if not isinstance(self.loss_f, FactorKLoss):
-            return self.loss_f.fused_step(data, self.model, self.optimizer, storer)
+            return self.loss_f.fused_step(data, self.model, self.optimizer, storer, **self._labels_kw(labels))
         if self.model.training:
             # the reference runs (and discards) a full-batch forward before the ValueError
             # (training.py:153): keep its N(0,1) draw so the device RNG stream matches (Q4)
             torch.randn(data.shape[0], self.model.latent_dim, dtype=torch.float32, device=data.device)
         return self.loss_f.call_optimize(data, self.model, self.optimizer, storer)
 
-    def _train_iteration(self, data, storer):
+    def _train_iteration(self, data, storer, labels=None):
         if self._is_native():
-            return self._train_iteration_async(data, storer).item()
+            return self._train_iteration_async(data, storer, **({} if labels is None else dict(labels=labels))).item()
         # any other model / loss combination: the reference's control flow, in which a loss that needs its
         # own optimisation schedule announces itself with ValueError
         data = data.to(self.device)
         try:
             recon, latent_dist, latent_sample = self.model(data)
-            loss = self.loss_f(data, recon, latent_dist, self.model.training, storer, latent_sample=latent_sample)
+            loss = self.loss_f(data, recon, latent_dist, self.model.training, storer, latent_sample=latent_sample,
+                               **self._labels_kw(labels))
         except ValueError:
             return self.loss_f.call_optimize(data, self.model, self.optimizer, storer).item()
         self.optimizer.zero_grad()
